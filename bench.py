@@ -2,6 +2,7 @@
 """Headline benchmark: pair-comparisons/sec of the all-pairs match loop on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c2low|c3|c4|c5|c5w|term] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -39,9 +40,9 @@ The JSON line carries, besides the driver's contract fields:
   cpu_baseline  the oracle's restatement of the reference's loop, 1 core, bounded sample
   c2 c2low c4 c5 c5w term   (default `--workload all`) every other BASELINE config, configs[4] on word-like text
                 and the reference's default configuration, timed in the SAME invocation after the headline, each
-                under the same contract (W warm-up steps, K timed steps between fences; c5 / c5w: min(K, 5) / min(K, 3)
-                steps of six 500k x 500k grids) with its own value / ms_per_step / steps / kernel_ms / roofline /
-                exhaustive / cpu_baseline.  N = 1 runs all six; N > 1 runs the configs BASELINE.json quotes on 8
+                under the same contract (W warm-up steps, then SUB_STEPS timed steps between fences whatever K is: 20;
+                c5 / c5w: 5 / 3 steps of six 500k x 500k grids) with its own value / ms_per_step / steps / kernel_ms /
+                roofline / exhaustive / cpu_baseline.  N = 1 runs all six; N > 1 runs the configs BASELINE.json quotes on 8
                 GPUs (c4, c5 and c5w: left rows divided over the ranks, "strong").  `--workload <one>` times that
                 workload alone.
   config.sub    the sub-records' numbers once more, as plain scalars under the `config` object (a parser that keeps
@@ -69,6 +70,11 @@ for _p in (str(ROOT), str(ROOT / "napkon-string-matching_amd")):
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2  # G wave64-instructions/s: 1024 SIMD-32 x 2.4 GHz, >= 2 cycles per instruction
 BYTES_PER_PAIR = 128  # two 64-byte operand rows
+# --steps K sets the timed steps of the measured workload and nothing else, so that a run grows by K x ms_per_step: the
+# sub-records of the default run and the auxiliary timings (kernel-only launches, the exhaustive run) do fixed work
+SUB_STEPS = {"c2": 20, "c2low": 20, "c4": 20, "c5": 5, "c5w": 3, "term": 20}
+KERNEL_REPS = 20
+EXHAUSTIVE_STEPS = 5
 
 
 def parse_args():
@@ -103,6 +109,10 @@ def parse_args():
                     help="if RCCL cannot be brought up on every rank, run the exchange staged through host memory "
                          "instead of exiting non-zero (the JSON's config.exchange says which one ran)")
     ap.add_argument("--no-c4", action="store_true", help="(kept for old command lines) the headline alone, no sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hits every grid of the last step returned as "
+                         "DIR/<workload>[_<grid>]_hits.npy (float64 rows score, i, j in canonical order; a seeded sample "
+                         "above 65536 hits) and DIR/<...>_count.npy (the grid's full hit count)")
     return ap.parse_args()
 
 
@@ -351,6 +361,42 @@ class Comm:
             self.dist.destroy_process_group()
 
 
+class OutputDump:
+    """``--dump-outputs DIR``: what the timed path computed, for comparing two builds output for output.  Per grid the
+    hits a caller receives (score, left row, right row) in the library's canonical order; grids with more than
+    SAMPLE hits contribute a fixed seeded sample of them (order kept) and their full count."""
+
+    SAMPLE = 1 << 16      # 1.5 MiB per grid: the default run's 23 grids stay under LIMIT
+    LIMIT = 64 * 10 ** 6  # bytes, all arrays together
+
+    def __init__(self, directory):
+        self.dir = Path(directory)
+        self.arrays = {}
+
+    def add_hits(self, name, buf, n):
+        import numpy as np
+
+        assert name + "_hits" not in self.arrays, name
+        kept = min(int(n), buf.capacity)
+        rec = buf.records[:kept].cpu().numpy()
+        ij = rec.view(np.int32).reshape(kept, 4)
+        hits = np.stack([rec[:, 0], ij[:, 2].astype(np.float64), ij[:, 3].astype(np.float64)], axis=1)
+        if kept > self.SAMPLE:
+            hits = hits[np.sort(np.random.default_rng(0).choice(kept, self.SAMPLE, replace=False))]
+        self.arrays[name + "_hits"] = hits
+        self.arrays[name + "_count"] = np.array([n], dtype=np.float64)
+
+    def write(self):
+        import numpy as np
+
+        total = sum(a.nbytes for a in self.arrays.values())
+        if total > self.LIMIT:
+            raise SystemExit(f"--dump-outputs: {total} bytes exceed the {self.LIMIT} byte limit")
+        self.dir.mkdir(parents=True, exist_ok=True)
+        for name, a in self.arrays.items():
+            np.save(self.dir / f"{name}.npy", a)
+
+
 def csrc_hash():
     """sha256 (16 hex digits) of the kernel sources: profiles are stamped with it (tools/pmc_to_json.py)."""
     h = hashlib.sha256()
@@ -569,11 +615,12 @@ def cpu_baseline(work, budget_pairs):
     }
 
 
-def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, words=False):
+def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, words=False, dump=None):
     """BASELINE configs[4]: three hap / pop / suep shaped cohorts, levels mode (compare_terms), categories
     filtered, intersection_vs_union then fuzzy_match for every cohort pair.  One step = the six grids.
     The left rows of every cohort pair are divided over the ranks (total work fixed: "strong").
-    ``words`` = the "c5w" workload: the same shape over 20 000 distinct word-like tokens, at the CACHE threshold 0.5."""
+    ``words`` = the "c5w" workload: the same shape over 20 000 distinct word-like tokens, at the CACHE threshold 0.5.
+    ``dump``: an OutputDump that receives the six grids' hits of the step that follows the timed ones."""
     import numpy as np
     import torch
 
@@ -624,6 +671,7 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
                                                    ca["cat"][lo:hi], cb["cat"], mode, left_offset=lo)
         grids.append(("jaccard", (lt, rt), (lt.struct(), rt.struct()), lt.category_mode))
         grids.append(("indel", (li, ls, ri, rs), (li.struct(), ls.struct(), ri.struct(), rs.struct()), li.category_mode))
+    grid_names = [f"{a}_{b}_{kind}" for a, b in pairs for kind in ("jaccard", "indel")]
     torch.cuda.synchronize(device)
     t_encode = time.perf_counter() - t0
 
@@ -688,7 +736,7 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
             cap <<= 1
         return cap
 
-    def measure(n_steps, n_warmup):
+    def measure(n_steps, n_warmup, dump_as=None):
         size_workspace()
         capacity = probe_capacity()
         bufs = [grid.HitBuffer(capacity, device) for _ in range(2)]
@@ -700,7 +748,7 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
         counts = []
 
         def step(record=False):
-            for g in grids:
+            for g, g_name in zip(grids, grid_names):
                 k = turn[0] & 1
                 turn[0] += 1
                 b = bufs[k]
@@ -715,6 +763,8 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
                     pending[k] = comm.gather_hits(b, gathered[k], async_op=True)
                 if record:
                     counts.append(int(b.count.item()))
+                    if dump_as is not None:
+                        dump.add_hits(f"{dump_as}_{g_name}", b, counts[-1])
 
         def fence():
             for k in (0, 1):
@@ -757,7 +807,7 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
         del bufs, gathered
         return out
 
-    m = measure(steps, warmup)
+    m = measure(steps, warmup, name if dump is not None else None)
     dt, counts, ms_indel, ms_jac = m["dt"], m["counts"], m["ms_indel"], m["ms_jac"]
     split_used = state["ws"] is not None
     pairs_per_step = 2 * len(pairs) * rows * rows  # both score functions over every cohort pair
@@ -824,7 +874,7 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
     if words and threshold == default_threshold and not args.no_extras:
         # ... and the same grids at config.yml's score threshold (what the result keeps after the cache filter)
         state["threshold"] = 0.7
-        m7 = measure(max(1, min(steps, 2)), 1)
+        m7 = measure(max(1, min(steps, 2)), 1, f"{name}_at_score_threshold" if dump is not None else None)
         result["at_score_threshold"] = {
             "threshold": 0.7, "steps": max(1, min(steps, 2)), "ms_per_step": m7["dt"] / max(1, min(steps, 2)) * 1e3,
             "fuzzy_grids_ms_per_step": m7["ms_indel"], "jaccard_grids_ms_per_step": m7["ms_jac"],
@@ -859,9 +909,10 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
 
 
 def run_raw(args, comm, device, name, rows=0, right_rows=0, threshold=None, steps=None, warmup=None, extras=True,
-            cpu_scale=1.0):
+            cpu_scale=1.0, dump=None):
     """One RAW-mode / term workload under the contract: W warm-up steps, K timed steps between
-    barrier + synchronize fences, MAX over the ranks.  Returns the JSON object."""
+    barrier + synchronize fences, MAX over the ranks.  Returns the JSON object.  ``dump``: an OutputDump that
+    receives the hits of the last timed step."""
     import torch
 
     from napkon_string_matching_amd import _lib, grid
@@ -964,6 +1015,9 @@ def run_raw(args, comm, device, name, rows=0, right_rows=0, threshold=None, step
     for _ in range(warmup):
         step(True)
     dt = timed(steps, True)
+    if dump is not None:  # before anything below reuses the hit buffers
+        last = bufs[(step_no[0] - 1) & 1]
+        dump.add_hits(name, last, int(last.count.item()))
     n_hits = int(buf.count.item())
     if n_hits > buf.capacity:
         raise SystemExit(f"hit buffer overflow ({n_hits} > {buf.capacity}); raise --capacity")
@@ -983,7 +1037,7 @@ def run_raw(args, comm, device, name, rows=0, right_rows=0, threshold=None, step
         torch.cuda.synchronize(device)
         return ev0.elapsed_time(ev1) / reps
 
-    k_ms = kernel_ms(True, max(3, steps))
+    k_ms = kernel_ms(True, KERNEL_REPS)
     alg_bytes = work.n * work.m * work.bytes_per_pair
     compulsory = work.left.nbytes() + work.right.nbytes() + n_hits * 16
     result = {
@@ -1023,7 +1077,7 @@ def run_raw(args, comm, device, name, rows=0, right_rows=0, threshold=None, step
     }
     if extras and not args.no_extras:
         # exhaustive variant (prune off): fewer repetitions, it is the slow one
-        ex_steps = max(2, min(steps, 5))
+        ex_steps = EXHAUSTIVE_STEPS
         step(False)
         dt_ex = timed(ex_steps, False)
         k_ms_ex = kernel_ms(False, ex_steps)
@@ -1067,6 +1121,9 @@ def main():
     device = torch.device("cuda", local_rank)
     comm = Comm(args, rank, world, device)
     assert comm.world == args.gpus
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs: single-process runs only (--gpus 1)")
+    dump = OutputDump(args.dump_outputs) if args.dump_outputs else None
 
     def release():
         import gc
@@ -1075,12 +1132,12 @@ def main():
         torch.cuda.empty_cache()
 
     if args.workload in ("c5", "c5w"):
-        result = run_c5(args, comm, device, words=args.workload == "c5w")
+        result = run_c5(args, comm, device, words=args.workload == "c5w", dump=dump)
     elif args.workload != "all":
-        result = run_raw(args, comm, device, args.workload, args.rows, args.right_rows, args.threshold)
+        result = run_raw(args, comm, device, args.workload, args.rows, args.right_rows, args.threshold, dump=dump)
     else:
         # the headline: BASELINE configs[2], the largest configuration quoted on one GPU ...
-        result = run_raw(args, comm, device, "c3", args.rows, args.right_rows, args.threshold)
+        result = run_raw(args, comm, device, "c3", args.rows, args.right_rows, args.threshold, dump=dump)
         # ... and every other workload under the same clock, attached as sub-records.  N > 1: the configs
         # BASELINE.json quotes on 8 GPUs (c4, c5; c5w = c5 on word-like text), left rows divided over the ranks.
         names = () if args.no_c4 else (("c2", "c2low", "c4", "c5", "c5w", "term") if world == 1 else ("c4", "c5", "c5w"))
@@ -1090,12 +1147,12 @@ def main():
             release()
             t_sub = time.perf_counter()
             if name in ("c5", "c5w"):
-                sub = run_c5(args, comm, device, steps=max(1, min(args.steps, 5 if name == "c5" else 3)), warmup=1, sub=True,
-                             words=name == "c5w")
+                sub = run_c5(args, comm, device, steps=SUB_STEPS[name], warmup=1, sub=True, words=name == "c5w", dump=dump)
             else:
                 # c2low / c4 share c2's CPU restatement (same function, same corpus generator): a short sample
                 sub = run_raw(args, comm, device, name, args.rows, 0 if name == "c4" else args.right_rows, None,
-                              extras=world == 1, cpu_scale=0.25 if name in ("c2low", "c4") else 1.0)
+                              steps=SUB_STEPS[name], extras=world == 1, cpu_scale=0.25 if name in ("c2low", "c4") else 1.0,
+                              dump=dump)
             rec = {k: sub[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "scaling", "dtype", "config",
                                        "roofline", "exhaustive", "cpu_baseline", "at_score_threshold") if k in sub}
             rec["workload"] = sub["config"]["workload"]
@@ -1119,6 +1176,8 @@ def main():
             result["config"]["sub"] = mirror
     if world > 1 and comm.dev_group is not None:
         assert comm.rccl_ranks == world, f"RCCL saw {comm.rccl_ranks} ranks of {world}"
+    if dump is not None:
+        dump.write()
     if rank == 0:
         print(json.dumps(result))
     comm.close()

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures in this directory by running THE REFERENCE ITSELF.
 
-Run in the build container only (it needs /root/reference):
+Run where a checkout of the reference exists, with its path as the argument:
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py <reference checkout>
 
 The reference's hot path imports two third-party packages that are absent offline:
 ``rapidfuzz`` (score_functions.py:3) and ``nltk`` (comparable_data.py:7-10,20-21, which
@@ -19,6 +19,7 @@ Everything written here is DATA (inputs and the reference's outputs); no referen
 source text is stored.  The fixtures are what ``tests/test_oracle_golden.py`` pins the
 oracle with, and what the GPU parity tests replay through the HIP path.
 """
+import gzip
 import json
 import random
 import sys
@@ -28,10 +29,9 @@ import zlib
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
-REFERENCE = Path("/root/reference")
 
 
-def install_stand_ins():
+def install_stand_ins(reference):
     rf = types.ModuleType("rapidfuzz")
     fz = types.ModuleType("rapidfuzz.fuzz")
 
@@ -56,7 +56,7 @@ def install_stand_ins():
     sys.modules.update(
         {"rapidfuzz": rf, "rapidfuzz.fuzz": fz, "nltk": nl, "nltk.corpus": corpus, "nltk.tokenize": tok}
     )
-    sys.path.insert(0, str(REFERENCE))
+    sys.path.insert(0, str(reference))
 
 
 def dump(name, payload):
@@ -132,8 +132,8 @@ def run_compare(Questionnaire, Mapping, case):
     return out
 
 
-def main():
-    install_stand_ins()
+def main(reference):
+    install_stand_ins(reference)
     from napkon_string_matching.compare.score_functions import intersection_vs_union, join_sorted
     from napkon_string_matching.types.comparable_data import (
         ComparableData,
@@ -404,6 +404,48 @@ def main():
     dump("analyse.json", {"cohorts": cohorts6, "compare_kwargs": kw6, "steps": [list(s_) for s_ in steps],
                           "rows": expected_rows, "analysis": matcher._analyse()})
 
+    # -- 7. gen_comparable / compare on random cohort frames (tests/support/random_frames.py, replayed by seed) --------
+    sys.path.insert(0, str(HERE.parent))
+    from support import random_frames as rf
+
+    def outcome(fn, inputs):
+        entry = {"inputs_crc32": rf.inputs_crc32(*inputs)}
+        try:
+            frame = fn()
+        except Exception as exc:  # the exception TYPE is part of the contract
+            entry["raises"] = type(exc).__name__
+            return entry
+        entry["frame"] = {
+            "index": [int(v) for v in frame.index],
+            "columns": list(frame.columns),
+            "rows": [[float(v) if col == "MatchScore" else v for col, v in zip(frame.columns, row)]
+                     for row in frame.itertuples(index=False)],
+        }
+        return entry
+
+    gen7 = []
+    for seed in range(1, 1501):
+        left, right, wl, bl, kw, _kinds = rf.case(seed, score_funcs=("intersection_vs_union",), sizes=(0, 1, 4, 4, 12, 12, 25, 25))
+        gen7.append({"seed": seed, **outcome(lambda: Questionnaire(left.copy()).gen_comparable(
+            Questionnaire(right.copy()), Mapping(data=wl), Mapping(data=bl), **kw).dataframe(), (left, right, wl, bl, kw))})
+    compare7 = []
+    for seed in range(2001, 2401):
+        left, right, wl, bl, kw, _kinds = rf.case(seed, score_funcs=("intersection_vs_union",), sizes=(1, 4, 12, 25))
+        kw["cache_threshold"] = random.Random(seed).choice([None, 0.05, 0.3, 0.6])
+        ref_kw = dict(kw)
+        column = ref_kw.pop("compare_column")
+        with tempfile.TemporaryDirectory() as tmp:
+            compare7.append({"seed": seed, **outcome(lambda: Questionnaire(left.copy()).compare(
+                Questionnaire(right.copy()), Mapping(data=wl), Mapping(data=bl), column, cached=False,
+                cache_dir=Path(tmp) / "cache", **ref_kw).dataframe(), (left, right, wl, bl, kw))})
+    path = HERE / "random_frames.json.gz"
+    text = json.dumps({"gen_comparable": gen7, "compare": compare7}, separators=(",", ":")) + "\n"
+    path.write_bytes(gzip.compress(text.encode("utf-8"), compresslevel=9, mtime=0))
+    print("wrote", path.name)
+
+
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) != 2 or not Path(sys.argv[1]).is_dir():
+        raise SystemExit("usage: make_golden.py <reference checkout>")
+    main(Path(sys.argv[1]).resolve())

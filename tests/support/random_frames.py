@@ -1,6 +1,8 @@
 """Random cohort frames, mappings and gen_comparable keyword sets for differential tests
 (tools/fuzz_api.py on the GPU, tests/test_oracle_vs_reference.py against the reference itself)."""
+import json
 import random
+import zlib
 
 import pandas as pd
 
@@ -74,3 +76,10 @@ def frames_differ(got, want, tol: float):
         elif any(not (x == y or (x != x and y != y) or (x is None and y is None)) for x, y in zip(a, b)):
             return f"column {col} differs"
     return None
+
+
+def inputs_crc32(left, right, whitelist, blacklist, kwargs):
+    """Fingerprint of one case's inputs: a stored outcome is only valid for the inputs it was computed from."""
+    text = json.dumps([left.to_json(orient="split"), right.to_json(orient="split"), whitelist, blacklist,
+                       sorted((k, str(v)) for k, v in kwargs.items())])
+    return zlib.crc32(text.encode("utf-8"))

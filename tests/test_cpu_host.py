@@ -450,3 +450,36 @@ def test_wide_item_routing_cpu():
     assert {t for t, a, b in seen if wl[a] or wr[b]} == {"any"}
     want = sorted(((1.0 / (1 + a + 10 * b), a, b) for a in range(4) for b in range(3)), key=lambda h: (-h[0], h[1], h[2]))
     assert hits.as_tuples() == want
+
+
+def test_bench_output_dump_cpu(tmp_path):
+    """bench.py --dump-outputs on a host hit buffer: one float64 row (score, i, j) per hit in buffer order, the full
+    count beside it, a fixed sample (order kept) above OutputDump.SAMPLE, only the records the buffer holds."""
+    from unittest import mock
+
+    import torch
+
+    from napkon_string_matching_amd import grid
+
+    with mock.patch.dict(os.environ):  # (bench.py sets environment defaults for its own process when imported)
+        import bench
+    for n, capacity in ((5, 8), (bench.OutputDump.SAMPLE + 100, 1 << 17), (100, 50)):
+        buf = grid.HitBuffer(capacity, "cpu")
+        kept = min(n, capacity)
+        buf.records[:kept, 0] = torch.linspace(1.0, 0.5, kept, dtype=torch.float64)
+        ij = buf.records.view(torch.int32).view(-1, 4)
+        ij[:kept, 2] = torch.arange(kept, dtype=torch.int32)
+        ij[:kept, 3] = 3 * torch.arange(kept, dtype=torch.int32)
+        out = tmp_path / f"dump{n}"
+        dump = bench.OutputDump(out)
+        dump.add_hits("grid", buf, n)
+        dump.write()
+        hits, count = np.load(out / "grid_hits.npy"), np.load(out / "grid_count.npy")
+        assert sorted(p.name for p in out.iterdir()) == ["grid_count.npy", "grid_hits.npy"]
+        assert hits.dtype == count.dtype == np.float64 and count.tolist() == [n]
+        assert hits.shape == (min(kept, bench.OutputDump.SAMPLE), 3)
+        assert np.all(np.diff(hits[:, 1]) > 0) and np.array_equal(hits[:, 2], 3 * hits[:, 1])
+        assert np.array_equal(hits[:, 0], buf.records[hits[:, 1].astype(np.int64), 0].numpy())
+        again = bench.OutputDump(tmp_path / "again")
+        again.add_hits("grid", buf, n)
+        assert np.array_equal(again.arrays["grid_hits"], hits)

@@ -1,44 +1,59 @@
-"""The oracle's gen_comparable against THE REFERENCE ITSELF on random cohort frames (build container only:
-needs /root/reference; the reference is imported with the inert rapidfuzz / nltk stand-ins of
-tests/golden/make_golden.py, so only intersection_vs_union is exercised -- fuzzy_match stays unpinned).
+"""The oracle's gen_comparable and compare against what THE REFERENCE ITSELF returned on random cohort frames.
+tests/golden/random_frames.json.gz holds the reference's outcome per seed (tests/golden/make_golden.py section 7:
+the reference imported with the inert rapidfuzz / nltk stand-ins, so only intersection_vs_union is exercised --
+fuzzy_match stays unpinned); the inputs are regenerated here from the same seeds.
 The same generator drives tools/fuzz_api.py, which compares the GPU package with the oracle."""
-import sys
+import gzip
+import json
+import random
 from pathlib import Path
 
+import pandas as pd
 import pytest
 
-REFERENCE = Path("/root/reference")
-pytestmark = pytest.mark.skipif(not REFERENCE.exists(), reason="the reference checkout only exists in the build container")
+FIXTURE = Path(__file__).resolve().parent / "golden" / "random_frames.json.gz"
 
 
-def test_oracle_gen_comparable_matches_reference():
-    sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
-    import make_golden
+@pytest.fixture(scope="module")
+def reference_outcomes():
+    return json.loads(gzip.decompress(FIXTURE.read_bytes()).decode("utf-8"))
 
-    make_golden.install_stand_ins()
-    from napkon_string_matching.types.mapping import Mapping
-    from napkon_string_matching.types.questionnaire import Questionnaire
 
+def _expected(entry, inputs):
+    """(frame, exception type name) the reference produced for ``inputs``."""
+    from support import random_frames as rf
+
+    assert entry["inputs_crc32"] == rf.inputs_crc32(*inputs), (
+        f"seed {entry['seed']}: tests/support/random_frames.py no longer draws the inputs the fixture was made from")
+    if "raises" in entry:
+        return None, entry["raises"]
+    f = entry["frame"]
+    return pd.DataFrame(f["rows"], index=f["index"], columns=f["columns"]), None
+
+
+def _run(fn):
+    try:
+        return fn(), None
+    except Exception as exc:  # the exception TYPE is part of the contract
+        return None, exc
+
+
+def test_oracle_gen_comparable_matches_reference(reference_outcomes):
     from oracle import compare as oc
     from support import random_frames as rf
 
+    cases = reference_outcomes["gen_comparable"]
+    assert [c["seed"] for c in cases] == list(range(1, 1501))
     outcomes = {"frames": 0, "rows": 0}
-    for seed in range(1, 1501):
+    for entry in cases:
+        seed = entry["seed"]
         left, right, wl, bl, kw, _kinds = rf.case(seed, score_funcs=("intersection_vs_union",), sizes=(0, 1, 4, 4, 12, 12, 25, 25))
-
-        def run(fn):
-            try:
-                return fn(), None
-            except Exception as exc:  # the exception TYPE is part of the contract
-                return None, exc
-
-        want, want_exc = run(lambda: Questionnaire(left.copy()).gen_comparable(
-            Questionnaire(right.copy()), Mapping(data=wl), Mapping(data=bl), **kw).dataframe())
-        got, got_exc = run(lambda: oc.gen_comparable(left.copy(), right.copy(), wl, bl, **kw))
-        assert (want_exc is None) == (got_exc is None) and type(want_exc) is type(got_exc), (
-            f"seed {seed}: reference {want_exc!r} / oracle {got_exc!r}")
+        want, want_exc = _expected(entry, (left, right, wl, bl, kw))
+        got, got_exc = _run(lambda: oc.gen_comparable(left.copy(), right.copy(), wl, bl, **kw))
+        assert (want_exc is None) == (got_exc is None) and want_exc in (None, type(got_exc).__name__), (
+            f"seed {seed}: reference {want_exc} / oracle {got_exc!r}")
         if want_exc is not None:
-            outcomes[type(want_exc).__name__] = outcomes.get(type(want_exc).__name__, 0) + 1
+            outcomes[want_exc] = outcomes.get(want_exc, 0) + 1
             continue
         problem = rf.frames_differ(got, want, 0.0)
         assert problem is None, f"seed {seed}: {problem}"
@@ -48,40 +63,23 @@ def test_oracle_gen_comparable_matches_reference():
     print(outcomes)
 
 
-def test_oracle_compare_matches_reference(tmp_path):
+def test_oracle_compare_matches_reference(reference_outcomes):
     """``compare``: score at ``cache_threshold or score_threshold``, keep ``>= score_threshold``, order by
     score descending (the order of equal scores is the reference's quicksort's business: not compared)."""
-    import random
-
-    sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
-    import make_golden
-
-    make_golden.install_stand_ins()
-    from napkon_string_matching.types.mapping import Mapping
-    from napkon_string_matching.types.questionnaire import Questionnaire
-
     from oracle import compare as oc
     from support import random_frames as rf
 
+    cases = reference_outcomes["compare"]
+    assert [c["seed"] for c in cases] == list(range(2001, 2401))
     frames = rows = 0
-    for seed in range(2001, 2401):
+    for entry in cases:
+        seed = entry["seed"]
         left, right, wl, bl, kw, _kinds = rf.case(seed, score_funcs=("intersection_vs_union",), sizes=(1, 4, 12, 25))
-        rng = random.Random(seed)
-        kw["cache_threshold"] = rng.choice([None, 0.05, 0.3, 0.6])
-        ref_kw = dict(kw, cached=False, cache_dir=tmp_path / f"cache{seed}")
-        column = ref_kw.pop("compare_column")
-
-        def run(fn):
-            try:
-                return fn(), None
-            except Exception as exc:
-                return None, exc
-
-        want, want_exc = run(lambda: Questionnaire(left.copy()).compare(
-            Questionnaire(right.copy()), Mapping(data=wl), Mapping(data=bl), column, **ref_kw).dataframe())
-        got, got_exc = run(lambda: oc.compare(left.copy(), right.copy(), wl, bl, **kw))
-        assert (want_exc is None) == (got_exc is None) and type(want_exc) is type(got_exc), (
-            f"seed {seed}: reference {want_exc!r} / oracle {got_exc!r}")
+        kw["cache_threshold"] = random.Random(seed).choice([None, 0.05, 0.3, 0.6])
+        want, want_exc = _expected(entry, (left, right, wl, bl, kw))
+        got, got_exc = _run(lambda: oc.compare(left.copy(), right.copy(), wl, bl, **kw))
+        assert (want_exc is None) == (got_exc is None) and want_exc in (None, type(got_exc).__name__), (
+            f"seed {seed}: reference {want_exc} / oracle {got_exc!r}")
         if want_exc is not None:
             continue
         scores = list(want["MatchScore"])
