@@ -13,6 +13,8 @@
  *                            with `intersection_vs_union` (types/comparable_data.py:223-232, :248-265),
  *                            the category predicate (:464-490) and the `>= score_threshold` filter (:243)
  *   nsm_indel_levels_grid    the same loop with `fuzzy_match`
+ *   nsm_*_raw_top_k          the same two score_funcs when only the k best candidates of each item are wanted
+ *                            (compare/score_functions.py:6-27; the 1xM use in terminology/mesh.py:207-220)
  *   nsm_sort_hits            Comparable.sort_by_score (types/comparable.py:69-70), made deterministic:
  *                            (score descending, i ascending, j ascending)
  *
@@ -225,6 +227,31 @@ const char* nsm_last_error(void);
 int nsm_jaccard_raw_grid(const nsm_set_table* left, const nsm_set_table* right, double threshold,
                          uint32_t flags, nsm_hit* hits /*device*/, uint64_t capacity,
                          unsigned long long* hit_count /*device, caller zeroes*/, void* stream);
+
+/* Per-item top-k of the RAW grids (ABI 5, additive): for every left row i the first min(k, #{j : score(i, j) >= threshold})
+ * records of row i in the order (score descending, j ascending), j the caller's id (right->orig) -- the records of the
+ * threshold grid above with a per-row rank cut.  It stands in for the reference's `score_func` over every pair
+ * (compare/score_functions.py:6-27) when only the best few candidates of an item are wanted, as in the 1 x M use of
+ * terminology/mesh.py:207-220 (rapidfuzz's process.extract(query, choices, scorer, limit, score_cutoff) for fuzzy_match).
+ *   out        device, room for left->n * k records; the selected records are written in ANY order (nsm_sort_hits
+ *              orders them); the output is bounded in advance: no capacity, no retry
+ *   out_count  device, caller zeroes; receives the number of records
+ *   stats      device uint64[4] or NULL; per call (added to): [0] pairs in the right classes (len_start / size_start)
+ *              that were visited, [1] pairs that passed the length / size bound, [2] pairs that passed the histogram /
+ *              signature bound, [3] exact evaluations (LCS or merge)
+ *   flags      NSM_FLAG_PRUNE: the classes are visited in the order of decreasing bound and each row keeps a floor (its
+ *              k-th best score so far); a class or a pair whose upper bound is strictly below max(threshold, floor) is
+ *              skipped.  Without it every pair is scored exactly (A/B runs, tests).  The records are the same either way
+ *   k          >= 1 (else NSM_E_BADARG); clamped to right->n; beyond 4096 after clamping NSM_E_UNSUPPORTED
+ * The right table needs len_start / size_start (NSM_E_BADARG); a width or stride mismatch is NSM_E_BADARG.  Jaccard pairs
+ * of two empty sets are never records (the host raises ZeroDivisionError beforehand, as for the grid).  The per-row lists
+ * live in scratch allocated stream-ordered inside the call (left->n * k records of 16 bytes). */
+int nsm_indel_raw_top_k(const nsm_str_table* left, const nsm_str_table* right, double threshold, int32_t k,
+                        uint32_t flags, nsm_hit* out /*device, left->n * k records*/,
+                        unsigned long long* out_count /*device, caller zeroes*/, uint64_t* stats /*device [4] or NULL*/,
+                        void* stream);
+int nsm_jaccard_raw_top_k(const nsm_set_table* left, const nsm_set_table* right, double threshold, int32_t k,
+                          uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream);
 
 /* Levels-mode Jaccard: score = sum_{s=1..max(Ll,Lr)} 2^-s * J(level min(s,Ll-1), level min(s,Lr-1))
  * accumulated in double in that order; optional category predicate. */

@@ -20,6 +20,7 @@
 //     L1 distance of the two strings' 32-bucket symbol histograms (8 v_sad_u8 per pair): a wave only
 //     runs the LCS for rows in which some lane can still reach its lcsmin.
 #include "nsm_common.hpp"
+#include "indel_score.hpp"
 
 namespace nsm {
 
@@ -34,15 +35,6 @@ struct IndelRawParams {
   unsigned long long cap;
   uint8_t lcsmin[132];  // indexed by la+lb (both >= 1)
 };
-
-// The exact double sequence of `QRatio(a, b) / 100` once LCS is known (oracle/score_functions.py).
-__device__ __forceinline__ double indel_score(int la, int lb, int lcs) {
-  if (la == 0 || lb == 0) return 0.0;
-  const double maximum = static_cast<double>(la + lb);
-  const double dist = static_cast<double>(la + lb - 2 * lcs);
-  const double norm_sim = 1.0 - dist / maximum;
-  return (norm_sim * 100.0) / 100.0;
-}
 
 static double indel_score_host(int la, int lb, int lcs) {
   if (la == 0 || lb == 0) return 0.0;

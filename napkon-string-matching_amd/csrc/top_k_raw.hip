@@ -1,0 +1,612 @@
+// Per-item top-k of the RAW grids: for every left row the best min(k, #eligible) right rows in the order (score
+// descending, caller's j ascending), eligible = score >= threshold.  The query of rapidfuzz's
+// process.extract(query, choices, limit, score_cutoff) for fuzzy_match (reference: compare/score_functions.py:20-27) and
+// intersection_vs_union (:6-13); terminology/mesh.py:207-220 asks it 1 x M per item.  The output is bounded by N k
+// records whatever the data, unlike the threshold grids.
+//
+// Mapping to CDNA4
+//   * one wavefront (a workgroup of its own) owns G consecutive rows of the LEFT table (sorted by length / set size, so
+//     the rows have nearly the same size); their lengths, histograms / signatures and the state of their lists are
+//     wave-uniform (SGPRs), the lanes stream right rows.  Every right row a lane fetches serves G pairs;
+//   * the right table is visited class by class (len_start / size_start), starting at the class of the group's first
+//     row and walking outwards in the order of decreasing class bound 2 min(la, lb) / (la + lb) (Jaccard: min / max);
+//   * each row keeps its list -- at most k (score, j) records -- in its own slice of a stream-ordered scratch buffer
+//     that only this wave touches (no atomics, deterministic); once the list is full its worst record is the row's
+//     FLOOR.  A class, or a pair, is skipped only when its upper bound is STRICTLY below max(threshold, floor): a pair
+//     that equals the floor may still win on j.  The sweep ends when no row can gain from the classes left;
+//   * bounds: the exact class bound, then the 32-bucket histogram bound LCS <= (la + lb - L1) / 2 (strides 64 and 128:
+//     a bucket of a longer row can saturate its uint8) / the signature bound of nsm_hip.h (sig, sig2);
+//   * survivors get their exact score: the multi-word bit-parallel LCS with the G rows' match masks resident in LDS
+//     (add_chain of indel_wide.hpp), or a merge of the two ascending id rows; the score is the double the RAW grids emit;
+//   * at the end the wave reserves its records in `out` with one atomic and copies its lists there.
+#include "indel_score.hpp"
+#include "indel_wide.hpp"
+
+namespace nsm {
+
+constexpr int kTopG = 8;         // left rows per wavefront
+constexpr int kTopMaxK = 4096;   // largest k (after clamping to the right table's rows)
+
+__device__ __forceinline__ double topk_jaccard_score(int a, int b, int inter) {  // the RAW Jaccard grid's quotient
+  return static_cast<double>(inter) / static_cast<double>(a + b - inter);
+}
+
+// Least LCS whose score reaches `eff` (la, lb >= 1), or min(la, lb) + 1 when none does.  The start
+// ceil(eff (la + lb) / 2) - 1 is below the answer (the rounding of the score is far smaller than one LCS step), the walk
+// up uses the exact double score: the bound is never rounded away from a pair that could still enter the list.
+__device__ __forceinline__ int indel_need(int la, int lb, double eff) {
+  if (eff <= 0.0) return 0;
+  const int top = min(la, lb);
+  int need = static_cast<int>(ceil(eff * static_cast<double>(la + lb) * 0.5)) - 1;
+  need = max(0, min(need, top + 1));
+  while (need <= top && indel_score(la, lb, need) < eff) ++need;
+  return need;
+}
+
+// The same for the intersection of a set of a ids and one of b ids (a + b >= 1).
+__device__ __forceinline__ int jaccard_need(int a, int b, double eff) {
+  if (eff <= 0.0) return 0;
+  const int top = min(a, b);
+  int need = static_cast<int>(floor(eff * static_cast<double>(a + b) / (1.0 + eff))) - 1;
+  need = max(0, min(need, top + 1));
+  while (need <= top && topk_jaccard_score(a, b, need) < eff) ++need;
+  return need;
+}
+
+// The lists of the wave's G rows.  Row g's records are list[(row0 + g) k .. + cnt(g)); only this wave reads or writes
+// them, so a workgroup-scope fence orders lane 0's store before the wave's reloads (nothing else is needed).  The rows'
+// state is held "one row per lane" -- lane g of cnt_v is row g's count -- and read with v_readlane: a loop over the rows
+// needs no dynamically indexed register array (which would live in scratch).
+struct TopLists {
+  nsm_hit* list;
+  int k;
+  int row0;
+  int lane;
+  int cnt_v = 0;
+  double worst_v = 0.0;  // the floor, valid when the list is full
+  int wj_v = 0;
+  int wp_v = 0;
+  int changes = 0;  // records that entered a list so far: the floors can only have moved when this did
+
+  __device__ int cnt(int g) const { return __builtin_amdgcn_readlane(cnt_v, g); }
+  __device__ bool full(int g) const { return cnt(g) == k; }
+  __device__ double worst(int g) const {
+    const unsigned long long b = __double_as_longlong(worst_v);
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b), g));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), g));
+    return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+  }
+  // max(threshold, floor): what a pair's upper bound must reach to matter to row g
+  __device__ double eff(int g, double threshold) const { return full(g) ? fmax(threshold, worst(g)) : threshold; }
+  // an eligible record (score >= threshold) enters row g's list
+  __device__ bool beats(int g, double s, int j) const {
+    if (!full(g)) return true;
+    const double w = worst(g);
+    return s > w || (s == w && j < __builtin_amdgcn_readlane(wj_v, g));
+  }
+
+  // the worst record of row g's full list (lowest score, then largest j): one wave-wide reduction
+  __device__ void rescan(int g) {
+    const nsm_hit* row = list + static_cast<size_t>(row0 + g) * k;
+    double s = __builtin_inf();
+    int j = -1, pos = -1;
+    for (int q = lane; q < k; q += kWave) {
+      const nsm_hit h = row[q];
+      if (h.score < s || (h.score == s && h.j > j)) { s = h.score; j = h.j; pos = q; }
+    }
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      const double s2 = __shfl_xor(s, off);
+      const int j2 = __shfl_xor(j, off), p2 = __shfl_xor(pos, off);
+      if (s2 < s || (s2 == s && j2 > j)) { s = s2; j = j2; pos = p2; }
+    }
+    if (lane == g) { worst_v = s; wj_v = j; wp_v = pos; }
+  }
+
+  // wave-uniform call, all lanes enabled: put (s, i, j) into row g's list if it belongs there
+  __device__ void offer(int g, double s, int i, int j) {
+    if (!beats(g, s, j)) return;
+    const bool was_full = full(g);
+    const int slot = was_full ? __builtin_amdgcn_readlane(wp_v, g) : cnt(g);
+    if (lane == 0) {
+      nsm_hit h;
+      h.score = s;
+      h.i = i;
+      h.j = j;
+      list[static_cast<size_t>(row0 + g) * k + slot] = h;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    ++changes;
+    if (!was_full && lane == g) ++cnt_v;
+    if (was_full || slot + 1 == k) rescan(g);
+  }
+
+  // lanes with `ok` hold an eligible record (s, j) for row g: offer them one by one (the floor rises on the way)
+  __device__ void offer_lanes(int g, bool ok, double s, int i, int j) {
+    for (unsigned long long todo = __ballot(ok); todo; todo &= todo - 1ull) {
+      const int leader = __builtin_ctzll(todo);
+      const unsigned long long b = __double_as_longlong(s);
+      const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b), leader));
+      const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), leader));
+      const double s_l = __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+      offer(g, s_l, i, __builtin_amdgcn_readlane(j, leader));
+    }
+  }
+
+  // copy the lists to out[*out_count ..] (one atomic per wave) and add the wave's counters to stats
+  __device__ void flush(int rows, nsm_hit* __restrict__ out, unsigned long long* __restrict__ out_count,
+                        unsigned long long* __restrict__ stats, const unsigned long long (&st)[4]) {
+    int total = 0;
+    for (int g = 0; g < rows; ++g) total += cnt(g);
+    unsigned long long base = 0;
+    if (lane == 0 && total) base = atomicAdd(out_count, static_cast<unsigned long long>(total));
+    base = (static_cast<unsigned long long>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(base >> 32), 0))) << 32) |
+           static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(base), 0));
+    for (int g = 0; g < rows; ++g) {
+      const nsm_hit* row = list + static_cast<size_t>(row0 + g) * k;
+      const int n = cnt(g);
+      for (int q = lane; q < n; q += kWave) out[base + q] = row[q];
+      base += n;
+    }
+    if (stats) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        unsigned long long v = st[c];
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off);
+        if (lane == 0 && v) atomicAdd(stats + c, v);
+      }
+    }
+  }
+};
+
+// The class walk: classes are indexed by their size z = 0 .. top (length / set size); starting at z0 -- the group's first
+// row's -- the walk goes to whichever neighbour, up (hi) or down (lo), has the larger bound for z0, and drops a direction
+// once no row of the group can gain from what is left of it.  A row's class bound is non-increasing away from its own
+// size, so the best class left in [from, to] for a row of size z is the one closest to z.
+struct ClassWalk {
+  int hi, lo;
+};
+
+// ------------------------------------------------------------------------------------------------------------------ Indel
+struct TopIndelParams {
+  int32_t n_left, n_right, k, pm_stride;
+  double threshold;
+};
+
+// W 64-bit words per pattern (stride 64 W).  LDS: [G][pm_stride][W] match masks of the group's rows.
+template <int W, bool PRUNE, bool HIST>
+__global__ __launch_bounds__(kWave) void indel_top_k_kernel(
+    const uint8_t* __restrict__ lcodes, const int32_t* __restrict__ llen, const int32_t* __restrict__ lorig,
+    const uint32_t* __restrict__ lhist, const uint8_t* __restrict__ rcodes, const int32_t* __restrict__ rlen_start,
+    const int32_t* __restrict__ rorig, const uint32_t* __restrict__ rhist, nsm_hit* __restrict__ list,
+    nsm_hit* __restrict__ out, unsigned long long* __restrict__ out_count, unsigned long long* __restrict__ stats,
+    const TopIndelParams p) {
+  constexpr int G = kTopG, STRIDE = 64 * W;
+  extern __shared__ __attribute__((aligned(16))) unsigned long long s_pm[];
+  const int lane = threadIdx.x;
+  const int row0 = blockIdx.x * G;
+  const int rows = min(G, p.n_left - row0);
+  const double thr = p.threshold;
+
+  // lane g < rows: row g's length and caller id
+  const int la_v = lane < rows ? llen[row0 + lane] : 0;
+  const int io_v = lane < rows ? lorig[row0 + lane] : 0;
+  auto la = [&](int g) { return __builtin_amdgcn_readlane(la_v, g); };
+  uint32_t lh[G][8];
+  if constexpr (HIST) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int r = row0 + min(g, rows - 1);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) lh[g][q] = lhist[static_cast<size_t>(r) * 8 + q];
+    }
+  }
+  // match masks of the rows: clear, then code unit u of row g ORs bit u % 64 into word u / 64 of pm[g][code]
+  for (int e = lane; e < G * p.pm_stride * W; e += kWave) s_pm[e] = 0ull;
+  __syncthreads();
+  for (int g = 0; g < rows; ++g) {
+    const int n = la(g);
+    for (int u = lane; u < n; u += kWave) {
+      const int c = lcodes[static_cast<size_t>(row0 + g) * STRIDE + u];
+      atomicOr(&s_pm[(static_cast<size_t>(g) * p.pm_stride + c) * W + u / kWave], 1ull << (u % kWave));
+    }
+  }
+  __syncthreads();
+
+  TopLists L{list, p.k, row0, lane};
+  unsigned long long st[4] = {0, 0, 0, 0};
+
+  // upper bound of a pair of row g with a right row of length lb: all of the shorter string in common
+  auto bound = [&](int g, int lb) { const int a = la(g); return indel_score(a, lb, min(a, lb)); };
+  auto alive = [&](int from, int to) {
+    if (from > to) return false;
+    if (!PRUNE) return true;
+    bool any = false;
+#pragma unroll
+    for (int g = 0; g < G; ++g) any = any || (g < rows && bound(g, min(max(la(g), from), to)) >= L.eff(g, thr));
+    return any;
+  };
+
+  const int la0 = la(0);
+  ClassWalk w{la0, la0 - 1};
+  while (true) {
+    const bool up = alive(w.hi, STRIDE), down = alive(0, w.lo);
+    if (!up && !down) break;
+    // bound of class hi for la0: 2 la0 / (la0 + hi); of class lo: 2 lo / (la0 + lo)
+    const int lb = (up && (!down || static_cast<long long>(la0) * (la0 + w.lo) >= static_cast<long long>(w.lo) * (la0 + w.hi)))
+                       ? w.hi++ : w.lo--;
+    const int s = rlen_start[STRIDE - lb], e = rlen_start[STRIDE - lb + 1];
+    // rows that can still gain from this class, and the least LCS that matters to each: recomputed when a record has
+    // entered a list since (only then can a floor have risen)
+    uint32_t active = 0;
+    int need[G];
+    int seen = -1;
+    for (int base = s; base < e; base += kWave) {
+      if (seen != L.changes) {
+        seen = L.changes;
+        active = 0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const double eff = L.eff(g, thr);
+          active |= (g < rows && (!PRUNE || bound(g, lb) >= eff)) ? (1u << g) : 0u;
+          need[g] = (PRUNE && la(g) > 0 && lb > 0) ? indel_need(la(g), lb, eff) : 0;
+        }
+      }
+      if (!active) break;
+      const int j = base + lane;
+      const bool valid = j < e;
+      const int jc = valid ? j : e - 1;
+      if (lane == 0) {
+        const unsigned long long nv = static_cast<unsigned long long>(min(kWave, e - base));
+        st[0] += nv * static_cast<unsigned long long>(rows);
+        st[1] += nv * static_cast<unsigned long long>(__popc(active));
+      }
+      uint32_t cand = valid ? active : 0u;
+      if constexpr (PRUNE && HIST) {
+        const uint4* hp = reinterpret_cast<const uint4*>(rhist + static_cast<size_t>(jc) * 8);
+        const uint4 h0 = hp[0], h1 = hp[1];
+        const uint32_t hr[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          uint32_t l1 = 0;
+#pragma unroll
+          for (int q = 0; q < 8; ++q) l1 = __builtin_amdgcn_sad_u8(lh[g][q], hr[q], l1);
+          if (static_cast<int>(l1) > la(g) + lb - 2 * need[g]) cand &= ~(1u << g);
+        }
+      }
+      st[2] += __popc(cand);
+      const int jo = rorig[jc];
+      for (int g = 0; g < rows; ++g) {
+        const bool mine = (cand >> g) & 1u;
+        if (!__any(mine)) continue;
+        const int a = la(g);
+        int lcs = 0;
+        if (mine && a > 0 && lb > 0) {
+          const unsigned long long* pm = s_pm + static_cast<size_t>(g) * p.pm_stride * W;
+          unsigned long long v[W], m[W], u[W], t[W];
+#pragma unroll
+          for (int q = 0; q < W; ++q) v[q] = ~0ull;
+          const uint4* tp = reinterpret_cast<const uint4*>(rcodes + static_cast<size_t>(jc) * STRIDE);
+          for (int u16 = 0; u16 < lb; u16 += 16) {
+            const uint4 x = tp[u16 / 16];
+            const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+              if (u16 + b < lb) {
+                const uint32_t code = (xs[b / 4] >> (8 * (b % 4))) & 0xffu;
+#pragma unroll
+                for (int q = 0; q < W; ++q) {
+                  m[q] = pm[code * W + q];
+                  u[q] = v[q] & m[q];
+                }
+                add_chain<W>(v, u, t);
+#pragma unroll
+                for (int q = 0; q < W; ++q) v[q] = t[q] | (v[q] & ~m[q]);
+              }
+            }
+          }
+#pragma unroll
+          for (int q = 0; q < W; ++q) lcs += __popcll(~v[q]);
+        }
+        st[3] += mine ? 1u : 0u;
+        const double sc = indel_score(a, lb, lcs);
+        L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
+      }
+    }
+  }
+  L.flush(rows, out, out_count, stats, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Jaccard
+struct TopJacParams {
+  int32_t n_left, n_right, k;
+  double threshold;
+};
+
+template <int W, bool PRUNE>
+__global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
+    const int32_t* __restrict__ lids, const int32_t* __restrict__ lcnt, const uint64_t* __restrict__ lsig,
+    const uint64_t* __restrict__ lsig2, const int32_t* __restrict__ lorig, const int32_t* __restrict__ rids,
+    const int32_t* __restrict__ rsize_start, const uint64_t* __restrict__ rsig, const uint64_t* __restrict__ rsig2,
+    const int32_t* __restrict__ rorig, nsm_hit* __restrict__ list, nsm_hit* __restrict__ out,
+    unsigned long long* __restrict__ out_count, unsigned long long* __restrict__ stats, const TopJacParams p) {
+  constexpr int G = kTopG;
+  constexpr uint64_t kCollBits = ~((1ull << 58) - 1);  // the top 6 bits of a signature word hold c (unary)
+  __shared__ int32_t s_ids[G * W];
+  const int lane = threadIdx.x;
+  const int row0 = blockIdx.x * G;
+  const int rows = min(G, p.n_left - row0);
+  const double thr = p.threshold;
+  const bool two_sigs = PRUNE && lsig2 && rsig2;
+
+  const int na_v = lane < rows ? lcnt[row0 + lane] : 0;
+  const int io_v = lane < rows ? lorig[row0 + lane] : 0;
+  auto na = [&](int g) { return __builtin_amdgcn_readlane(na_v, g); };
+  uint64_t sl[G], sl2[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int r = row0 + min(g, rows - 1);
+    sl[g] = PRUNE ? lsig[r] : 0ull;
+    sl2[g] = two_sigs ? lsig2[r] : 0ull;
+  }
+  for (int e = lane; e < G * W; e += kWave) s_ids[e] = (e / W < rows) ? lids[static_cast<size_t>(row0) * W + e] : -1;
+  __syncthreads();
+
+  TopLists L{list, p.k, row0, lane};
+  unsigned long long st[4] = {0, 0, 0, 0};
+
+  // upper bound with a set of b ids: min / max -- 0 when exactly one side is empty; two empty sets never score
+  auto bound = [&](int g, int b) {
+    const int a = na(g);
+    return a + b == 0 ? -__builtin_inf() : topk_jaccard_score(a, b, min(a, b));
+  };
+  auto alive = [&](int from, int to) {
+    if (from > to) return false;
+    if (!PRUNE) return true;
+    bool any = false;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      int b = min(max(na(g), from), to);
+      if (b == 0 && na(g) == 0 && to >= 1) b = 1;  // (an empty row scores 0 against any non-empty set)
+      any = any || (g < rows && bound(g, b) >= L.eff(g, thr));
+    }
+    return any;
+  };
+
+  const int a0 = na(0);
+  ClassWalk w{a0, a0 - 1};
+  while (true) {
+    const bool up = alive(w.hi, W), down = alive(0, w.lo);
+    if (!up && !down) break;
+    // bound of class hi for a0: a0 / hi; of class lo: lo / a0
+    const int b = (up && (!down || static_cast<long long>(a0) * a0 >= static_cast<long long>(w.lo) * w.hi)) ? w.hi++ : w.lo--;
+    const int s = rsize_start[W - b], e = rsize_start[W - b + 1];
+    uint32_t active = 0;
+    int need[G];
+    int seen = -1;
+    for (int base = s; base < e; base += kWave) {
+      if (seen != L.changes) {  // (as in the Indel kernel: only a record entering a list moves a floor)
+        seen = L.changes;
+        active = 0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const double eff = L.eff(g, thr);
+          active |= (g < rows && na(g) + b > 0 && (!PRUNE || bound(g, b) >= eff)) ? (1u << g) : 0u;
+          need[g] = (PRUNE && na(g) + b > 0) ? jaccard_need(na(g), b, eff) : 0;
+        }
+      }
+      if (!active) break;
+      const int j = base + lane;
+      const bool valid = j < e;
+      const int jc = valid ? j : e - 1;
+      if (lane == 0) {
+        const unsigned long long nv = static_cast<unsigned long long>(min(kWave, e - base));
+        st[0] += nv * static_cast<unsigned long long>(rows);
+        st[1] += nv * static_cast<unsigned long long>(__popc(active));
+      }
+      uint32_t cand = valid ? active : 0u;
+      if constexpr (PRUNE) {
+        // |A n B| <= popcount(sigA & sigB) with the right word's top 6 bits set (nsm_hip.h), under both signatures
+        const uint64_t sr = rsig[jc] | kCollBits;
+        const uint64_t sr2 = two_sigs ? (rsig2[jc] | kCollBits) : 0ull;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          int ub = __popcll(sl[g] & sr);
+          if (two_sigs) ub = min(ub, __popcll(sl2[g] & sr2));
+          if (ub < need[g]) cand &= ~(1u << g);
+        }
+      }
+      st[2] += __popc(cand);
+      const int jo = rorig[jc];
+      const int4* rp = reinterpret_cast<const int4*>(rids + static_cast<size_t>(jc) * W);
+      for (int g = 0; g < rows; ++g) {
+        const bool mine = (cand >> g) & 1u;
+        if (!__any(mine)) continue;
+        const int a = na(g);
+        int inter = 0;
+        if (mine) {
+          // merge: the right row's ids (ascending) against the left row's (ascending, in LDS)
+          const int32_t* li = s_ids + g * W;
+          int q = 0;
+          for (int v = 0; v < b; v += 4) {
+            const int4 y4 = rp[v / 4];
+            const int ys[4] = {y4.x, y4.y, y4.z, y4.w};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              if (v + t < b) {
+                const int y = ys[t];
+                while (q < a && li[q] < y) ++q;
+                if (q < a && li[q] == y) { ++inter; ++q; }
+              }
+            }
+          }
+        }
+        st[3] += mine ? 1u : 0u;
+        const double sc = mine ? topk_jaccard_score(a, b, inter) : 0.0;
+        L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
+      }
+    }
+  }
+  L.flush(rows, out, out_count, stats, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- launch
+// Scratch for the per-row lists, stream-ordered: it is freed behind the kernel on the same stream.
+static int with_lists(int n_left, int k, hipStream_t s, nsm_hit** list) {
+  const size_t bytes = static_cast<size_t>(n_left) * static_cast<size_t>(k) * sizeof(nsm_hit);
+  return hip_status(hipMallocAsync(reinterpret_cast<void**>(list), bytes ? bytes : 1, s), "top_k list scratch");
+}
+
+template <int W, bool PRUNE, bool HIST>
+static int launch_indel_top_k(const nsm_str_table* l, const nsm_str_table* r, const TopIndelParams& p, nsm_hit* list,
+                              nsm_hit* out, unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
+  const size_t lds = static_cast<size_t>(kTopG) * p.pm_stride * W * 8;
+  auto kern = indel_top_k_kernel<W, PRUNE, HIST>;
+  if (lds > 64 * 1024) {
+    const int st = hip_status(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  static_cast<int>(lds)),
+                              "indel_top_k_kernel LDS");
+    if (st) return st;
+  }
+  const dim3 grid((p.n_left + kTopG - 1) / kTopG);
+  hipLaunchKernelGGL(kern, grid, dim3(kWave), lds, s, l->codes, l->len, l->orig, reinterpret_cast<const uint32_t*>(l->hist),
+                     r->codes, r->len_start, r->orig, reinterpret_cast<const uint32_t*>(r->hist), list, out, out_count,
+                     stats, p);
+  return hip_status(hipGetLastError(), "indel_top_k_kernel launch");
+}
+
+template <int W>
+static int dispatch_indel(bool prune, bool hist, const nsm_str_table* l, const nsm_str_table* r, const TopIndelParams& p,
+                          nsm_hit* list, nsm_hit* out, unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
+  if (!prune) return launch_indel_top_k<W, false, false>(l, r, p, list, out, out_count, stats, s);
+  if (hist) return launch_indel_top_k<W, true, true>(l, r, p, list, out, out_count, stats, s);
+  return launch_indel_top_k<W, true, false>(l, r, p, list, out, out_count, stats, s);
+}
+
+template <int W, bool PRUNE>
+static int launch_jaccard_top_k(const nsm_set_table* l, const nsm_set_table* r, const TopJacParams& p, nsm_hit* list,
+                                nsm_hit* out, unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
+  const dim3 grid((p.n_left + kTopG - 1) / kTopG);
+  hipLaunchKernelGGL((jaccard_top_k_kernel<W, PRUNE>), grid, dim3(kWave), 0, s, l->ids, l->cnt, l->sig, l->sig2, l->orig,
+                     r->ids, r->size_start, r->sig, r->sig2, r->orig, list, out, out_count, stats, p);
+  return hip_status(hipGetLastError(), "jaccard_top_k_kernel launch");
+}
+
+// k after clamping to the right side, or an error status (k < 1: NSM_E_BADARG, beyond kTopMaxK: NSM_E_UNSUPPORTED)
+static int clamp_k(const char* who, int32_t k, int32_t n_right, int* k_eff) {
+  if (k < 1) {
+    set_error("%s: k = %d (must be >= 1)", who, k);
+    return NSM_E_BADARG;
+  }
+  *k_eff = k < n_right ? k : n_right;
+  if (*k_eff > kTopMaxK) {
+    set_error("%s: k = %d exceeds the supported %d", who, *k_eff, kTopMaxK);
+    return NSM_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+}  // namespace nsm
+
+extern "C" int nsm_indel_raw_top_k(const nsm_str_table* left, const nsm_str_table* right, double threshold, int32_t k,
+                                   uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream) {
+  using namespace nsm;
+  if (!left || !right || !out_count || !out) {
+    set_error("nsm_indel_raw_top_k: null argument");
+    return NSM_E_BADARG;
+  }
+  int keff = 0;
+  if (k < 1) return clamp_k("nsm_indel_raw_top_k", k, right->n, &keff);
+  if (left->stride != right->stride) {
+    set_error("nsm_indel_raw_top_k: strides differ (%d, %d)", left->stride, right->stride);
+    return NSM_E_BADARG;
+  }
+  if (left->stride != 64 && left->stride != 128 && left->stride != 256 && left->stride != 512) {
+    set_error("nsm_indel_raw_top_k: stride %d unsupported (64, 128, 256 or 512 code units)", left->stride);
+    return NSM_E_UNSUPPORTED;
+  }
+  if (left->alphabet != right->alphabet || left->alphabet < 1 || left->alphabet > 255) {
+    set_error("nsm_indel_raw_top_k: alphabets differ or exceed 255 (%d, %d)", left->alphabet, right->alphabet);
+    return NSM_E_BADARG;
+  }
+  if (left->n < 0 || right->n < 0) {
+    set_error("nsm_indel_raw_top_k: negative row count");
+    return NSM_E_BADARG;
+  }
+  if (!left->codes || !left->len || !left->orig || !right->codes || !right->len_start || !right->orig) {
+    set_error("nsm_indel_raw_top_k: table has a null column (the right table needs len_start)");
+    return NSM_E_BADARG;
+  }
+  if (int st = clamp_k("nsm_indel_raw_top_k", k, right->n, &keff)) return st;
+  if (left->n == 0 || right->n == 0) return 0;
+  TopIndelParams p;
+  p.n_left = left->n;
+  p.n_right = right->n;
+  p.k = keff;
+  p.pm_stride = ((left->alphabet + 1) + 63) / 64 * 64;
+  p.threshold = threshold;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool prune = (flags & NSM_FLAG_PRUNE) != 0;
+  // (a 32-bucket count saturates at 255: the histogram bound holds for rows of at most 255 code units)
+  const bool hist = prune && left->hist && right->hist && left->stride <= 128;
+  nsm_hit* list = nullptr;
+  if (int st = with_lists(left->n, keff, s, &list)) return st;
+  unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  int st = 0;
+  switch (left->stride) {
+    case 64: st = dispatch_indel<1>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
+    case 128: st = dispatch_indel<2>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
+    case 256: st = dispatch_indel<4>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
+    default: st = dispatch_indel<8>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
+  }
+  const int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
+  return st ? st : fst;
+}
+
+extern "C" int nsm_jaccard_raw_top_k(const nsm_set_table* left, const nsm_set_table* right, double threshold, int32_t k,
+                                     uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats,
+                                     void* stream) {
+  using namespace nsm;
+  if (!left || !right || !out_count || !out) {
+    set_error("nsm_jaccard_raw_top_k: null argument");
+    return NSM_E_BADARG;
+  }
+  int keff = 0;
+  if (k < 1) return clamp_k("nsm_jaccard_raw_top_k", k, right->n, &keff);
+  if (left->width != right->width || (left->width != 16 && left->width != 32 && left->width != 64)) {
+    set_error("nsm_jaccard_raw_top_k: width %d/%d unsupported (both sides 16, 32 or 64)", left->width, right->width);
+    return NSM_E_BADARG;
+  }
+  if (left->n < 0 || right->n < 0) {
+    set_error("nsm_jaccard_raw_top_k: negative row count");
+    return NSM_E_BADARG;
+  }
+  if (!left->ids || !left->cnt || !left->orig || !right->ids || !right->size_start || !right->orig) {
+    set_error("nsm_jaccard_raw_top_k: table has a null column (the right table needs size_start)");
+    return NSM_E_BADARG;
+  }
+  if (int st = clamp_k("nsm_jaccard_raw_top_k", k, right->n, &keff)) return st;
+  if (left->n == 0 || right->n == 0) return 0;
+  TopJacParams p;
+  p.n_left = left->n;
+  p.n_right = right->n;
+  p.k = keff;
+  p.threshold = threshold;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool prune = (flags & NSM_FLAG_PRUNE) && left->sig && right->sig;
+  nsm_hit* list = nullptr;
+  if (int st = with_lists(left->n, keff, s, &list)) return st;
+  unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  int st = 0;
+  switch (left->width) {
+    case 16: st = prune ? launch_jaccard_top_k<16, true>(left, right, p, list, out, out_count, sp, s)
+                        : launch_jaccard_top_k<16, false>(left, right, p, list, out, out_count, sp, s); break;
+    case 32: st = prune ? launch_jaccard_top_k<32, true>(left, right, p, list, out, out_count, sp, s)
+                        : launch_jaccard_top_k<32, false>(left, right, p, list, out, out_count, sp, s); break;
+    default: st = prune ? launch_jaccard_top_k<64, true>(left, right, p, list, out, out_count, sp, s)
+                        : launch_jaccard_top_k<64, false>(left, right, p, list, out, out_count, sp, s); break;
+  }
+  const int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
+  return st ? st : fst;
+}

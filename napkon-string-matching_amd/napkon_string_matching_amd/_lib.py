@@ -110,6 +110,8 @@ EXPORTS = (
     "nsm_build_level_items",
     "nsm_indel_any_grid",
     "nsm_jaccard_any_grid",
+    "nsm_indel_raw_top_k",
+    "nsm_jaccard_raw_top_k",
 )
 
 _lib = None
@@ -153,6 +155,11 @@ def load() -> ctypes.CDLL:
         P(NsmAnyItems), P(NsmAnyStrings), P(NsmAnyItems), P(NsmAnyStrings), ctypes.c_double, ctypes.c_int32,
         ctypes.c_uint32] + grid_tail
     lib.nsm_jaccard_any_grid.argtypes = [P(NsmAnySets), P(NsmAnySets), ctypes.c_double, ctypes.c_int32, ctypes.c_uint32] + grid_tail
+    # threshold, k, flags, out, out_count, stats, stream
+    top_k_tail = [ctypes.c_double, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p]
+    lib.nsm_indel_raw_top_k.argtypes = [P(NsmStrTable), P(NsmStrTable)] + top_k_tail
+    lib.nsm_jaccard_raw_top_k.argtypes = [P(NsmSetTable), P(NsmSetTable)] + top_k_tail
     # hits, scratch, capacity, hit_count, n_hint, id_limit, stream
     lib.nsm_sort_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_u64, ctypes.c_void_p, c_u64, ctypes.c_uint32,
                                   ctypes.c_void_p]

@@ -8,7 +8,10 @@ Same names, call convention and error behaviour as the reference's
 * calling it scores ONE pair -- as a 1 x 1 grid on the GPU, through the same kernels as the
   batched path (there is no CPU implementation of the arithmetic in this package);
 * ``plugin.raw_grid(left_items, right_items, threshold)`` / the levels builders used by
-  ``ComparableData.gen_comparable`` score N x M pairs in one launch.
+  ``ComparableData.gen_comparable`` score N x M pairs in one launch;
+* ``plugin.top_k(left_items, right_items, k, threshold)`` keeps the ``k`` best right items of every left item
+  (score descending, right index ascending among equals) -- rapidfuzz's ``process.extract(query, choices, scorer,
+  limit, score_cutoff)`` for all queries at once; the output is bounded by N k records whatever the data.
 
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
@@ -105,6 +108,37 @@ class _IntersectionVsUnion:
                                                        raw=True, device=dev)
         return wide.split_grid(split[0], split[1], fast, general)
 
+    @staticmethod
+    def top_k(left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
+              prune: bool = True) -> grid.Hits:
+        """Per left item the first ``k`` records of ``raw_grid(left_items, right_items, threshold)`` (score descending,
+        right index ascending), all of them in canonical order."""
+        from .. import wide
+
+        k = grid.check_k(k)
+        dev = device or _device()
+        l_rows = [list(set_operand(v)) for v in left_items]
+        r_rows = [list(set_operand(v)) for v in right_items]
+        if any(not r for r in l_rows) and any(not r for r in r_rows):
+            raise ZeroDivisionError("division by zero")  # (:13)
+
+        def fast(li, ri):
+            vocab = tables.Vocabulary()
+            ls, rs = [l_rows[k_] for k_ in li], [r_rows[k_] for k_ in ri]
+            width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
+            lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
+            rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
+            return grid.jaccard_raw_top_k(lt, rt, k, threshold, prune=prune)
+
+        split = wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows])
+        if split is None:
+            return fast(range(len(l_rows)), range(len(r_rows)))
+        # items of more than 64 distinct tokens: the general kernel at `threshold`; the parts are disjoint in j for every
+        # i, so the union of their per-row selections holds the answer
+        general = lambda li, ri: grid.select_top_k(
+            wide.jaccard_any_grid([[l_rows[k_]] for k_ in li], [[r_rows[k_]] for k_ in ri], threshold, raw=True, device=dev), k)
+        return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)
+
 
 class _FuzzyMatch:
     __name__ = "fuzzy_match"
@@ -133,6 +167,30 @@ class _FuzzyMatch:
         general = lambda li, ri: wide.indel_any_grid([[l_ops[k]] for k in li], [[r_ops[k]] for k in ri], threshold, raw=True,
                                                      device=dev)
         return wide.split_grid(split[0], split[1], fast, general)
+
+    @staticmethod
+    def top_k(left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
+              prune: bool = True) -> grid.Hits:
+        """Per left item the first ``k`` records of ``raw_grid(left_items, right_items, threshold)`` (score descending,
+        right index ascending), all of them in canonical order."""
+        from .. import wide
+
+        k = grid.check_k(k)
+        dev = device or _device()
+        l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+
+        def fast(li, ri):
+            lt, rt = tables.encode_strings([l_ops[k_] for k_ in li], [r_ops[k_] for k_ in ri], dev)
+            return grid.indel_raw_top_k(lt, rt, k, threshold, prune=prune)
+
+        split = wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops])
+        if split is None:
+            return fast(range(len(l_ops)), range(len(r_ops)))
+        # strings beyond the fast kernels: the general kernel at `threshold`; the parts are disjoint in j for every i, so
+        # the union of their per-row selections holds the answer
+        general = lambda li, ri: grid.select_top_k(
+            wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], threshold, raw=True, device=dev), k)
+        return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)
 
 
 intersection_vs_union = _IntersectionVsUnion()

@@ -178,6 +178,83 @@ def indel_raw_grid(
     return run_grid(launch, left.codes.device, capacity, "nsm_indel_raw_grid")
 
 
+# ------------------------------------------------------------------------------- RAW top-k
+TOP_K_MAX = 4096  # largest k the kernels keep per row (after clamping to the right side's rows)
+
+
+def check_k(k) -> int:
+    """``k`` of a top-k query: an ``int`` (not a bool) of at least 1, else ``ValueError`` -- before any device work."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+        raise ValueError(f"k must be an int >= 1, got {k!r}")
+    return int(k)
+
+
+def select_top_k(hits: Hits, k: int) -> Hits:
+    """The first ``k`` records of every left item (score descending, j ascending), returned in canonical order: the
+    definition of a top-k query in terms of a threshold grid's hits (also how per-part results are merged)."""
+    if len(hits) == 0:
+        return hits
+    by_row = np.lexsort((hits.j, -hits.score, hits.i))
+    i_sorted = hits.i[by_row]
+    start = np.r_[0, np.flatnonzero(i_sorted[1:] != i_sorted[:-1]) + 1]
+    rank = np.arange(len(by_row)) - np.repeat(start, np.diff(np.r_[start, len(by_row)]))
+    keep = by_row[rank < k]
+    order = keep[np.lexsort((hits.j[keep], hits.i[keep], -hits.score[keep]))]
+    return Hits(hits.score[order], hits.i[order], hits.j[order])
+
+
+def _top_k(launch: Callable, n_left: int, n_right: int, k: int, device, what: str, stats: Optional[list] = None,
+           id_limit: int = 0) -> Hits:
+    """Run a top-k launch ``launch(out, out_count, stats, k, stream)`` into a buffer of ``n_left * min(k, n_right)`` records
+    (the output size is known in advance: no retry), then order the records canonically on the device."""
+    dev = _require_gpu(device)
+    k_eff = min(k, max(n_right, 1))
+    if k_eff > TOP_K_MAX:  # (what the C entry would answer with NSM_E_UNSUPPORTED, before n_left * k records are allocated)
+        raise NotImplementedError(f"{what}: k = {k_eff} (after clamping to the right side's {n_right} rows) exceeds the "
+                                  f"supported {TOP_K_MAX}")
+    buf = HitBuffer(max(1, n_left * k_eff), dev)
+    st = torch.zeros(4, dtype=torch.int64, device=dev)
+    buf.reset()
+    if n_left and n_right:
+        _lib.check(launch(buf.records, buf.count, st, k_eff, torch.cuda.current_stream(dev).cuda_stream), what)
+    n = int(buf.count.item())  # synchronises the stream
+    if stats is not None:
+        stats[:] = [int(v) for v in st.tolist()]
+    return sort_hits_device(buf, n, id_limit)
+
+
+def indel_raw_top_k(left: StrTable, right: StrTable, k: int, threshold: float, prune: bool = True,
+                    stats: Optional[list] = None) -> Hits:
+    """For every left item the first ``min(k, #hits of its row)`` records of ``indel_raw_grid(left, right, threshold)``
+    in the order (score descending, j ascending), all of them in canonical order.  ``stats``: a list that receives
+    [pairs in visited classes, pairs past the length bound, pairs past the histogram bound, exact LCS evaluations]."""
+    k = check_k(k)
+    lib = _lib.load()
+    ls, rs = left.struct(), right.struct()
+    flags = _lib.FLAG_PRUNE if prune else 0
+    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_indel_raw_top_k(
+        ls, rs, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
+        left.n, right.n, k, left.codes.device, "nsm_indel_raw_top_k", stats)
+
+
+def jaccard_raw_top_k(left: SetTable, right: SetTable, k: int, threshold: float, prune: bool = True,
+                      stats: Optional[list] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_raw_top_k``; stats[2] counts the pairs past the signature bound,
+    stats[3] the exact merges."""
+    k = check_k(k)
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    if left.has_empty and right.has_empty:
+        raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
+    lib = _lib.load()
+    ls, rs = left.struct(), right.struct()
+    flags = _lib.FLAG_PRUNE if prune else 0
+    id_limit = max(left.id_limit, right.id_limit) if left.id_limit and right.id_limit else 0
+    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_jaccard_raw_top_k(
+        ls, rs, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
+        left.n, right.n, k, left.ids.device, "nsm_jaccard_raw_top_k", stats, id_limit)
+
+
 # ------------------------------------------------------------------------------- levels grids
 def jaccard_levels_grid(
     left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True,

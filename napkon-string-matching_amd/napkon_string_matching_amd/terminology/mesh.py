@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import pandas as pd
 
 from ..compare import score_functions
+from ..grid import TOP_K_MAX, check_k
 
 TERMINOLOGY_COLUMN_TERM = "Term"
 TERMINOLOGY_COLUMN_ID = "Id"
@@ -43,18 +44,33 @@ class MeshProvider:
     def headings(self) -> pd.DataFrame:
         return self._headings
 
-    def get_matches(self, term: Sequence[str], score_threshold: float = 0.1) -> List[Match]:
+    def get_matches(self, term: Sequence[str], score_threshold: float = 0.1, limit: Optional[int] = None) -> List[Match]:
         """(Id, Term, Score) of every synonym scoring ``>= score_threshold`` against ``" ".join(term)``,
         best first, one row per Id (mesh.py:207-220).  Equal scores keep the synonym table's order
-        (the reference's quicksort leaves them unspecified)."""
-        return self.get_matches_batch([term], score_threshold)[0]
+        (the reference's quicksort leaves them unspecified).  ``limit``: only the first ``limit`` of them."""
+        return self.get_matches_batch([term], score_threshold, limit)[0]
 
-    def get_matches_batch(self, terms: Sequence[Sequence[str]], score_threshold: float = 0.1) -> List[List[Match]]:
+    def get_matches_batch(self, terms: Sequence[Sequence[str]], score_threshold: float = 0.1,
+                          limit: Optional[int] = None) -> List[List[Match]]:
+        """``get_matches`` of every term in one grid.  With ``limit`` each list is the unlimited one cut after ``limit``
+        entries, from a top-k query instead of the threshold grid: the output is bounded by ``limit`` times the most
+        synonym rows of one Id per term, whatever the threshold (the first ``limit`` distinct Ids of a term always lie
+        among its first ``limit * s`` rows when no Id has more than ``s`` rows).  Where ``limit * s`` exceeds the 4096 records
+        the top-k kernels keep per row (``grid.TOP_K_MAX``), the threshold grid is cut instead: same lists, unbounded output."""
         syn = self.synonyms
         ids = list(syn[TERMINOLOGY_COLUMN_ID])
         syn_terms = list(syn[TERMINOLOGY_COLUMN_TERM])
         joined = [" ".join(term) for term in terms]  # mesh.py:207
-        hits = score_functions.fuzzy_match.raw_grid(joined, syn_terms, score_threshold)
+        if limit is None:
+            hits = score_functions.fuzzy_match.raw_grid(joined, syn_terms, score_threshold)
+        else:
+            limit = check_k(limit)
+            rows_per_id = int(syn[TERMINOLOGY_COLUMN_ID].value_counts().max()) if len(syn) else 1
+            if min(limit * rows_per_id, len(syn_terms)) > TOP_K_MAX:
+                # (beyond what the top-k kernels keep per row: the threshold grid, cut below -- the same lists)
+                hits = score_functions.fuzzy_match.raw_grid(joined, syn_terms, score_threshold)
+            else:
+                hits = score_functions.fuzzy_match.top_k(joined, syn_terms, limit * rows_per_id, score_threshold)
         out: List[List[Match]] = [[] for _ in terms]
         # hits arrive ordered by (score desc, item, synonym row): per item that is already
         # "score descending, table order among equals"
@@ -64,6 +80,8 @@ class MeshProvider:
                 continue  # drop_duplicates(subset=Id) keeps the best row of an Id
             seen[i].add(ids[j])
             out[i].append((ids[j], syn_terms[j], score))
+        if limit is not None:
+            out = [rows[:limit] for rows in out]
         return out
 
 
@@ -82,12 +100,14 @@ class TerminologyProvider:
         for p in self.providers:
             p.initialize()
 
-    def get_matches(self, term: Sequence[str], score_threshold: float = 0.1) -> Optional[List[Match]]:
-        return self.get_matches_batch([term], score_threshold)[0]
+    def get_matches(self, term: Sequence[str], score_threshold: float = 0.1, limit: Optional[int] = None) -> Optional[List[Match]]:
+        return self.get_matches_batch([term], score_threshold, limit)[0]
 
-    def get_matches_batch(self, terms, score_threshold: float = 0.1) -> List[Optional[List[Match]]]:
+    def get_matches_batch(self, terms, score_threshold: float = 0.1, limit: Optional[int] = None) -> List[Optional[List[Match]]]:
+        """The providers' lists concatenated, as in the reference.  ``limit`` applies to each provider's list on its own:
+        a term gets up to ``limit`` matches from every provider."""
         merged: List[List[Match]] = [[] for _ in terms]
         for p in self.providers:
-            for k, rows in enumerate(p.get_matches_batch(terms, score_threshold)):
+            for k, rows in enumerate(p.get_matches_batch(terms, score_threshold, limit)):
                 merged[k] += rows
         return [rows if rows else None for rows in merged]

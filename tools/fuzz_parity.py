@@ -24,7 +24,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=300.0)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--family", default=None, help="only this kernel family (jaccard_raw, indel_raw, jaccard_levels, indel_levels, indel_split, wide)")
+    ap.add_argument("--family", default=None, help="only this kernel family (jaccard_raw, indel_raw, jaccard_levels, indel_levels, indel_split, wide; "
+                    "indel_top_k and jaccard_top_k are drawn only when named here)")
     args = ap.parse_args()
 
     import numpy as np
@@ -92,6 +93,53 @@ def main():
         counts[family] = counts.get(family, 0) + 1
         thr = rng.choice(thresholds)
         n, m = rng.randint(1, 400), rng.randint(1, 600)
+        if family in ("indel_top_k", "jaccard_top_k"):
+            # per-item top-k (nsm_*_raw_top_k) against the definition: the oracle's threshold grid, cut per left item after
+            # rank k in the order (score descending, j ascending).  Only through --family: the default draw is unchanged.
+            thr = rng.choice(thresholds + [-1.0, 0.0, -0.5])
+            n, m = rng.randint(1, 160), rng.randint(1, 300)
+            k = rng.choice([1, 1, 2, 3, 5, 10, rng.randint(1, m + 8), m, m + 3])
+            prune = rng.random() < 0.75
+            if family == "indel_top_k":
+                hi = rng.choice([4, 8, 30, 64, 64, 100, 128, 200, 256, 400, 512])
+                alphabet = rng.choice(["ab", "abc", "abcdefgh ", "abcdefghijklmnopqrstuvwxyz0123456789 ", "".join(chr(0x100 + c) for c in range(150))])
+                left = [rand_string(rng, alphabet, 0 if rng.random() < 0.2 else 1, hi) for _ in range(n)]
+                right = [rand_string(rng, alphabet, 0 if rng.random() < 0.2 else 1, hi) for _ in range(m)]
+                dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda s_: "".join(s_))  # exact copies: ties
+                lt, rt = tables.encode_strings(left, right, dev)
+                cp = lambda ss: native.csr([[ord(c) for c in s_] for s_ in ss])
+                full = native.indel_raw(cp(left), cp(right), thr, cap=n * m + 1)
+                what = f"indel_top_k hi={hi} |alphabet|={len(alphabet)} thr={thr} k={k} prune={prune} {n}x{m}"
+                got = grid.indel_raw_top_k(lt, rt, k, thr, prune=prune)
+            else:
+                width = rng.choice([16, 16, 32, 64])
+                kmax = rng.randint(1, width)
+                vocab = rng.choice([kmax + 1, 3 * kmax, 50 * kmax])
+                left_empty, right_empty = rng.random() < 0.2, rng.random() < 0.2
+                left = rand_sets(rng, n, kmax, vocab, allow_empty=left_empty)
+                right = rand_sets(rng, m, kmax, vocab, allow_empty=right_empty and not left_empty)
+                dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda r: list(r))
+                pad = lambda rr: np.array([r + [-1] * (width - len(r)) for r in rr], dtype=np.int32).reshape(len(rr), width)
+                lt = tables.SetTable.from_padded(pad(left), "left", dev, width=width)
+                rt = tables.SetTable.from_padded(pad(right), "right", dev, width=width)
+                what = f"jaccard_top_k W={width} kmax={kmax} vocab={vocab} thr={thr} k={k} prune={prune} {n}x{m}"
+                if any(not r for r in left) and any(not r for r in right):  # (a copied empty row): the reference raises
+                    try:
+                        grid.jaccard_raw_top_k(lt, rt, k, thr, prune=prune)
+                    except ZeroDivisionError:
+                        continue
+                    print(json.dumps({"FAIL": what + " (no ZeroDivisionError for empty x empty)", "round_seed": rnd}))
+                    sys.exit(1)
+                full = native.jaccard_raw(native.csr(left), native.csr(right), thr, cap=n * m + 1)
+                what = f"jaccard_top_k W={width} kmax={kmax} vocab={vocab} thr={thr} k={k} prune={prune} {n}x{m}"
+                got = grid.jaccard_raw_top_k(lt, rt, k, thr, prune=prune)
+            rows = {}
+            for h in full:
+                rows.setdefault(h[1], []).append(h)
+            want = sorted((h for lst in rows.values() for h in sorted(lst, key=lambda t: (-t[0], t[2]))[:k]),
+                          key=lambda t: (-t[0], t[1], t[2]))
+            check(got, want, what)
+            continue
         if family == "wide":
             # operands beyond the fast kernels through the plugin faces (only the wide items leave the fast path)
             from napkon_string_matching_amd.compare import score_functions as sf
