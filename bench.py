@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: pair-comparisons/sec of the all-pairs match loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c2low|c3|c4|c5|c5w|term] [--no-cpu-baseline]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c2low|c3|c4|c5|c5w|term] [--full]
+                    [--no-cpu-baseline] [--dump-outputs DIR]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -20,9 +20,12 @@ configs[4] (three 500k-item cohorts, 4 levels, 32 categories, filter_categories,
 through the levels-mode kernels, left rows of every cohort pair divided over the ranks: "strong") at config.yml's
 score threshold 0.7; `--workload c5w` is the same shape on WORD-LIKE text (20 000 distinct words of 3..7 letters
 instead of "t<digits>") at the threshold the reference's flow hands to the grid when a cache threshold is set, 0.5
-(types/comparable_data.py:102-108, config.yml:11-12), with the 0.7 run reported beside it.
+(types/comparable_data.py:102-108, config.yml:11-12), with the 0.7 run reported beside it (--full).
 
-The JSON line carries, besides the driver's contract fields:
+A plain run sets up the workload, warms up, times the K steps and prints the JSON line: the driver's contract fields
+and the workload's config.  With --dump-outputs it writes the same arrays as a --full run: after the timed steps, the
+grids only --full would time (the sub-records below, c5w's 0.7 run) are set up and run once more for their outputs
+alone.  --full measures everything else, in the same invocation after the timed steps, and adds to the JSON line:
   roofline      dominant kernel against the bound it can actually approach, the VALU issue rate (this path
                 keeps its operands on chip: measured HBM traffic is < 2 % of peak, and the "algorithmic bytes"
                 of SURVEY.md 8d -- 128 B per pair -- exceed what any kernel moves by two orders of magnitude,
@@ -36,6 +39,8 @@ The JSON line carries, besides the driver's contract fields:
                 (SQ_ACTIVE_INST_VALU x 4 / SIMD-cycles: counts a quad-cycle per instruction, can exceed 1),
                 traffic (HBM bytes per launch, FETCH_SIZE x 2 + WRITE_SIZE) with hbm_frac, the algorithmic and
                 compulsory byte counts, and the profile's stamp (git head, hash of csrc/ -- a stale profile shows).
+                c5 / c5w: config.fuzzy_grids_ms_per_step / jaccard_grids_ms_per_step beside it; c5w: at_score_threshold
+                (the same grids at 0.7).
   exhaustive    the same grid with the exact prune disabled (every pair's full comparison evaluated)
   cpu_baseline  the oracle's restatement of the reference's loop, 1 core, bounded sample
   c2 c2low c4 c5 c5w term   (default `--workload all`) every other BASELINE config, configs[4] on word-like text
@@ -71,7 +76,7 @@ HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2  # G wave64-instructions/s: 1024 SIMD-32 x 2.4 GHz, >= 2 cycles per instruction
 BYTES_PER_PAIR = 128  # two 64-byte operand rows
 # --steps K sets the timed steps of the measured workload and nothing else, so that a run grows by K x ms_per_step: the
-# sub-records of the default run and the auxiliary timings (kernel-only launches, the exhaustive run) do fixed work
+# sub-records of the default --full run and the auxiliary timings (kernel-only launches, the exhaustive run) do fixed work
 SUB_STEPS = {"c2": 20, "c2low": 20, "c4": 20, "c5": 5, "c5w": 3, "term": 20}
 KERNEL_REPS = 20
 EXHAUSTIVE_STEPS = 5
@@ -83,17 +88,22 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=("all", "c2", "c2low", "c3", "c4", "c5", "c5w", "term"), default="all",
-                    help="all = the c3 headline line with every other workload attached as a sub-record")
+                    help="all = the c3 headline line (with --full: every other workload attached as a sub-record)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: per-kernel timings and "
+                         "rooflines, the exhaustive (prune off) run, CPU baselines, c5w's run at the score threshold and "
+                         "(--workload all) every other workload as a sub-record")
     ap.add_argument("--rows", type=int, default=0, help="override rows per side per GPU (debug)")
     ap.add_argument("--right-rows", type=int, default=0, help="override the right side's rows (debug)")
     ap.add_argument("--threshold", type=float, default=None, help="override the workload's threshold (debug)")
     ap.add_argument("--id-range", type=int, default=0, help="c2 / c4: draw token ids from [0, N) instead of 2^17 (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--post-format", type=int, choices=(0, 1, 2), default=None,
                     help="posting entries of the RAW tables' global index: 0 = 64 bits, 1 = 32 bits, 2 = 32 bits + signature "
                          "fold (the default where the rows fit); A/B runs of the global-index kernel")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the exhaustive (prune off) run and c5w's second run at the score threshold (profiling passes)")
+                    help="skip the exhaustive (prune off) run of --full and c5w's second run at the score threshold "
+                         "(profiling passes)")
     ap.add_argument("--graph", type=int, default=0, help="1: replay each step as one captured hipGraph")
     ap.add_argument("--serial-sort", action="store_true",
                     help="N = 1: order the hits on the launch stream instead of a second stream (no overlap with the next step's grid)")
@@ -620,6 +630,7 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
     filtered, intersection_vs_union then fuzzy_match for every cohort pair.  One step = the six grids.
     The left rows of every cohort pair are divided over the ranks (total work fixed: "strong").
     ``words`` = the "c5w" workload: the same shape over 20 000 distinct word-like tokens, at the CACHE threshold 0.5.
+    With --full also the per-kernel timings, the roofline, c5w's run at the score threshold and the CPU baseline.
     ``dump``: an OutputDump that receives the six grids' hits of the step that follows the timed ones."""
     import numpy as np
     import torch
@@ -801,14 +812,16 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
             torch.cuda.synchronize(device)
             return ev0.elapsed_time(ev1) / reps
 
-        reps = max(2, min(n_steps, 5))
-        out = {"dt": dt, "counts": counts, "ms_indel": kernel_ms("indel", reps), "ms_jac": kernel_ms("jaccard", reps),
-               "capacity": capacity, "overflow_word": int(state["ws"][1].item()) & 0xFFFFFFFF if state["ws"] is not None else None}
+        out = {"dt": dt, "counts": counts, "capacity": capacity}
+        if args.full:
+            reps = max(2, min(n_steps, 5))
+            out["ms_indel"], out["ms_jac"] = kernel_ms("indel", reps), kernel_ms("jaccard", reps)
+        out["overflow_word"] = int(state["ws"][1].item()) & 0xFFFFFFFF if state["ws"] is not None else None
         del bufs, gathered
         return out
 
     m = measure(steps, warmup, name if dump is not None else None)
-    dt, counts, ms_indel, ms_jac = m["dt"], m["counts"], m["ms_indel"], m["ms_jac"]
+    dt, counts = m["dt"], m["counts"]
     split_used = state["ws"] is not None
     pairs_per_step = 2 * len(pairs) * rows * rows  # both score functions over every cohort pair
     local_pairs = len(pairs) * (hi - lo) * rows    # pairs one fuzzy pass of this rank scores
@@ -858,8 +871,7 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
             "rccl_ranks_seen": comm.rccl_ranks,
             "encode_and_h2d_seconds_once": round(t_encode, 2),
             "level_string_generation_seconds_once": round(t_generate, 2),
-            "fuzzy_grids_ms_per_step": ms_indel,
-            "jaccard_grids_ms_per_step": ms_jac,
+            **({"fuzzy_grids_ms_per_step": m["ms_indel"], "jaccard_grids_ms_per_step": m["ms_jac"]} if args.full else {}),
             "fuzzy_path": ("split (scan -> survivor queue in a caller-owned workspace -> finish)" if split_used else
                            "shared-tile kernel" if tiled else "single kernel (scan + park + dense finish)"),
             "fuzzy_route_measured": [r["measured"] for r in state["route"]],
@@ -867,23 +879,26 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
             "split_workspace_bytes": int(state["ws"].numel() * 8) if split_used else 0,
             "split_queue_overflowed": bool(m["overflow_word"]) if split_used else None,
         },
-        "roofline": valu_roofline(name, kernel_match, kernel_label,
-                                  ms_indel, len(pairs), local_pairs // len(pairs) * bytes_per_pair, str_bytes // len(pairs),
-                                  default_shape=not args.rows and (args.threshold is None or sub) and world == 1),
     }
-    if words and threshold == default_threshold and not args.no_extras:
-        # ... and the same grids at config.yml's score threshold (what the result keeps after the cache filter)
+    if args.full:
+        result["roofline"] = valu_roofline(name, kernel_match, kernel_label, m["ms_indel"], len(pairs),
+                                           local_pairs // len(pairs) * bytes_per_pair, str_bytes // len(pairs),
+                                           default_shape=not args.rows and (args.threshold is None or sub) and world == 1)
+    if words and threshold == default_threshold and not args.no_extras and (args.full or dump is not None):
+        # ... and the same grids at config.yml's score threshold (what the result keeps after the cache filter); without
+        # --full only for their outputs
         state["threshold"] = 0.7
         m7 = measure(max(1, min(steps, 2)), 1, f"{name}_at_score_threshold" if dump is not None else None)
-        result["at_score_threshold"] = {
-            "threshold": 0.7, "steps": max(1, min(steps, 2)), "ms_per_step": m7["dt"] / max(1, min(steps, 2)) * 1e3,
-            "fuzzy_grids_ms_per_step": m7["ms_indel"], "jaccard_grids_ms_per_step": m7["ms_jac"],
-            "hits_per_grid_this_rank": m7["counts"],
-            "fuzzy_path": "split" if state["ws"] is not None else "single kernel (scan + park + dense finish)",
-            "split_queue_overflowed": bool(m7["overflow_word"]) if state["ws"] is not None else None,
-        }
+        if args.full:
+            result["at_score_threshold"] = {
+                "threshold": 0.7, "steps": max(1, min(steps, 2)), "ms_per_step": m7["dt"] / max(1, min(steps, 2)) * 1e3,
+                "fuzzy_grids_ms_per_step": m7["ms_indel"], "jaccard_grids_ms_per_step": m7["ms_jac"],
+                "hits_per_grid_this_rank": m7["counts"],
+                "fuzzy_path": "split" if state["ws"] is not None else "single kernel (scan + park + dense finish)",
+                "split_queue_overflowed": bool(m7["overflow_word"]) if state["ws"] is not None else None,
+            }
         state["threshold"] = float(threshold)
-    if rank == 0 and world == 1 and cpu and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu and args.full and not args.no_cpu_baseline:
         from oracle import compare as oc
         from oracle import score_functions as osf
 
@@ -911,8 +926,8 @@ def run_c5(args, comm, device, steps=None, warmup=None, cpu=True, sub=False, wor
 def run_raw(args, comm, device, name, rows=0, right_rows=0, threshold=None, steps=None, warmup=None, extras=True,
             cpu_scale=1.0, dump=None):
     """One RAW-mode / term workload under the contract: W warm-up steps, K timed steps between
-    barrier + synchronize fences, MAX over the ranks.  Returns the JSON object.  ``dump``: an OutputDump that
-    receives the hits of the last timed step."""
+    barrier + synchronize fences, MAX over the ranks; with --full then the roofline, the exhaustive run (``extras``) and
+    the CPU baseline.  Returns the JSON object.  ``dump``: an OutputDump that receives the hits of the last timed step."""
     import torch
 
     from napkon_string_matching_amd import _lib, grid
@@ -1023,23 +1038,6 @@ def run_raw(args, comm, device, name, rows=0, right_rows=0, threshold=None, step
         raise SystemExit(f"hit buffer overflow ({n_hits} > {buf.capacity}); raise --capacity")
     pairs_per_step = comm.sum_int(work.n) * work.m  # (the last shard of a strong-scaled grid may be shorter)
     value = pairs_per_step * steps / dt
-
-    # ---- per-kernel duration of the dominant kernel, HIP events on the launch stream
-    def kernel_ms(prune, reps):
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        buf.count.zero_()
-        work.launch(buf, stream, prune)
-        torch.cuda.synchronize(device)
-        ev0.record()
-        for _ in range(reps):
-            work.launch(buf, stream, prune)
-        ev1.record()
-        torch.cuda.synchronize(device)
-        return ev0.elapsed_time(ev1) / reps
-
-    k_ms = kernel_ms(True, KERNEL_REPS)
-    alg_bytes = work.n * work.m * work.bytes_per_pair
-    compulsory = work.left.nbytes() + work.right.nbytes() + n_hits * 16
     result = {
         "metric": "pair-comparisons/sec (whole node), N x M all-pairs",
         "value": value,
@@ -1069,12 +1067,32 @@ def run_raw(args, comm, device, name, rows=0, right_rows=0, threshold=None, step
                              else "launch stream"),
             "encode_and_h2d_seconds_once": round(work.encode_h2d_seconds, 4),
         },
-        "roofline": (hbm_roofline(work.name, work.kernel_match, work.kernel + " (candidates from the right table's global "
-                                  "inverted index)", k_ms, global_index_bytes(work), n_hits, default_shape=default_shape)
-                     if work.name in ("c2", "c2low", "c4") else
-                     valu_roofline(work.name, work.kernel_match, work.kernel + " (exact prune on)", k_ms, 1, alg_bytes,
-                                   compulsory, default_shape=default_shape)),
     }
+    if not args.full:
+        return result
+
+    # ---- per-kernel duration of the dominant kernel, HIP events on the launch stream
+    def kernel_ms(prune, reps):
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        buf.count.zero_()
+        work.launch(buf, stream, prune)
+        torch.cuda.synchronize(device)
+        ev0.record()
+        for _ in range(reps):
+            work.launch(buf, stream, prune)
+        ev1.record()
+        torch.cuda.synchronize(device)
+        return ev0.elapsed_time(ev1) / reps
+
+    k_ms = kernel_ms(True, KERNEL_REPS)
+    alg_bytes = work.n * work.m * work.bytes_per_pair
+    compulsory = work.left.nbytes() + work.right.nbytes() + n_hits * 16
+    result["roofline"] = (hbm_roofline(work.name, work.kernel_match, work.kernel + " (candidates from the right table's "
+                                       "global inverted index)", k_ms, global_index_bytes(work), n_hits,
+                                       default_shape=default_shape)
+                          if work.name in ("c2", "c2low", "c4") else
+                          valu_roofline(work.name, work.kernel_match, work.kernel + " (exact prune on)", k_ms, 1, alg_bytes,
+                                        compulsory, default_shape=default_shape))
     if extras and not args.no_extras:
         # exhaustive variant (prune off): fewer repetitions, it is the slow one
         ex_steps = EXHAUSTIVE_STEPS
@@ -1138,21 +1156,26 @@ def main():
     else:
         # the headline: BASELINE configs[2], the largest configuration quoted on one GPU ...
         result = run_raw(args, comm, device, "c3", args.rows, args.right_rows, args.threshold, dump=dump)
-        # ... and every other workload under the same clock, attached as sub-records.  N > 1: the configs
+        # ... and (--full) every other workload under the same clock, attached as sub-records.  N > 1: the configs
         # BASELINE.json quotes on 8 GPUs (c4, c5; c5w = c5 on word-like text), left rows divided over the ranks.
-        names = () if args.no_c4 else (("c2", "c2low", "c4", "c5", "c5w", "term") if world == 1 else ("c4", "c5", "c5w"))
+        # Without --full they run only when their outputs are dumped: one timed step each, no record.
+        names = () if args.no_c4 or not (args.full or dump is not None) else (
+            ("c2", "c2low", "c4", "c5", "c5w", "term") if world == 1 else ("c4", "c5", "c5w"))
         t_all = time.perf_counter()
         mirror = {}
         for name in names:
             release()
             t_sub = time.perf_counter()
+            steps = SUB_STEPS[name] if args.full else 1
             if name in ("c5", "c5w"):
-                sub = run_c5(args, comm, device, steps=SUB_STEPS[name], warmup=1, sub=True, words=name == "c5w", dump=dump)
+                sub = run_c5(args, comm, device, steps=steps, warmup=1, sub=True, words=name == "c5w", dump=dump)
             else:
                 # c2low / c4 share c2's CPU restatement (same function, same corpus generator): a short sample
                 sub = run_raw(args, comm, device, name, args.rows, 0 if name == "c4" else args.right_rows, None,
-                              steps=SUB_STEPS[name], extras=world == 1, cpu_scale=0.25 if name in ("c2low", "c4") else 1.0,
+                              steps=steps, extras=world == 1, cpu_scale=0.25 if name in ("c2low", "c4") else 1.0,
                               dump=dump)
+            if not args.full:
+                continue
             rec = {k: sub[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "scaling", "dtype", "config",
                                        "roofline", "exhaustive", "cpu_baseline", "at_score_threshold") if k in sub}
             rec["workload"] = sub["config"]["workload"]
@@ -1171,7 +1194,7 @@ def main():
             }
             if "at_score_threshold" in rec:
                 mirror[name]["ms_per_step_at_0.7"] = rec["at_score_threshold"]["ms_per_step"]
-        if names:
+        if names and args.full:
             result["sub_records_wall_seconds"] = round(time.perf_counter() - t_all, 1)
             result["config"]["sub"] = mirror
     if world > 1 and comm.dev_group is not None:

@@ -1,6 +1,6 @@
-"""bench.py's contract on the GPU box: one JSON line with the driver's fields, the roofline and
-cpu_baseline objects; the N = 2 path (two ranks sharing the GPU, gloo-staged exchange) launched the way
-the driver launches N > 1."""
+"""bench.py's contract on the GPU box: one JSON line with the driver's fields, and with --full the roofline and
+cpu_baseline objects; a plain run that measures the headline alone but dumps what --full dumps; the N = 2 path (two
+ranks sharing the GPU, gloo-staged exchange) launched the way the driver launches N > 1."""
 import json
 import socket
 import subprocess
@@ -46,7 +46,7 @@ def _check_roofline(roof, need_frac):
 @pytest.mark.parametrize("workload", ["c2", "c2low", "c3", "c4", "c5", "c5w", "term"])
 def test_bench_line(workload):
     rows = {"c2": "8000", "c2low": "8000", "c3": "8000", "c4": "60000", "c5": "6000", "c5w": "6000", "term": "3000"}[workload]
-    d = _line([sys.executable, "bench.py", "--workload", workload, "--rows", rows, "--steps", "2", "--warmup", "1"])
+    d = _line([sys.executable, "bench.py", "--workload", workload, "--rows", rows, "--steps", "2", "--warmup", "1", "--full"])
     assert all(k in d for k in CONTRACT), sorted(d)
     assert not any(k in d for k in ("c2", "c2low", "c3", "c4", "c5", "c5w", "term"))  # one workload alone: no sub-records
     assert "sub" not in d["config"]
@@ -68,15 +68,15 @@ def test_bench_line(workload):
 @pytest.mark.parametrize("workload", ["c3", "c5w"])
 def test_bench_dump_outputs(workload, tmp_path):
     """--dump-outputs: every grid's hits of the last step (float64 score, i, j) and its count, under 64 MB in all;
-    the same arguments give the same arrays (seeded inputs)."""
+    a --full run and a plain one give the same arrays (seeded inputs)."""
     import numpy as np
 
     rows = {"c3": "8000", "c5w": "6000"}[workload]
     cmd = [sys.executable, "bench.py", "--workload", workload, "--rows", rows, "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--dump-outputs"]
     runs = []
-    for k in range(2):
-        line = _line(cmd + [str(tmp_path / f"run{k}")])
+    for k, extra in enumerate((["--full"], [])):
+        line = _line(cmd + [str(tmp_path / f"run{k}")] + extra)
         runs.append((line, {p.name: np.load(p) for p in (tmp_path / f"run{k}").glob("*.npy")}))
     (d, arrays), (_, again) = runs
     assert sorted(arrays) == sorted(again) and all(np.array_equal(arrays[k], again[k]) for k in arrays)
@@ -104,7 +104,7 @@ def test_bench_default_roofline_is_a_fraction():
     single-GPU config (C3); every other BASELINE config, configs[4] on word-like text and the reference's default
     configuration ride along as sub-records under the same contract, and their numbers are mirrored as plain scalars
     into config.sub (round-3 verdict: the driver's parser keeps `config`, not unknown top-level keys)."""
-    d = _line([sys.executable, "bench.py", "--steps", "5", "--warmup", "2"])
+    d = _line([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--full"])
     _check_roofline(d["roofline"], need_frac=True)
     assert d["roofline"]["stale"] == (not d["roofline"]["profile"]["matches_source"])
     assert d["exhaustive"]["valu_issue_frac"] is None or 0.0 < d["exhaustive"]["valu_issue_frac"] <= 1.0
@@ -131,6 +131,28 @@ def test_bench_default_roofline_is_a_fraction():
     assert mirror["c5w"]["ms_per_step_at_0.7"] == d["c5w"]["at_score_threshold"]["ms_per_step"]
     assert d["c5"]["config"]["split_queue_overflowed"] is False
     assert d["sub_records_wall_seconds"] < 480
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the default run times the headline and nothing else: no per-kernel timing, roofline, exhaustive
+    run, CPU baseline or sub-record.  Its --dump-outputs still writes every grid a --full run writes, array for array."""
+    import numpy as np
+
+    cmd = [sys.executable, "bench.py", "--rows", "6000", "--steps", "2", "--warmup", "1", "--dump-outputs"]
+    plain = _line(cmd + [str(tmp_path / "plain")])
+    full = _line(cmd + [str(tmp_path / "full"), "--full", "--no-cpu-baseline"])
+    assert all(k in plain for k in CONTRACT if k != "roofline"), sorted(plain)
+    assert not any(k in plain for k in ("roofline", "exhaustive", "cpu_baseline", "sub_records_wall_seconds",
+                                        "c2", "c2low", "c4", "c5", "c5w", "term"))
+    assert "sub" not in plain["config"] and "C3" in plain["config"]["workload"] and plain["steps"] == 2
+    assert plain["config"]["hits_per_rank"] == full["config"]["hits_per_rank"] > 0
+    arrays = {p.name: np.load(p) for p in (tmp_path / "plain").glob("*.npy")}
+    again = {p.name: np.load(p) for p in (tmp_path / "full").glob("*.npy")}
+    assert sorted(arrays) == sorted(again) and all(np.array_equal(arrays[k], again[k]) for k in arrays)
+    grids = [f"{w}_{a}_{b}_{kind}" for w in ("c5", "c5w", "c5w_at_score_threshold")
+             for a, b in (("hap", "pop"), ("hap", "suep"), ("pop", "suep")) for kind in ("jaccard", "indel")]
+    names = ["c3", "c2", "c2low", "c4", "term"] + grids
+    assert sorted(arrays) == sorted([f"{n}_hits.npy" for n in names] + [f"{n}_count.npy" for n in names])
 
 
 def test_bench_rccl_failure_is_loud():
@@ -163,7 +185,7 @@ def test_bench_two_ranks_gloo():
         port = s.getsockname()[1]
     d = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--rows", "6000", "--dist-backend", "gloo"])
+               "--rows", "6000", "--dist-backend", "gloo", "--full"])
     assert d["n_gpus"] == 2 and d["config"]["pairs_per_step"] == 2 * 6000 * 6000 and "cpu_baseline" not in d
     # N > 1 carries the configs BASELINE.json quotes on 8 GPUs (c5w = c5 on word-like text), left rows divided over the ranks
     assert set(("c4", "c5", "c5w")) <= set(d) and "c2" not in d and "term" not in d and "C3" in d["config"]["workload"]

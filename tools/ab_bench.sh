@@ -7,6 +7,6 @@ show='import sys,json; d=json.loads(sys.stdin.read()); print("%-24s step %8.4f m
 for round in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = "-" ]; then unset NSM_HIP_LIBRARY; else export NSM_HIP_LIBRARY=$lib; fi
-    timeout -k 10 600 python bench.py --no-cpu-baseline "${args[@]}" 2>/dev/null | python -c "$show" "$(basename $lib)" || exit 1
+    timeout -k 10 600 python bench.py --full --no-cpu-baseline "${args[@]}" 2>/dev/null | python -c "$show" "$(basename $lib)" || exit 1
   done
 done
