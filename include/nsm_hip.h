@@ -15,6 +15,8 @@
  *   nsm_indel_levels_grid    the same loop with `fuzzy_match`
  *   nsm_*_raw_top_k          the same two score_funcs when only the k best candidates of each item are wanted
  *                            (compare/score_functions.py:6-27; the 1xM use in terminology/mesh.py:207-220)
+ *   nsm_*_levels_top_k       the levels grids (compare_terms, categories, blacklist) when only the k best candidates of each
+ *                            left item are wanted (types/comparable_data.py:195-243 followed by a per-item rank cut)
  *   nsm_sort_hits            Comparable.sort_by_score (types/comparable.py:69-70), made deterministic:
  *                            (score descending, i ascending, j ascending)
  *
@@ -294,6 +296,41 @@ int nsm_indel_levels_grid(const nsm_level_items* left, const nsm_str_table* left
                           double threshold, int32_t category_mode, uint32_t flags, nsm_hit* hits,
                           uint64_t capacity, unsigned long long* hit_count, void* workspace,
                           uint64_t workspace_bytes, double expected_survivors, void* stream);
+
+/* Per-item top-k of the LEVELS grids (ABI 5, additive): for every left item i the first
+ * min(k, #{j : score(i, j) >= threshold, pair allowed}) records of item i in the order (score descending, j ascending), j the
+ * caller's id (right->orig).  A pair is allowed when it passes the category predicate (category_mode, through the items'
+ * `cat` masks as in the grids) and is not banned.  The scores are the levels grids' doubles, bit for bit
+ * (sum_{s=1..max(Ll,Lr)} 2^-s * ratio(level min(s,Ll-1), level min(s,Lr-1)), accumulated in that order), so the records
+ * equal those of nsm_indel_levels_grid / nsm_jaccard_levels_grid followed by a per-item rank cut.  It stands in for
+ * gen_comparable (types/comparable_data.py:195-243) when only the best few candidates of an item are wanted.
+ *   banned_start, banned_j  device CSR of the blacklist keyed by the LEFT caller id (left->orig), or both NULL:
+ *              banned_j[banned_start[i] .. banned_start[i + 1]) are the banned right caller ids of left item i, sorted
+ *              ascending; banned_start has an entry for every left caller id up to the largest + 1 (ids that carry an
+ *              offset -- a sharded rank's block -- count from 0).  A banned pair never takes a slot; the list is only
+ *              consulted for a pair that is about to enter a list
+ *   out, out_count, k  as for nsm_*_raw_top_k: room for left->n * k records, written in ANY order (nsm_sort_hits orders
+ *              them); k >= 1 (else NSM_E_BADARG), clamped to right->n, beyond 4096 after clamping NSM_E_UNSUPPORTED
+ *   stats      device uint64[4] or NULL, added to: [0] pairs visited, [1] pairs past the category predicate and the
+ *              step-1 length / set-size bound, [2] pairs past the step-1 histogram / signature bound, [3] pairs that got
+ *              at least one exact level score (without NSM_FLAG_PRUNE: every allowed pair)
+ *   flags      NSM_FLAG_PRUNE: each item keeps a floor (its k-th best score so far) and a pair is skipped, or its steps cut
+ *              short, only when an upper bound of its score is strictly below max(threshold, floor).  Without it every
+ *              allowed pair is scored in full.  The records are the same either way
+ * Items must be ONE row each: partitioned tables (seg / seg_start) are NSM_E_UNSUPPORTED.  A stride, alphabet or width
+ * mismatch is NSM_E_BADARG; strides 64..512, alphabets up to 255, widths 16 / 32 / 64 and up to 64 levels are covered.
+ * Zero-level items are the host's business, as for the grids: a pair with one is never a record.  Scratch for the
+ * per-item lists (left->n * k records of 16 bytes) is allocated stream-ordered inside the call. */
+int nsm_indel_levels_top_k(const nsm_level_items* left, const nsm_str_table* left_strings,
+                           const nsm_level_items* right, const nsm_str_table* right_strings,
+                           double threshold, int32_t k, int32_t category_mode, uint32_t flags,
+                           const int32_t* banned_start /*device or NULL*/, const int32_t* banned_j /*device or NULL*/,
+                           nsm_hit* out /*device, left->n * k records*/, unsigned long long* out_count /*device, caller zeroes*/,
+                           uint64_t* stats /*device [4] or NULL*/, void* stream);
+int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set_table* right,
+                             double threshold, int32_t k, int32_t category_mode, uint32_t flags,
+                             const int32_t* banned_start, const int32_t* banned_j,
+                             nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream);
 
 /* Destroy the side stream and events the library created for `stream` on the current device.  The caller makes sure no nsm_indel_levels_grid work is still queued on that stream.  Returns 0. */
 int nsm_release(void* stream);

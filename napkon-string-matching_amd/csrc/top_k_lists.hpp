@@ -1,0 +1,137 @@
+// Per-row top-k lists shared by the top-k kernels (top_k_raw.hip, top_k_levels.hip): a wavefront keeps the lists of its
+// rows in stream-ordered scratch, each row's worst record is its floor, and the wave copies its lists out at the end.
+#pragma once
+#include "nsm_common.hpp"
+
+namespace nsm {
+
+constexpr int kTopMaxK = 4096;   // largest k (after clamping to the right table's rows)
+
+// The lists of the wave's G rows.  Row g's records are list[(row0 + g) k .. + cnt(g)); only this wave reads or writes
+// them, so a workgroup-scope fence orders lane 0's store before the wave's reloads (nothing else is needed).  The rows'
+// state is held "one row per lane" -- lane g of cnt_v is row g's count -- and read with v_readlane: a loop over the rows
+// needs no dynamically indexed register array (which would live in scratch).
+struct TopLists {
+  nsm_hit* list;
+  int k;
+  int row0;
+  int lane;
+  int cnt_v = 0;
+  double worst_v = 0.0;  // the floor, valid when the list is full
+  int wj_v = 0;
+  int wp_v = 0;
+  int changes = 0;  // records that entered a list so far: the floors can only have moved when this did
+
+  __device__ int cnt(int g) const { return __builtin_amdgcn_readlane(cnt_v, g); }
+  __device__ bool full(int g) const { return cnt(g) == k; }
+  __device__ double worst(int g) const {
+    const unsigned long long b = __double_as_longlong(worst_v);
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b), g));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), g));
+    return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+  }
+  // max(threshold, floor): what a pair's upper bound must reach to matter to row g
+  __device__ double eff(int g, double threshold) const { return full(g) ? fmax(threshold, worst(g)) : threshold; }
+  // an eligible record (score >= threshold) enters row g's list
+  __device__ bool beats(int g, double s, int j) const {
+    if (!full(g)) return true;
+    const double w = worst(g);
+    return s > w || (s == w && j < __builtin_amdgcn_readlane(wj_v, g));
+  }
+
+  // the worst record of row g's full list (lowest score, then largest j): one wave-wide reduction
+  __device__ void rescan(int g) {
+    const nsm_hit* row = list + static_cast<size_t>(row0 + g) * k;
+    double s = __builtin_inf();
+    int j = -1, pos = -1;
+    for (int q = lane; q < k; q += kWave) {
+      const nsm_hit h = row[q];
+      if (h.score < s || (h.score == s && h.j > j)) { s = h.score; j = h.j; pos = q; }
+    }
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      const double s2 = __shfl_xor(s, off);
+      const int j2 = __shfl_xor(j, off), p2 = __shfl_xor(pos, off);
+      if (s2 < s || (s2 == s && j2 > j)) { s = s2; j = j2; pos = p2; }
+    }
+    if (lane == g) { worst_v = s; wj_v = j; wp_v = pos; }
+  }
+
+  // wave-uniform call, all lanes enabled: put (s, i, j) into row g's list if it belongs there
+  __device__ void offer(int g, double s, int i, int j) {
+    if (!beats(g, s, j)) return;
+    const bool was_full = full(g);
+    const int slot = was_full ? __builtin_amdgcn_readlane(wp_v, g) : cnt(g);
+    if (lane == 0) {
+      nsm_hit h;
+      h.score = s;
+      h.i = i;
+      h.j = j;
+      list[static_cast<size_t>(row0 + g) * k + slot] = h;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    ++changes;
+    if (!was_full && lane == g) ++cnt_v;
+    if (was_full || slot + 1 == k) rescan(g);
+  }
+
+  // lanes with `ok` hold an eligible record (s, j) for row g: offer them one by one (the floor rises on the way)
+  __device__ void offer_lanes(int g, bool ok, double s, int i, int j) {
+    for (unsigned long long todo = __ballot(ok); todo; todo &= todo - 1ull) {
+      const int leader = __builtin_ctzll(todo);
+      const unsigned long long b = __double_as_longlong(s);
+      const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b), leader));
+      const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), leader));
+      const double s_l = __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+      offer(g, s_l, i, __builtin_amdgcn_readlane(j, leader));
+    }
+  }
+
+  // copy the lists to out[*out_count ..] (one atomic per wave) and add the wave's counters to stats
+  __device__ void flush(int rows, nsm_hit* __restrict__ out, unsigned long long* __restrict__ out_count,
+                        unsigned long long* __restrict__ stats, const unsigned long long (&st)[4]) {
+    int total = 0;
+    for (int g = 0; g < rows; ++g) total += cnt(g);
+    unsigned long long base = 0;
+    if (lane == 0 && total) base = atomicAdd(out_count, static_cast<unsigned long long>(total));
+    base = (static_cast<unsigned long long>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(base >> 32), 0))) << 32) |
+           static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(base), 0));
+    for (int g = 0; g < rows; ++g) {
+      const nsm_hit* row = list + static_cast<size_t>(row0 + g) * k;
+      const int n = cnt(g);
+      for (int q = lane; q < n; q += kWave) out[base + q] = row[q];
+      base += n;
+    }
+    if (stats) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        unsigned long long v = st[c];
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off);
+        if (lane == 0 && v) atomicAdd(stats + c, v);
+      }
+    }
+  }
+};
+
+// Scratch for the per-row lists, stream-ordered: it is freed behind the kernel on the same stream.
+static int with_lists(int n_left, int k, hipStream_t s, nsm_hit** list) {
+  const size_t bytes = static_cast<size_t>(n_left) * static_cast<size_t>(k) * sizeof(nsm_hit);
+  return hip_status(hipMallocAsync(reinterpret_cast<void**>(list), bytes ? bytes : 1, s), "top_k list scratch");
+}
+
+// k after clamping to the right side, or an error status (k < 1: NSM_E_BADARG, beyond kTopMaxK: NSM_E_UNSUPPORTED)
+static int clamp_k(const char* who, int32_t k, int32_t n_right, int* k_eff) {
+  if (k < 1) {
+    set_error("%s: k = %d (must be >= 1)", who, k);
+    return NSM_E_BADARG;
+  }
+  *k_eff = k < n_right ? k : n_right;
+  if (*k_eff > kTopMaxK) {
+    set_error("%s: k = %d exceeds the supported %d", who, *k_eff, kTopMaxK);
+    return NSM_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+}  // namespace nsm

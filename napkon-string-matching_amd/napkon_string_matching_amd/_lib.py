@@ -112,6 +112,8 @@ EXPORTS = (
     "nsm_jaccard_any_grid",
     "nsm_indel_raw_top_k",
     "nsm_jaccard_raw_top_k",
+    "nsm_indel_levels_top_k",
+    "nsm_jaccard_levels_top_k",
 )
 
 _lib = None
@@ -160,6 +162,11 @@ def load() -> ctypes.CDLL:
                   ctypes.c_void_p]
     lib.nsm_indel_raw_top_k.argtypes = [P(NsmStrTable), P(NsmStrTable)] + top_k_tail
     lib.nsm_jaccard_raw_top_k.argtypes = [P(NsmSetTable), P(NsmSetTable)] + top_k_tail
+    # threshold, k, category_mode, flags, banned_start, banned_j, out, out_count, stats, stream
+    levels_top_k_tail = [ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.nsm_indel_levels_top_k.argtypes = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable)] + levels_top_k_tail
+    lib.nsm_jaccard_levels_top_k.argtypes = [P(NsmSetTable), P(NsmSetTable)] + levels_top_k_tail
     # hits, scratch, capacity, hit_count, n_hint, id_limit, stream
     lib.nsm_sort_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_u64, ctypes.c_void_p, c_u64, ctypes.c_uint32,
                                   ctypes.c_void_p]

@@ -255,6 +255,77 @@ def jaccard_raw_top_k(left: SetTable, right: SetTable, k: int, threshold: float,
         left.n, right.n, k, left.ids.device, "nsm_jaccard_raw_top_k", stats, id_limit)
 
 
+# ------------------------------------------------------------------------------- levels top-k
+def banned_csr(banned, n_ids: int, device):
+    """The device CSR of a blacklist that ``nsm_*_levels_top_k`` read: ``banned`` = (left ids, right ids) of the banned
+    pairs, in the tables' caller ids (``orig``); ``n_ids`` = one more than the largest left caller id.  Returns
+    (banned_start int32 [n_ids + 1], banned_j int32, each item's ids ascending), or (None, None) for no blacklist."""
+    if banned is None:
+        return None, None
+    bi = np.asarray(banned[0], dtype=np.int64).reshape(-1)
+    bj = np.asarray(banned[1], dtype=np.int64).reshape(-1)
+    if bi.shape != bj.shape:
+        raise ValueError("banned: the left and right id arrays differ in length")
+    if len(bi) == 0:
+        return None, None
+    if int(bi.min()) < 0 or int(bj.min()) < 0:
+        raise ValueError("banned: caller ids must be >= 0")
+    n = max(int(n_ids), int(bi.max()) + 1)
+    order = np.lexsort((bj, bi))
+    start = np.zeros(n + 1, dtype=np.int32)
+    start[1:] = np.cumsum(np.bincount(bi, minlength=n))
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+    return to_dev(start), to_dev(bj[order])
+
+
+def _left_id_limit(orig: torch.Tensor, n: int) -> int:
+    return int(orig[:n].max().item()) + 1 if n else 0
+
+
+def indel_levels_top_k(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, k: int,
+                       threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
+                       stats: Optional[list] = None) -> Hits:
+    """For every left item the first ``min(k, #hits of its row)`` records of ``indel_levels_grid(...)`` without the
+    ``banned`` pairs, in the order (score descending, j ascending), all of them in canonical order.  ``banned``: None or
+    (left ids, right ids) of pairs that never take a slot, in caller ids.  Tables must be encoded with
+    ``partition=False``.  ``stats``: a list that receives [pairs visited, pairs past the category predicate and the
+    length bound, pairs past the histogram bound, pairs that got an exact level score]."""
+    k = check_k(k)
+    lib = _lib.load()
+    if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
+        category_mode = left.category_mode
+    li, ls, ri, rs = left.struct(), left_strings.struct(), right.struct(), right_strings.struct()
+    flags = _lib.FLAG_PRUNE if prune else 0
+    dev = left.first.device
+    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), dev)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_indel_levels_top_k(
+        li, ls, ri, rs, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
+        st.data_ptr(), stream), left.n, right.n, k, dev, "nsm_indel_levels_top_k", stats)
+
+
+def jaccard_levels_top_k(left: SetTable, right: SetTable, k: int, threshold: float, category_mode: int = _lib.CAT_NONE,
+                         prune: bool = True, banned=None, stats: Optional[list] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_levels_top_k`` (tables from ``SetTable.from_levels`` /
+    ``from_nested_arrays`` with ``partition=False``); stats[2] counts the pairs past the signature bound."""
+    k = check_k(k)
+    if left.nlev is None or right.nlev is None:
+        raise ValueError("levels top-k needs tables built with SetTable.from_levels")
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    lib = _lib.load()
+    if left.category_mode is not None:
+        category_mode = left.category_mode
+    ls, rs = left.struct(), right.struct()
+    flags = _lib.FLAG_PRUNE if prune else 0
+    dev = left.ids.device
+    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), dev)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_jaccard_levels_top_k(
+        ls, rs, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
+        st.data_ptr(), stream), left.n, right.n, k, dev, "nsm_jaccard_levels_top_k", stats)
+
+
 # ------------------------------------------------------------------------------- levels grids
 def jaccard_levels_grid(
     left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True,

@@ -346,10 +346,16 @@ class ComparableData:
         identifier_column_left: Optional[str] = None,
         identifier_column_right: Optional[str] = None,
         *args,
+        top_k: Optional[int] = None,
         **kwargs,
     ) -> Comparable:
         """:69-128.  Scores at ``cache_threshold or score_threshold``, keeps ``>= score_threshold``,
         orders by score descending.
+
+        ``top_k``: keep only the first ``top_k`` pairs of every left item in the order (score descending, right item
+        ascending) -- the frame ``compare()`` returns without it, restricted to those pair labels (rapidfuzz's
+        ``process.extract(limit=)`` over ``compare_terms``).  Each item's pairs are cut in score order, so cutting at
+        ``cache_threshold`` and then filtering at ``score_threshold`` keeps the meaning of both.
 
         Compare cache: the reference keys ``compared__score_{md5}.json`` by a hash
         that embeds object addresses (``str(kwargs.items())`` of ``Mapping`` objects, :61-67), so it
@@ -359,12 +365,14 @@ class ComparableData:
         is the reference's: ``{"left_name", "right_name", "data": [records]}`` (indent 4); like
         upstream, a frame read back from the cache carries a fresh RangeIndex instead of pair labels.
         """
+        if top_k is not None:
+            top_k = grid.check_k(top_k)
         first = cache_threshold if cache_threshold else score_threshold
         cache_file = None
         if cached and cache_dir is not None:
             cache_file = Path(cache_dir) / CACHE_FILE_PATTERN.format(
                 self._hash_compare_args(other, existing_mappings_whitelist, existing_mappings_blacklist,
-                                        compare_column, first, kwargs))
+                                        compare_column, first, kwargs, top_k))
         # hit or miss is decided ONCE for all ranks of a sharded run (rank 0 looks, everybody follows): with a
         # rank-local exists() the ranks can disagree -- a cache_dir that is not shared between nodes, or a repeated
         # compare() where one rank looks before rank 0's rename has landed -- and the ranks that miss would then
@@ -387,6 +395,7 @@ class ComparableData:
                 compare_column=compare_column,
                 identifier_column_left=identifier_column_left,
                 identifier_column_right=identifier_column_right,
+                top_k=top_k,
                 **kwargs,
             )
             if cache_file is not None:
@@ -410,7 +419,7 @@ class ComparableData:
         result.sort_by_score()
         return result
 
-    def _hash_compare_args(self, other, whitelist, blacklist, compare_column, cache_threshold, kwargs) -> str:
+    def _hash_compare_args(self, other, whitelist, blacklist, compare_column, cache_threshold, kwargs, top_k=None) -> str:
         other_csv = other.to_csv() if hasattr(other, "to_csv") else pd.DataFrame(other).to_csv(index=False)
         parts = [
             self.to_csv(), other_csv,
@@ -420,6 +429,8 @@ class ComparableData:
             json.dumps({k: kwargs.get(k) for k in ("score_func", "filter_categories", "category_column", "left_name",
                                                     "right_name")}, sort_keys=True, default=str),
         ]
+        if top_k is not None:  # (absent from the key otherwise: the keys of plain calls stay what they were)
+            parts.append(f"top_k={int(top_k)}")
         return md5("\x1f".join(parts).encode("utf-8"), usedforsecurity=False).hexdigest()
 
     def gen_comparable(
@@ -437,9 +448,13 @@ class ComparableData:
         identifier_column_left: Optional[str] = None,
         identifier_column_right: Optional[str] = None,
         *args,
+        top_k: Optional[int] = None,
         **kwargs,
     ) -> Comparable:
-        """:133-246 (steps 1-12 of SURVEY.md 3.2), the per-pair part on the GPU."""
+        """:133-246 (steps 1-12 of SURVEY.md 3.2), the per-pair part on the GPU.  ``top_k``: per left item only the
+        first ``top_k`` pairs (score descending, right item ascending) of what would be returned (``compare``)."""
+        if top_k is not None:
+            top_k = grid.check_k(top_k)
         plugin = getattr(score_functions, score_func)  # AttributeError for an unknown name (:150)
         whitelist = _as_mapping(existing_mappings_whitelist)
         blacklist = _as_mapping(existing_mappings_blacklist)
@@ -478,6 +493,9 @@ class ComparableData:
                 raise IndexError("single positional indexer is out-of-bounds")  # df.iloc[0] at :465
             cl, cr = list(lf[category_column]), list(rf[category_column])
             cats = _Categories(cl, cr, cl[first[0]], cr[first[1]])
+            if top_k is not None and not cats.on_device:
+                raise NotImplementedError("top_k with more than 64 distinct category labels (the predicate must run on the "
+                                          "device, where each item keeps its list)")
         elif n_l == 0 or n_r == 0:
             # the reference's blacklist step indexes the cross join with a list of booleans (:549-552); for
             # an EMPTY cross join that list is empty, pandas reads it as "no columns", and :223-232 then
@@ -503,10 +521,27 @@ class ComparableData:
             row_lo, row_hi = distributed.shard_bounds(n_l, rank, world_size)
             keep_l = keep_l[(keep_l >= row_lo) & (keep_l < row_hi)]
             extra_hits = [p for p in extra_hits if row_lo <= p[0] < row_hi]
+        if top_k is not None and min(top_k, int(keep_r.size)) > grid.TOP_K_MAX:
+            raise NotImplementedError(f"top_k = {min(top_k, int(keep_r.size))} (after clamping to the right side's "
+                                      f"{int(keep_r.size)} items) exceeds the supported {grid.TOP_K_MAX}")
         logger.info("calculate score")
         host_filter = bool(banned) or (cats is not None and not cats.on_device)
         pending = None
-        if keep_l.size and keep_r.size:
+        if keep_l.size and keep_r.size and top_k is not None:
+            # per-item lists on the device: categories and blacklist go to the kernel, which keeps each item's best
+            on_device = cats is not None
+            hits = _levels_top_k(
+                plugin,
+                [levels_l[k] for k in keep_l],
+                [levels_r[k] for k in keep_r],
+                score_threshold,
+                top_k,
+                cats.left_mask[keep_l] if on_device else None,
+                cats.right_mask[keep_r] if on_device else None,
+                cats.mode if on_device else _lib.CAT_NONE,
+                banned=_local_banned(banned, keep_l, keep_r),
+            )
+        elif keep_l.size and keep_r.size:
             on_device = cats is not None and cats.on_device
             hits = _levels_grid(
                 plugin,
@@ -527,7 +562,8 @@ class ComparableData:
             # the buffers go GPU -> all-gather -> GPU at a capacity agreed with one MAX all-reduce; otherwise the ranks
             # exchange what they have filtered on the host.  The choice is collective (one MIN all-reduce).
             nothing_to_score = not (keep_l.size and keep_r.size)  # (this rank's shard: it then contributes an empty buffer)
-            direct = distributed.agree_all((pending is not None or nothing_to_score) and not extra and not host_filter)
+            direct = distributed.agree_all(top_k is None and (pending is not None or nothing_to_score) and not extra and
+                                           not host_filter)
         else:
             direct = False
         if direct:
@@ -544,8 +580,12 @@ class ComparableData:
                 ej = np.array([p[1] for p in extra_hits], dtype=np.int64)
                 hi, hj, hs = np.concatenate([hi, ei]), np.concatenate([hj, ej]), np.concatenate([hs, np.zeros(len(ei))])
 
+            if top_k is not None:
+                # (the kernel applied categories and blacklist; the zero-level pairs join the per-item selection)
+                sel = grid.select_top_k(grid.Hits(hs, hi, hj), top_k)
+                hi, hj, hs = sel.i, sel.j, sel.score
             # ---- per hit: blacklist (and categories when they could not go to the device)
-            if len(hs) and host_filter:
+            elif len(hs) and host_filter:
                 ok = np.fromiter(
                     (
                         (int(a), int(b)) not in banned and (cats is None or cats.on_device or cats.match(int(a), int(b)))
@@ -680,10 +720,13 @@ def _may_be_wide_sets(*sides) -> bool:
     return any(size(it[-1]) > 64 for items in sides for it in items if len(it))
 
 
-def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, defer=False):
+def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, defer=False, top_k=None,
+                         banned=None):
     """The suffix-nested fast layout of both sides + ``nsm_jaccard_levels_grid``; raises ``tables.IrregularLevels`` when an
-    item does not fit it."""
-    part = tables.partition_allowed(cat_mode, cat_l, cat_r)
+    item does not fit it.  ``top_k``: ``nsm_jaccard_levels_top_k`` instead, without the ``banned`` pairs (tables without a
+    category partition and without an inverted index)."""
+    part = tables.partition_allowed(cat_mode, cat_l, cat_r) if top_k is None else False
+    index = None if top_k is None else False
     memo = ComparableData._item_memo
     if memo is not None:
         # inside item_memo(): one vocabulary for the whole run, every item encoded once (tables.LevelPool,
@@ -696,7 +739,8 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
         for (ids, plen, nlev), side, cat in zip(rows, ("left", "right"), (cat_l, cat_r)):
             deepest = max(4, -(-(int(nlev.max()) if len(nlev) else 1) // 4) * 4)
             sides.append(tables.SetTable.from_nested_arrays(ids, plen[:, :deepest], nlev, side, dev, categories=cat,
-                                                            width=width, category_mode=cat_mode, partition=part))
+                                                            width=width, category_mode=cat_mode, partition=part,
+                                                            index=index))
         lt, rt = sides
     else:
         vocab = tables.Vocabulary()
@@ -705,11 +749,13 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
             max((len(set(it[-1])) for it in sl if it), default=1), max((len(set(it[-1])) for it in sr if it), default=1)
         )
         lt = tables.SetTable.from_levels(sl, "left", dev, vocab, width=width, categories=cat_l, category_mode=cat_mode,
-                                         partition=part)
+                                         partition=part, index=index)
         rt = tables.SetTable.from_levels(sr, "right", dev, vocab, width=width, categories=cat_r,
-                                         category_mode=cat_mode, partition=part)
+                                         category_mode=cat_mode, partition=part, index=index)
     if len(vocab) >= 1 << 25:
         raise NotImplementedError("vocabulary of 2^25 or more distinct tokens")
+    if top_k is not None:
+        return grid.jaccard_levels_top_k(lt, rt, top_k, threshold, category_mode=cat_mode, banned=banned)
     # the library picks the inverted-index kernel from the threshold alone (it cannot see the vocabulary); the host
     # can: with a large vocabulary few pairs share an id and the index wins at every threshold (3 x 100k^2 items of
     # ~8 ids: 20k words 2.1 vs 2.2 ms at 0.7 and 4.2 vs 22 ms at 0.1; 2^17 words 1.0 vs 2.3 ms and 1.8 vs 20.9 ms)
@@ -772,3 +818,98 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
         return wide.split_grid(split[0], split[1], fast, general)
     li, ls, ri, rs = tables.encode_level_strings(ops_l, ops_r, dev, cat_l, cat_r, cat_mode)
     return grid.indel_levels_grid(li, ls, ri, rs, threshold, category_mode=cat_mode, defer=defer)
+
+
+# =============================================================================== per-item top-k
+def _local_banned(banned: set, keep_l: np.ndarray, keep_r: np.ndarray):
+    """The blacklist's pairs among the items ``keep_l`` x ``keep_r`` as (left, right) positions in those lists."""
+    if not banned:
+        return None
+    pos_l = {int(g): k for k, g in enumerate(keep_l)}
+    pos_r = {int(g): k for k, g in enumerate(keep_r)}
+    pairs = [(pos_l[a], pos_r[b]) for a, b in banned if a in pos_l and b in pos_r]
+    if not pairs:
+        return None
+    arr = np.array(pairs, dtype=np.int64)
+    return arr[:, 0], arr[:, 1]
+
+
+def _restrict_banned(banned, li, ri):
+    """``banned`` (positions in the parent lists) restricted to the sub-grid ``li`` x ``ri``, in positions of the sub-lists."""
+    if banned is None:
+        return None
+    li, ri = np.asarray(li, dtype=np.int64), np.asarray(ri, dtype=np.int64)
+    bi, bj = banned
+    size = lambda idx, b: int(max(idx.max(initial=-1), b.max(initial=-1))) + 1
+    pos_l = np.full(size(li, bi), -1, dtype=np.int64)
+    pos_r = np.full(size(ri, bj), -1, dtype=np.int64)
+    pos_l[li], pos_r[ri] = np.arange(len(li)), np.arange(len(ri))
+    ok = (pos_l[bi] >= 0) & (pos_r[bj] >= 0)
+    return (pos_l[bi][ok], pos_r[bj][ok]) if ok.any() else None
+
+
+def _drop_banned(hits: grid.Hits, banned, li, ri) -> grid.Hits:
+    """``hits`` of the sub-grid ``li`` x ``ri`` without the pairs of ``banned`` (positions in the parent lists)."""
+    if banned is None or len(hits) == 0:
+        return hits
+    li, ri = np.asarray(li, dtype=np.int64), np.asarray(ri, dtype=np.int64)
+    n_r = int(max(ri.max(initial=-1), banned[1].max(initial=-1))) + 1
+    ok = ~np.isin(li[hits.i] * n_r + ri[hits.j], banned[0] * n_r + banned[1])
+    return grid.Hits(hits.score[ok], hits.i[ok], hits.j[ok])
+
+
+def _levels_top_k(plugin, levels_l, levels_r, threshold, k, cat_l, cat_r, cat_mode=_lib.CAT_NONE, banned=None) -> grid.Hits:
+    """Per left item the first ``k`` records (score descending, right index ascending) of ``_levels_grid`` without the
+    ``banned`` pairs ((left, right) positions in these lists, or None).  Items the fast kernels take go through
+    ``nsm_*_levels_top_k`` (tables without a category partition: an item must stay one row to keep one list); wide or
+    irregular items through the general kernels at the threshold, cut per item on the host; the parts are disjoint in j
+    for every i, so the per-item selection over their union is the answer."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise _lib.NsmLibraryError("the match loop runs on an MI355X (HIP device); there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    from .. import wide
+
+    sub = lambda seq, idx: [seq[q] for q in idx]
+    cut = lambda cat, idx: None if cat is None else np.asarray(cat)[np.asarray(idx, dtype=np.int64)]
+    if plugin.kind == "sets":
+        as_set_levels = lambda it: [lv if isinstance(lv, list) else lv.split() for lv in it]
+
+        def split_route(split):
+            fast = lambda li, ri: _levels_top_k(plugin, sub(levels_l, li), sub(levels_r, ri), threshold, k, cut(cat_l, li),
+                                                cut(cat_r, ri), cat_mode, _restrict_banned(banned, li, ri))
+            general = lambda li, ri: grid.select_top_k(_drop_banned(wide.jaccard_any_grid(
+                [as_set_levels(levels_l[q]) for q in li], [as_set_levels(levels_r[q]) for q in ri], threshold, cut(cat_l, li),
+                cut(cat_r, ri), cat_mode, device=dev), banned, li, ri), k)
+            return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)
+
+        split = wide.wide_set_items([as_set_levels(it) for it in levels_l], [as_set_levels(it) for it in levels_r]) \
+            if _may_be_wide_sets(levels_l, levels_r) else None
+        if split is not None:
+            return split_route(split)
+        try:
+            return _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, top_k=k,
+                                        banned=banned)
+        except tables.IrregularLevels:
+            split = wide.wide_set_items([as_set_levels(it) for it in levels_l], [as_set_levels(it) for it in levels_r],
+                                        nesting=True)
+            if split is None:
+                raise
+            return split_route(split)
+    prep = lambda items: ComparableData._memoised(
+        "fuzzy", items, lambda it: [score_functions.fuzzy_operand(lv) for lv in it])
+    ops_l, ops_r = prep(levels_l), prep(levels_r)
+
+    def fast(li, ri):
+        a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
+                                                 partition=False)
+        return grid.indel_levels_top_k(a, b, c, d, k, threshold, category_mode=cat_mode, banned=_restrict_banned(banned, li, ri))
+
+    split = wide.wide_string_items(ops_l, ops_r)
+    if split is None:
+        return fast(range(len(ops_l)), range(len(ops_r)))
+    # level strings of more than 512 code units / a grid of more than 255 distinct code units (wide.py)
+    general = lambda li, ri: grid.select_top_k(_drop_banned(wide.indel_any_grid(
+        sub(ops_l, li), sub(ops_r, ri), threshold, cut(cat_l, li), cut(cat_r, ri), cat_mode, device=dev), banned, li, ri), k)
+    return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)

@@ -1,12 +1,18 @@
 """Per-item top-k (nsm_*_raw_top_k) against the threshold grid plus a per-row selection.  Prints ONE JSON line.
 
     python tools/bench_top_k.py [--reps 20] [--c3 200000] [--term 20000] [--c2 50000]
+    python tools/bench_top_k.py --levels [--reps 5] [--term 20000] [--c5w 100000]
 
 Cases: synthetic.c3_corpus() fuzzy at k in {1, 10, 100} x thresholds {0, 0.5, 0.8}; Term-shaped fuzzy operands
 (synthetic.term_cohort, the reference's default configuration) at 0.5; c2_corpus() Jaccard at {0, 0.1, 0.5}, k = 10.
 Per case: ms per call (HIP events, after a warm-up), records, stats[0..3] / (N M), and -- where the threshold grid's hits
 fit in 2^28 records, counted from its warm-up call -- the grid's own time (device grid, sort, copy of the hits to the host)
 and, separately, the host-side per-row selection of those hits; else "n/a" and the bytes the hits would need.
+
+--levels: the levels-mode queries (nsm_*_levels_top_k) instead: Term-shaped items (compare_terms x fuzzy_match, the
+reference's default configuration) at 0.5 and 0 with k in {1, 10}; a c5w-shaped grid (configs[4] on word-like text, list
+categories) at 0.5 and 0, k = 10, for both score functions; and ComparableData.compare(..., top_k=10) end to end against
+compare() on Term-shaped cohorts (one call each, wall clock).
 """
 import argparse
 import json
@@ -63,13 +69,88 @@ def case(name, lt, rt, n, m, top_k, raw_grid, k, thr, reps):
     return row
 
 
+def levels_case(name, run_top_k, run_grid, n, m, k, thr, reps):
+    """``case`` for the levels queries: ``run_top_k(k, thr, stats)`` / ``run_grid(thr)`` close over their tables."""
+    return case(name, None, None, n, m, lambda _l, _r, kk, t, stats: run_top_k(kk, t, stats),
+                lambda _l, _r, t: run_grid(t), k, thr, reps)
+
+
+def term_frame(items, prefix):
+    import pandas as pd
+
+    from napkon_string_matching_amd.types.questionnaire import Questionnaire
+
+    rows = [{"Identifier": f"{prefix}{q}", "Variable": f"v{q}", "Sheet": "s", "Category": ["c"], "Term": it,
+             "Tokens": [], "Parameter": ""} for q, it in enumerate(items)]
+    return Questionnaire(pd.DataFrame(rows))
+
+
+def main_levels(args) -> None:
+    dev = torch.device("cuda:0")
+    rows = []
+    a = synthetic.term_cohort(args.term, 1234)
+    b = synthetic.term_cohort(args.term, 5678, plant_from=a)
+    la = [[sf.fuzzy_operand(lv) for lv in it] for it in synthetic.term_levels(a)]
+    lb = [[sf.fuzzy_operand(lv) for lv in it] for it in synthetic.term_levels(b)]
+    tabs = tables.encode_level_strings(la, lb, dev, partition=False)
+    for thr in (0.5, 0.0):
+        for k in (1, 10):
+            rows.append(levels_case("term_levels_fuzzy", lambda kk, t, st: grid.indel_levels_top_k(*tabs, kk, t, stats=st),
+                                    lambda t: grid.indel_levels_grid(*tabs, t), args.term, args.term, k, thr, args.reps))
+
+    lex = synthetic.word_vocabulary()
+    hap = synthetic.c5_cohort(args.c5w, 3, lex=lex)
+    pop = synthetic.c5_cohort(args.c5w, 4, plant_from=hap, lex=lex)
+    mode = 2  # list x list categories: "intersect, or both empty"
+    cps = tables.encode_level_codes(synthetic.c5_level_codes(hap), synthetic.c5_level_codes(pop), len(synthetic.WORD_ALPHABET),
+                                    dev, hap["cat"], pop["cat"], mode, partition=False)
+    ptabs = tables.encode_level_codes(synthetic.c5_level_codes(hap), synthetic.c5_level_codes(pop), len(synthetic.WORD_ALPHABET),
+                                      dev, hap["cat"], pop["cat"], mode)  # (the grid's own, partitioned layout)
+    st_l = tables.SetTable.from_nested_arrays(hap["ids"], hap["plen"], hap["nlev"], "left", dev, categories=hap["cat"],
+                                              category_mode=mode, partition=False, index=False)
+    st_r = tables.SetTable.from_nested_arrays(pop["ids"], pop["plen"], pop["nlev"], "right", dev, categories=pop["cat"],
+                                              category_mode=mode, partition=False, index=False)
+    sp_l = tables.SetTable.from_nested_arrays(hap["ids"], hap["plen"], hap["nlev"], "left", dev, categories=hap["cat"],
+                                              category_mode=mode)
+    sp_r = tables.SetTable.from_nested_arrays(pop["ids"], pop["plen"], pop["nlev"], "right", dev, categories=pop["cat"],
+                                              category_mode=mode)
+    for thr in (0.5, 0.0):
+        rows.append(levels_case("c5w_levels_fuzzy", lambda kk, t, st: grid.indel_levels_top_k(*cps, kk, t, category_mode=mode,
+                                                                                             stats=st),
+                                lambda t: grid.indel_levels_grid(*ptabs, t, category_mode=mode), args.c5w, args.c5w, 10, thr,
+                                args.reps))
+        rows.append(levels_case("c5w_levels_jaccard", lambda kk, t, st: grid.jaccard_levels_top_k(st_l, st_r, kk, t,
+                                                                                                 category_mode=mode, stats=st),
+                                lambda t: grid.jaccard_levels_grid(sp_l, sp_r, t, category_mode=mode), args.c5w, args.c5w, 10,
+                                thr, args.reps))
+
+    # end to end: the public API on Term-shaped cohorts, the reference's default configuration at 0.5
+    left, right = term_frame(a, "hap"), term_frame(b, "pop")
+    kw = dict(score_func="fuzzy_match", compare_column="Term", left_name="hap", right_name="pop", score_threshold=0.5,
+              cached=False)
+    e2e = {"case": "term_compare", "n": args.term, "m": args.term, "score_threshold": 0.5}
+    left.compare(right, None, None, top_k=10, **kw)  # (warm-up: library, encoders)
+    for label, extra in (("compare_top_k10", {"top_k": 10}), ("compare", {})):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = left.compare(right, None, None, **kw, **extra)
+        e2e[label + "_s"] = round(time.perf_counter() - t0, 3)
+        e2e[label + "_rows"] = len(got)
+    rows.append(e2e)
+    print(json.dumps({"bench": "top_k_levels", "device": torch.cuda.get_device_name(0), "reps": args.reps, "cases": rows}))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--c3", type=int, default=200_000)
     ap.add_argument("--term", type=int, default=20_000)
     ap.add_argument("--c2", type=int, default=50_000)
+    ap.add_argument("--levels", action="store_true", help="the levels-mode queries instead (see above)")
+    ap.add_argument("--c5w", type=int, default=100_000)
     args = ap.parse_args()
+    if args.levels:
+        return main_levels(args)
     dev = torch.device("cuda:0")
     rows = []
 

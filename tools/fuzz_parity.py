@@ -25,7 +25,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=300.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--family", default=None, help="only this kernel family (jaccard_raw, indel_raw, jaccard_levels, indel_levels, indel_split, wide; "
-                    "indel_top_k and jaccard_top_k are drawn only when named here)")
+                    "indel_top_k, jaccard_top_k, indel_levels_top_k and jaccard_levels_top_k are drawn only when named here)")
     args = ap.parse_args()
 
     import numpy as np
@@ -93,6 +93,79 @@ def main():
         counts[family] = counts.get(family, 0) + 1
         thr = rng.choice(thresholds)
         n, m = rng.randint(1, 400), rng.randint(1, 600)
+        if family in ("indel_levels_top_k", "jaccard_levels_top_k"):
+            # per-item top-k of the levels grids (nsm_*_levels_top_k) against the definition: the oracle's levels grid
+            # without the banned pairs, cut per left item after rank k (score descending, j ascending).  Draws categories,
+            # banned pairs, depths, strides, k and thresholds.  Only through --family: the default draw is unchanged.
+            thr = rng.choice(thresholds + [-1.0, 0.0, -0.5])
+            n, m = rng.randint(1, 100), rng.randint(1, 200)
+            k = rng.choice([1, 1, 2, 3, 5, 10, rng.randint(1, m + 8), m, m + 3])
+            prune = rng.random() < 0.75
+            ncat = rng.choice([0, 0, 3, 6, 64])
+            mode = _lib.CAT_NONE if ncat == 0 else rng.choice([_lib.CAT_INTERSECT, _lib.CAT_INTERSECT_OR_BOTH_EMPTY])
+            lcat = rcat = None
+            if ncat:
+                def cats(cnt):
+                    out = np.zeros(cnt, dtype=np.uint64)
+                    for q in range(cnt):
+                        for _ in range(rng.choice([0, 1, 1, 2, 3])):
+                            out[q] |= np.uint64(1) << np.uint64(rng.randrange(ncat))
+                    return out
+
+                lcat, rcat = cats(n), cats(m)
+            if family == "jaccard_levels_top_k":
+                vocab = rng.choice([12, 60, 400, 20_000])
+                max_levels, max_new = rng.choice([1, 2, 4, 9, 20, 64]), rng.choice([1, 2, 3, 8])
+                left = [nested_item(rng, vocab, max_levels, max_new) for _ in range(n)]
+                right = [nested_item(rng, vocab, max_levels, max_new) for _ in range(m)]
+                dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda it: [list(lv) for lv in it])  # exact copies: ties
+                biggest = max(len(it[-1]) for it in left + right)
+                if biggest > 64:
+                    continue
+                width = rng.choice([w for w in (16, 32, 64) if w >= biggest])
+                vocabulary = tables.Vocabulary()
+                lt = tables.SetTable.from_levels(left, "left", dev, vocabulary, width=width, categories=lcat, category_mode=mode,
+                                                 partition=False, index=False)
+                rt = tables.SetTable.from_levels(right, "right", dev, vocabulary, width=width, categories=rcat, category_mode=mode,
+                                                 partition=False, index=False)
+                full = native.levels(False, left, right, thr, lcat, rcat, mode, cap=n * m + 1)
+                what = f"W={width} vocab={vocab} levels<={max_levels} new<={max_new}"
+            else:
+                hi = rng.choice([4, 10, 40, 64, 64, 120, 250, 500])
+                alphabet = rng.choice(["ab", "abc ", "abcdefghij klm", "abcdefghijklmnopqrstuvwxyz0123456789 ",
+                                       "".join(chr(0x100 + c) for c in range(250))])
+                max_levels = rng.choice([1, 2, 4, 4, 7, 64])
+                item = lambda: [rand_string(rng, alphabet, 0, hi) for _ in range(rng.randint(1, max_levels))]
+                left, right = [item() for _ in range(n)], [item() for _ in range(m)]
+                dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda it: list(it))  # exact copies: ties
+                li, ls, ri, rs = tables.encode_level_strings(left, right, dev, lcat, rcat, mode, partition=False)
+                cps = lambda items: [[[ord(c) for c in s_] for s_ in it] for it in items]
+                full = native.levels(True, cps(left), cps(right), thr, lcat, rcat, mode, cap=n * m + 1)
+                what = f"hi={hi} stride={ls.stride} |alphabet|={len(alphabet)} levels<={max_levels}"
+            # banned: random pairs and, per row, often its best pair (what the list would otherwise keep first)
+            banned = {(rng.randrange(n), rng.randrange(m)) for _ in range(rng.choice([0, 0, 3, n]))}
+            best = {}
+            for h in full:
+                if h[1] not in best or (-h[0], h[2]) < (-best[h[1]][0], best[h[1]][2]):
+                    best[h[1]] = h
+            banned |= {(i_, h[2]) for i_, h in best.items() if rng.random() < 0.3}
+            ban_arr = None
+            if banned:
+                arr = np.array(sorted(banned), dtype=np.int64)
+                ban_arr = (arr[:, 0], arr[:, 1])
+            what = (f"{family} {what} thr={thr} k={k} prune={prune} mode={mode} ncat={ncat} banned={len(banned)} {n}x{m}")
+            if family == "jaccard_levels_top_k":
+                got = grid.jaccard_levels_top_k(lt, rt, k, thr, category_mode=mode, prune=prune, banned=ban_arr)
+            else:
+                got = grid.indel_levels_top_k(li, ls, ri, rs, k, thr, category_mode=mode, prune=prune, banned=ban_arr)
+            rows = {}
+            for h in full:
+                if (h[1], h[2]) not in banned:
+                    rows.setdefault(h[1], []).append(h)
+            want = sorted((h for lst in rows.values() for h in sorted(lst, key=lambda t: (-t[0], t[2]))[:k]),
+                          key=lambda t: (-t[0], t[1], t[2]))
+            check(got, want, what)
+            continue
         if family in ("indel_top_k", "jaccard_top_k"):
             # per-item top-k (nsm_*_raw_top_k) against the definition: the oracle's threshold grid, cut per left item after
             # rank k in the order (score descending, j ascending).  Only through --family: the default draw is unchanged.
