@@ -9,13 +9,14 @@ non-zero with the failing round's seed.  Test infrastructure: not part of the pr
 import argparse
 import os
 import json
+import math
 import random
 import sys
 import time
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-for p in (str(ROOT), str(ROOT / "napkon-string-matching_amd")):
+for p in (str(ROOT), str(ROOT / "napkon-string-matching_amd"), str(ROOT / "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
@@ -25,7 +26,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=300.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--family", default=None, help="only this kernel family (jaccard_raw, indel_raw, jaccard_levels, indel_levels, indel_split, wide; "
-                    "indel_top_k, jaccard_top_k, indel_levels_top_k and jaccard_levels_top_k are drawn only when named here)")
+                    "indel_top_k, jaccard_top_k, indel_levels_top_k, jaccard_levels_top_k, wide_levels_indel and wide_levels_jaccard are "
+                    "drawn only when named here)")
     args = ap.parse_args()
 
     import numpy as np
@@ -93,6 +95,80 @@ def main():
         counts[family] = counts.get(family, 0) + 1
         thr = rng.choice(thresholds)
         n, m = rng.randint(1, 400), rng.randint(1, 600)
+        if family in ("wide_levels_indel", "wide_levels_jaccard"):
+            # the general kernels (csrc/any_grids.hip) called directly, levels mode: depths up to 300 in one wave, string
+            # lengths at the chunk seams / carry words / the cap, alphabets at 255 / 256 / 1023, nested or independent level
+            # sets, 64-bit category masks, thresholds from the list or exactly on an oracle score.  Only through --family.
+            from napkon_string_matching_amd import wide
+            from support import any_operands as ao
+
+            n, m = rng.randint(1, 40), rng.randint(1, 140)
+            deep = rng.random() < 0.5
+            depth = lambda: rng.choice([1, 2, 3, 4, 8, 63, 64, 65, 100, 300] if deep else [1, 1, 2, 3, 4, 8])
+            mode = rng.choice([_lib.CAT_NONE, _lib.CAT_INTERSECT, _lib.CAT_INTERSECT_OR_BOTH_EMPTY])
+            lcat, rcat = (None, None) if mode == _lib.CAT_NONE else (ao._masks(rng, n), ao._masks(rng, m))
+            if family == "wide_levels_indel":
+                alphabet = rng.choice([1, 4, 12, 255, 256, 1023])
+                edges = [0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257]
+                budget = [3]  # strings at the cap per grid (the oracle's LCS is quadratic)
+
+                def length(d):
+                    if d > 8:
+                        return rng.randint(0, 20)
+                    if budget[0] and rng.random() < 0.02:
+                        budget[0] -= 1
+                        return rng.choice([4095, 4096])
+                    return rng.choice(edges) if rng.random() < 0.4 else rng.randint(0, 90)
+
+                def item():
+                    d = depth()
+                    return [ao._units(rng, length(d), alphabet) for _ in range(d)]
+
+                def mutate(it):
+                    it = [list(lv) for lv in it]
+                    for _ in range(rng.randint(0, 2)):
+                        lv = it[rng.randrange(len(it))]
+                        if lv:
+                            at = rng.choice([0, len(lv) - 1, min(len(lv) - 1, 127), min(len(lv) - 1, 128), rng.randrange(len(lv))])
+                            lv[at:at + 1] = [] if rng.random() < 0.5 else [rng.randrange(alphabet)]
+                    return it if rng.random() < 0.7 else ao._recut(rng, it)
+
+                what = f"|alphabet|={alphabet}"
+            else:
+                nested = rng.random() < 0.5
+                vocab = rng.choice([30, 300, 5000])
+                width = lambda: rng.randint(65, min(300, vocab)) if vocab > 65 and rng.random() < 0.1 else rng.randint(1, min(vocab, 6))
+
+                def item(may_be_empty=False):
+                    d = depth()
+                    if nested:
+                        return ao._nested_item(rng, d, vocab, max_new=rng.choice([1, 2, min(40, vocab)]), start=rng.randint(1, 3))
+                    return [[] if may_be_empty and rng.random() < 0.1 else rng.sample(range(vocab), width()) for _ in range(d)]
+
+                def mutate(it):
+                    it = [list(lv) for lv in it]
+                    if rng.random() < 0.5:  # one more token from some level on (a nested item stays nested)
+                        at = rng.randrange(len(it))
+                        it = [lv + [vocab + 1] if k >= at else lv for k, lv in enumerate(it)]
+                    return it if rng.random() < 0.7 else ao._recut(rng, it)
+
+                what = f"nested={nested} vocab={vocab}"
+            left = [item() for _ in range(n)]
+            right = [item(True) if family == "wide_levels_jaccard" else item() for _ in range(m)]
+            dup_some(rng, left, right, rng.choice([0.0, 0.15, 0.5]), mutate)
+            g = ao.Grid(f"round{rnd}", "indel" if family == "wide_levels_indel" else "jaccard", left, right, cat_l=lcat, cat_r=rcat,
+                        mode=mode)
+            full = ao.oracle_call(g, 0.0)
+            if full and rng.random() < 0.5:  # exactly on a pair's score, or one ulp above it
+                thr = rng.choice(full)[0]
+                if rng.random() < 0.3:
+                    thr = math.nextafter(thr, 2.0)
+            want = ao.oracle_call(g, thr)
+            kl, kr = ao.kernel_operands(g)
+            fn = wide.indel_any_grid if g.kind == "indel" else wide.jaccard_any_grid
+            got = fn(kl, kr, thr, lcat, rcat, mode, capacity=rng.choice([None, 16]))
+            check(got, want, f"{family} {what} deep={deep} thr={thr!r} mode={mode} {n}x{m}")
+            continue
         if family in ("indel_levels_top_k", "jaccard_levels_top_k"):
             # per-item top-k of the levels grids (nsm_*_levels_top_k) against the definition: the oracle's levels grid
             # without the banned pairs, cut per left item after rank k (score descending, j ascending).  Draws categories,
