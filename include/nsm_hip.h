@@ -15,6 +15,8 @@
  *   nsm_indel_levels_grid    the same loop with `fuzzy_match`
  *   nsm_*_raw_top_k          the same two score_funcs when only the k best candidates of each item are wanted
  *                            (compare/score_functions.py:6-27; the 1xM use in terminology/mesh.py:207-220)
+ *   nsm_*_raw_top_k_grouped  the same with one record per group of right rows: MeshProvider.get_matches' sort +
+ *                            drop_duplicates(subset="Id") + limit (terminology/mesh.py:207-220)
  *   nsm_*_levels_top_k       the levels grids (compare_terms, categories, blacklist) when only the k best candidates of each
  *                            left item are wanted (types/comparable_data.py:195-243 followed by a per-item rank cut)
  *   nsm_sort_hits            Comparable.sort_by_score (types/comparable.py:69-70), made deterministic:
@@ -254,6 +256,34 @@ int nsm_indel_raw_top_k(const nsm_str_table* left, const nsm_str_table* right, d
                         void* stream);
 int nsm_jaccard_raw_top_k(const nsm_set_table* left, const nsm_set_table* right, double threshold, int32_t k,
                           uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream);
+
+/* Grouped per-item top-k of the RAW grids (ABI 5, additive): right row j belongs to group right_group[j] and every left row
+ * gets the best row of each group, then the k best groups.  For left row i:
+ *   1. eligible records are the pairs (i, j) with score(i, j) >= threshold, scored exactly as the RAW grids score them;
+ *   2. a group's REPRESENTATIVE is its eligible record that comes first in (score descending, j ascending);
+ *   3. the answer is the first min(k, #groups with an eligible record) representatives in (score descending, j ascending).
+ * This is MeshProvider.get_matches of the reference (terminology/mesh.py:207-220): score one term against every synonym
+ * row, keep the rows >= score_threshold, sort by score, drop_duplicates(subset="Id") -- one row per heading, the best one --
+ * cut after `limit` headings (ties in table order).  With every row a group of its own the records are those of
+ * nsm_*_raw_top_k; with one group there is at most one record per left row.  The output is bounded by left->n * k records
+ * whatever the number of rows per group.
+ *   right_group  device int32, indexed by the caller's j, i.e. by the values of right->orig (one entry for every value up
+ *              to the largest); arbitrary values, compared for equality only -- nothing is indexed with them.  NULL is
+ *              NSM_E_BADARG
+ *   out, out_count, stats, flags, k  as for nsm_*_raw_top_k (k >= 1 else NSM_E_BADARG, clamped to right->n, beyond 4096
+ *              after clamping NSM_E_UNSUPPORTED); the same argument checks apply, before any launch
+ * A list keeps at most one record per group; the group ids of its records live in a second stream-ordered scratch buffer
+ * (left->n * k int32) next to the lists.  NSM_FLAG_PRUNE skips exactly what it skips in nsm_*_raw_top_k (the floor of a
+ * full list is a representative's score and representatives only improve); without it every pair is scored
+ * (stats[3] = left->n * right->n).  The records are the same either way. */
+int nsm_indel_raw_top_k_grouped(const nsm_str_table* left, const nsm_str_table* right,
+                                const int32_t* right_group /*device; indexed by the caller's j (right->orig values)*/,
+                                double threshold, int32_t k, uint32_t flags,
+                                nsm_hit* out /*device, left->n * k records*/, unsigned long long* out_count /*device, caller zeroes*/,
+                                uint64_t* stats /*device [4] or NULL*/, void* stream);
+int nsm_jaccard_raw_top_k_grouped(const nsm_set_table* left, const nsm_set_table* right, const int32_t* right_group,
+                                  double threshold, int32_t k, uint32_t flags,
+                                  nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream);
 
 /* Levels-mode Jaccard: score = sum_{s=1..max(Ll,Lr)} 2^-s * J(level min(s,Ll-1), level min(s,Lr-1))
  * accumulated in double in that order; optional category predicate. */

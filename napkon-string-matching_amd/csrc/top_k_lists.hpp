@@ -114,6 +114,74 @@ struct TopLists {
   }
 };
 
+// Lists that hold at most ONE record per group of right rows: the group's best row so far (its representative), so a
+// full list is k distinct groups.  The group ids of the records sit in a parallel int32 slice (grp[(row0 + g) k + q] is
+// the group of list[(row0 + g) k + q]): a look-up scans that slice, it never gathers group[h.j] again.
+//
+// The floor stays what it is for TopLists -- the worst record of a full list -- and stays exact: it is a representative's
+// score, a group's representative only ever improves, and the list holds k distinct groups, so the final k-th best
+// representative is never below it.  A candidate that would improve its own group's record comes before a record of the
+// list, hence before (or in place of) the worst one: beats() in front of an offer drops nothing that matters.
+struct GroupedTopLists : TopLists {
+  int32_t* grp = nullptr;
+
+  // wave-uniform call, all lanes enabled: (s, i, j) of group gid enters row g's list if it belongs there
+  __device__ void offer(int g, double s, int i, int j, int gid) {
+    if (!beats(g, s, j)) return;
+    const size_t row = static_cast<size_t>(row0 + g) * k;
+    const int n = cnt(g);
+    // is the group in the list, and does the candidate come before its record?  64 group ids per pass
+    int pos = -1;
+    bool improves = false;
+    for (int base = 0; base < n; base += kWave) {
+      const int q = base + lane;
+      const bool same = q < n && grp[row + q] == gid;
+      bool better = false;
+      if (same) {
+        const nsm_hit cur = list[row + q];
+        better = s > cur.score || (s == cur.score && j < cur.j);
+      }
+      const unsigned long long found = __ballot(same);
+      if (found) {
+        pos = base + __builtin_ctzll(found);
+        improves = __ballot(better) != 0ull;
+        break;
+      }
+    }
+    if (pos >= 0 && !improves) return;
+    const bool was_full = n == k;
+    const bool append = pos < 0 && !was_full;
+    const int worst_pos = __builtin_amdgcn_readlane(wp_v, g);
+    // present: its own slot; absent: the next free slot, or the worst record's
+    const int slot = pos >= 0 ? pos : (was_full ? worst_pos : n);
+    if (lane == 0) {
+      nsm_hit h;
+      h.score = s;
+      h.i = i;
+      h.j = j;
+      list[row + slot] = h;
+      grp[row + slot] = gid;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    ++changes;
+    if (append && lane == g) ++cnt_v;
+    // the worst record is unknown (the list has just filled up) or has just been overwritten
+    if (append ? slot + 1 == k : (was_full && slot == worst_pos)) rescan(g);
+  }
+
+  // lanes with `ok` hold an eligible record (s, j) of group gid for row g: offer them one by one
+  __device__ void offer_lanes(int g, bool ok, double s, int i, int j, int gid) {
+    for (unsigned long long todo = __ballot(ok); todo; todo &= todo - 1ull) {
+      const int leader = __builtin_ctzll(todo);
+      const unsigned long long b = __double_as_longlong(s);
+      const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b), leader));
+      const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), leader));
+      const double s_l = __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+      offer(g, s_l, i, __builtin_amdgcn_readlane(j, leader), __builtin_amdgcn_readlane(gid, leader));
+    }
+  }
+};
+
 // Scratch for the per-row lists, stream-ordered: it is freed behind the kernel on the same stream.
 static int with_lists(int n_left, int k, hipStream_t s, nsm_hit** list) {
   const size_t bytes = static_cast<size_t>(n_left) * static_cast<size_t>(k) * sizeof(nsm_hit);

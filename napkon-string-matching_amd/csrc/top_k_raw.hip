@@ -19,9 +19,15 @@
 //   * survivors get their exact score: the multi-word bit-parallel LCS with the G rows' match masks resident in LDS
 //     (add_chain of indel_wide.hpp), or a merge of the two ascending id rows; the score is the double the RAW grids emit;
 //   * at the end the wave reserves its records in `out` with one atomic and copies its lists there.
+//
+// Grouped variants (GROUPED, nsm_*_raw_top_k_grouped): right row j belongs to group right_group[j] and a list keeps at most
+// one record per group, the group's best row -- terminology/mesh.py:207-220's sort + drop_duplicates(subset="Id") + limit.
+// Everything above is unchanged; the difference is the list object (GroupedTopLists, top_k_lists.hpp).
 #include "indel_score.hpp"
 #include "indel_wide.hpp"
 #include "top_k_lists.hpp"
+
+#include <type_traits>
 
 namespace nsm {
 
@@ -61,20 +67,37 @@ struct ClassWalk {
   int hi, lo;
 };
 
+// The lists of a wave: TopLists, or (GROUPED) the lists that keep one record per group of right rows.
+template <bool GROUPED>
+using TopListsOf = std::conditional_t<GROUPED, GroupedTopLists, TopLists>;
+
+template <bool GROUPED>
+__device__ __forceinline__ TopListsOf<GROUPED> make_lists(nsm_hit* list, int32_t* glist, int k, int row0, int lane) {
+  if constexpr (GROUPED) {
+    GroupedTopLists L{{list, k, row0, lane}};
+    L.grp = glist;
+    return L;
+  } else {
+    return TopLists{list, k, row0, lane};
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ Indel
 struct TopIndelParams {
   int32_t n_left, n_right, k, pm_stride;
   double threshold;
 };
 
-// W 64-bit words per pattern (stride 64 W).  LDS: [G][pm_stride][W] match masks of the group's rows.
-template <int W, bool PRUNE, bool HIST>
+// W 64-bit words per pattern (stride 64 W).  LDS: [G][pm_stride][W] match masks of the group's rows.  GROUPED: rgroup[jo]
+// is the group of the right row with caller id jo and glist the group ids of the lists' records (top_k_lists.hpp), both
+// unused otherwise; the work split, the class walk and every bound are those of the ungrouped query.
+template <int W, bool PRUNE, bool HIST, bool GROUPED>
 __global__ __launch_bounds__(kWave) void indel_top_k_kernel(
     const uint8_t* __restrict__ lcodes, const int32_t* __restrict__ llen, const int32_t* __restrict__ lorig,
     const uint32_t* __restrict__ lhist, const uint8_t* __restrict__ rcodes, const int32_t* __restrict__ rlen_start,
     const int32_t* __restrict__ rorig, const uint32_t* __restrict__ rhist, nsm_hit* __restrict__ list,
     nsm_hit* __restrict__ out, unsigned long long* __restrict__ out_count, unsigned long long* __restrict__ stats,
-    const TopIndelParams p) {
+    const TopIndelParams p, const int32_t* __restrict__ rgroup, int32_t* __restrict__ glist) {
   constexpr int G = kTopG, STRIDE = 64 * W;
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_pm[];
   const int lane = threadIdx.x;
@@ -107,7 +130,7 @@ __global__ __launch_bounds__(kWave) void indel_top_k_kernel(
   }
   __syncthreads();
 
-  TopLists L{list, p.k, row0, lane};
+  TopListsOf<GROUPED> L = make_lists<GROUPED>(list, glist, p.k, row0, lane);
   unsigned long long st[4] = {0, 0, 0, 0};
 
   // upper bound of a pair of row g with a right row of length lb: all of the shorter string in common
@@ -204,7 +227,10 @@ __global__ __launch_bounds__(kWave) void indel_top_k_kernel(
         }
         st[3] += mine ? 1u : 0u;
         const double sc = indel_score(a, lb, lcs);
-        L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
+        if constexpr (GROUPED)
+          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo, rgroup[jo]);
+        else
+          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
       }
     }
   }
@@ -217,13 +243,14 @@ struct TopJacParams {
   double threshold;
 };
 
-template <int W, bool PRUNE>
+template <int W, bool PRUNE, bool GROUPED>  // (GROUPED, rgroup, glist: as in the Indel kernel)
 __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
     const int32_t* __restrict__ lids, const int32_t* __restrict__ lcnt, const uint64_t* __restrict__ lsig,
     const uint64_t* __restrict__ lsig2, const int32_t* __restrict__ lorig, const int32_t* __restrict__ rids,
     const int32_t* __restrict__ rsize_start, const uint64_t* __restrict__ rsig, const uint64_t* __restrict__ rsig2,
     const int32_t* __restrict__ rorig, nsm_hit* __restrict__ list, nsm_hit* __restrict__ out,
-    unsigned long long* __restrict__ out_count, unsigned long long* __restrict__ stats, const TopJacParams p) {
+    unsigned long long* __restrict__ out_count, unsigned long long* __restrict__ stats, const TopJacParams p,
+    const int32_t* __restrict__ rgroup, int32_t* __restrict__ glist) {
   constexpr int G = kTopG;
   constexpr uint64_t kCollBits = ~((1ull << 58) - 1);  // the top 6 bits of a signature word hold c (unary)
   __shared__ int32_t s_ids[G * W];
@@ -246,7 +273,7 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
   for (int e = lane; e < G * W; e += kWave) s_ids[e] = (e / W < rows) ? lids[static_cast<size_t>(row0) * W + e] : -1;
   __syncthreads();
 
-  TopLists L{list, p.k, row0, lane};
+  TopListsOf<GROUPED> L = make_lists<GROUPED>(list, glist, p.k, row0, lane);
   unsigned long long st[4] = {0, 0, 0, 0};
 
   // upper bound with a set of b ids: min / max -- 0 when exactly one side is empty; two empty sets never score
@@ -337,7 +364,10 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
         }
         st[3] += mine ? 1u : 0u;
         const double sc = mine ? topk_jaccard_score(a, b, inter) : 0.0;
-        L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
+        if constexpr (GROUPED)
+          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo, rgroup[jo]);
+        else
+          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
       }
     }
   }
@@ -345,73 +375,95 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch
+// rgroup == nullptr: the ungrouped kernels (rgroup and glist unused); else the grouped ones
 template <int W, bool PRUNE, bool HIST>
-static int launch_indel_top_k(const nsm_str_table* l, const nsm_str_table* r, const TopIndelParams& p, nsm_hit* list,
-                              nsm_hit* out, unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
+static int launch_indel_top_k(const nsm_str_table* l, const nsm_str_table* r, const int32_t* rgroup, const TopIndelParams& p,
+                              nsm_hit* list, int32_t* glist, nsm_hit* out, unsigned long long* out_count,
+                              unsigned long long* stats, hipStream_t s) {
   const size_t lds = static_cast<size_t>(kTopG) * p.pm_stride * W * 8;
-  auto kern = indel_top_k_kernel<W, PRUNE, HIST>;
+  const void* kern = rgroup ? reinterpret_cast<const void*>(indel_top_k_kernel<W, PRUNE, HIST, true>)
+                            : reinterpret_cast<const void*>(indel_top_k_kernel<W, PRUNE, HIST, false>);
   if (lds > 64 * 1024) {
-    const int st = hip_status(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  static_cast<int>(lds)),
+    const int st = hip_status(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)),
                               "indel_top_k_kernel LDS");
     if (st) return st;
   }
   const dim3 grid((p.n_left + kTopG - 1) / kTopG);
-  hipLaunchKernelGGL(kern, grid, dim3(kWave), lds, s, l->codes, l->len, l->orig, reinterpret_cast<const uint32_t*>(l->hist),
-                     r->codes, r->len_start, r->orig, reinterpret_cast<const uint32_t*>(r->hist), list, out, out_count,
-                     stats, p);
+  const uint32_t* lh = reinterpret_cast<const uint32_t*>(l->hist);
+  const uint32_t* rh = reinterpret_cast<const uint32_t*>(r->hist);
+  if (rgroup)
+    hipLaunchKernelGGL((indel_top_k_kernel<W, PRUNE, HIST, true>), grid, dim3(kWave), lds, s, l->codes, l->len, l->orig, lh,
+                       r->codes, r->len_start, r->orig, rh, list, out, out_count, stats, p, rgroup, glist);
+  else
+    hipLaunchKernelGGL((indel_top_k_kernel<W, PRUNE, HIST, false>), grid, dim3(kWave), lds, s, l->codes, l->len, l->orig, lh,
+                       r->codes, r->len_start, r->orig, rh, list, out, out_count, stats, p, rgroup, glist);
   return hip_status(hipGetLastError(), "indel_top_k_kernel launch");
 }
 
 template <int W>
-static int dispatch_indel(bool prune, bool hist, const nsm_str_table* l, const nsm_str_table* r, const TopIndelParams& p,
-                          nsm_hit* list, nsm_hit* out, unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
-  if (!prune) return launch_indel_top_k<W, false, false>(l, r, p, list, out, out_count, stats, s);
-  if (hist) return launch_indel_top_k<W, true, true>(l, r, p, list, out, out_count, stats, s);
-  return launch_indel_top_k<W, true, false>(l, r, p, list, out, out_count, stats, s);
+static int dispatch_indel(bool prune, bool hist, const nsm_str_table* l, const nsm_str_table* r, const int32_t* rgroup,
+                          const TopIndelParams& p, nsm_hit* list, int32_t* glist, nsm_hit* out, unsigned long long* out_count,
+                          unsigned long long* stats, hipStream_t s) {
+  if (!prune) return launch_indel_top_k<W, false, false>(l, r, rgroup, p, list, glist, out, out_count, stats, s);
+  if (hist) return launch_indel_top_k<W, true, true>(l, r, rgroup, p, list, glist, out, out_count, stats, s);
+  return launch_indel_top_k<W, true, false>(l, r, rgroup, p, list, glist, out, out_count, stats, s);
 }
 
 template <int W, bool PRUNE>
-static int launch_jaccard_top_k(const nsm_set_table* l, const nsm_set_table* r, const TopJacParams& p, nsm_hit* list,
-                                nsm_hit* out, unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
+static int launch_jaccard_top_k(const nsm_set_table* l, const nsm_set_table* r, const int32_t* rgroup, const TopJacParams& p,
+                                nsm_hit* list, int32_t* glist, nsm_hit* out, unsigned long long* out_count,
+                                unsigned long long* stats, hipStream_t s) {
   const dim3 grid((p.n_left + kTopG - 1) / kTopG);
-  hipLaunchKernelGGL((jaccard_top_k_kernel<W, PRUNE>), grid, dim3(kWave), 0, s, l->ids, l->cnt, l->sig, l->sig2, l->orig,
-                     r->ids, r->size_start, r->sig, r->sig2, r->orig, list, out, out_count, stats, p);
+  if (rgroup)
+    hipLaunchKernelGGL((jaccard_top_k_kernel<W, PRUNE, true>), grid, dim3(kWave), 0, s, l->ids, l->cnt, l->sig, l->sig2, l->orig,
+                       r->ids, r->size_start, r->sig, r->sig2, r->orig, list, out, out_count, stats, p, rgroup, glist);
+  else
+    hipLaunchKernelGGL((jaccard_top_k_kernel<W, PRUNE, false>), grid, dim3(kWave), 0, s, l->ids, l->cnt, l->sig, l->sig2, l->orig,
+                       r->ids, r->size_start, r->sig, r->sig2, r->orig, list, out, out_count, stats, p, rgroup, glist);
   return hip_status(hipGetLastError(), "jaccard_top_k_kernel launch");
 }
 
-}  // namespace nsm
+// Scratch for the group ids of the lists' records (grouped queries only), stream-ordered like the lists.
+static int with_groups(int n_left, int k, hipStream_t s, int32_t** glist) {
+  const size_t bytes = static_cast<size_t>(n_left) * static_cast<size_t>(k) * sizeof(int32_t);
+  return hip_status(hipMallocAsync(reinterpret_cast<void**>(glist), bytes ? bytes : 1, s), "top_k group scratch");
+}
 
-extern "C" int nsm_indel_raw_top_k(const nsm_str_table* left, const nsm_str_table* right, double threshold, int32_t k,
-                                   uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream) {
-  using namespace nsm;
+// Both Indel entries: `grouped` asks for right_group (one record per group, top_k_lists.hpp).
+static int indel_raw_top_k(const char* who, bool grouped, const nsm_str_table* left, const nsm_str_table* right,
+                           const int32_t* right_group, double threshold, int32_t k, uint32_t flags, nsm_hit* out,
+                           unsigned long long* out_count, uint64_t* stats, void* stream) {
   if (!left || !right || !out_count || !out) {
-    set_error("nsm_indel_raw_top_k: null argument");
+    set_error("%s: null argument", who);
     return NSM_E_BADARG;
   }
   int keff = 0;
-  if (k < 1) return clamp_k("nsm_indel_raw_top_k", k, right->n, &keff);
+  if (k < 1) return clamp_k(who, k, right->n, &keff);
+  if (grouped && !right_group) {
+    set_error("%s: right_group is null", who);
+    return NSM_E_BADARG;
+  }
   if (left->stride != right->stride) {
-    set_error("nsm_indel_raw_top_k: strides differ (%d, %d)", left->stride, right->stride);
+    set_error("%s: strides differ (%d, %d)", who, left->stride, right->stride);
     return NSM_E_BADARG;
   }
   if (left->stride != 64 && left->stride != 128 && left->stride != 256 && left->stride != 512) {
-    set_error("nsm_indel_raw_top_k: stride %d unsupported (64, 128, 256 or 512 code units)", left->stride);
+    set_error("%s: stride %d unsupported (64, 128, 256 or 512 code units)", who, left->stride);
     return NSM_E_UNSUPPORTED;
   }
   if (left->alphabet != right->alphabet || left->alphabet < 1 || left->alphabet > 255) {
-    set_error("nsm_indel_raw_top_k: alphabets differ or exceed 255 (%d, %d)", left->alphabet, right->alphabet);
+    set_error("%s: alphabets differ or exceed 255 (%d, %d)", who, left->alphabet, right->alphabet);
     return NSM_E_BADARG;
   }
   if (left->n < 0 || right->n < 0) {
-    set_error("nsm_indel_raw_top_k: negative row count");
+    set_error("%s: negative row count", who);
     return NSM_E_BADARG;
   }
   if (!left->codes || !left->len || !left->orig || !right->codes || !right->len_start || !right->orig) {
-    set_error("nsm_indel_raw_top_k: table has a null column (the right table needs len_start)");
+    set_error("%s: table has a null column (the right table needs len_start)", who);
     return NSM_E_BADARG;
   }
-  if (int st = clamp_k("nsm_indel_raw_top_k", k, right->n, &keff)) return st;
+  if (int st = clamp_k(who, k, right->n, &keff)) return st;
   if (left->n == 0 || right->n == 0) return 0;
   TopIndelParams p;
   p.n_left = left->n;
@@ -425,41 +477,56 @@ extern "C" int nsm_indel_raw_top_k(const nsm_str_table* left, const nsm_str_tabl
   const bool hist = prune && left->hist && right->hist && left->stride <= 128;
   nsm_hit* list = nullptr;
   if (int st = with_lists(left->n, keff, s, &list)) return st;
+  int32_t* glist = nullptr;
+  if (grouped) {
+    if (int st = with_groups(left->n, keff, s, &glist)) {
+      (void)hipFreeAsync(list, s);
+      return st;
+    }
+  }
   unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  const int32_t* rg = grouped ? right_group : nullptr;
   int st = 0;
   switch (left->stride) {
-    case 64: st = dispatch_indel<1>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
-    case 128: st = dispatch_indel<2>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
-    case 256: st = dispatch_indel<4>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
-    default: st = dispatch_indel<8>(prune, hist, left, right, p, list, out, out_count, sp, s); break;
+    case 64: st = dispatch_indel<1>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
+    case 128: st = dispatch_indel<2>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
+    case 256: st = dispatch_indel<4>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
+    default: st = dispatch_indel<8>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
   }
-  const int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
+  int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
+  if (grouped) {
+    const int gst = hip_status(hipFreeAsync(glist, s), "top_k group scratch");
+    fst = fst ? fst : gst;
+  }
   return st ? st : fst;
 }
 
-extern "C" int nsm_jaccard_raw_top_k(const nsm_set_table* left, const nsm_set_table* right, double threshold, int32_t k,
-                                     uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats,
-                                     void* stream) {
-  using namespace nsm;
+static int jaccard_raw_top_k(const char* who, bool grouped, const nsm_set_table* left, const nsm_set_table* right,
+                             const int32_t* right_group, double threshold, int32_t k, uint32_t flags, nsm_hit* out,
+                             unsigned long long* out_count, uint64_t* stats, void* stream) {
   if (!left || !right || !out_count || !out) {
-    set_error("nsm_jaccard_raw_top_k: null argument");
+    set_error("%s: null argument", who);
     return NSM_E_BADARG;
   }
   int keff = 0;
-  if (k < 1) return clamp_k("nsm_jaccard_raw_top_k", k, right->n, &keff);
+  if (k < 1) return clamp_k(who, k, right->n, &keff);
+  if (grouped && !right_group) {
+    set_error("%s: right_group is null", who);
+    return NSM_E_BADARG;
+  }
   if (left->width != right->width || (left->width != 16 && left->width != 32 && left->width != 64)) {
-    set_error("nsm_jaccard_raw_top_k: width %d/%d unsupported (both sides 16, 32 or 64)", left->width, right->width);
+    set_error("%s: width %d/%d unsupported (both sides 16, 32 or 64)", who, left->width, right->width);
     return NSM_E_BADARG;
   }
   if (left->n < 0 || right->n < 0) {
-    set_error("nsm_jaccard_raw_top_k: negative row count");
+    set_error("%s: negative row count", who);
     return NSM_E_BADARG;
   }
   if (!left->ids || !left->cnt || !left->orig || !right->ids || !right->size_start || !right->orig) {
-    set_error("nsm_jaccard_raw_top_k: table has a null column (the right table needs size_start)");
+    set_error("%s: table has a null column (the right table needs size_start)", who);
     return NSM_E_BADARG;
   }
-  if (int st = clamp_k("nsm_jaccard_raw_top_k", k, right->n, &keff)) return st;
+  if (int st = clamp_k(who, k, right->n, &keff)) return st;
   if (left->n == 0 || right->n == 0) return 0;
   TopJacParams p;
   p.n_left = left->n;
@@ -470,16 +537,57 @@ extern "C" int nsm_jaccard_raw_top_k(const nsm_set_table* left, const nsm_set_ta
   const bool prune = (flags & NSM_FLAG_PRUNE) && left->sig && right->sig;
   nsm_hit* list = nullptr;
   if (int st = with_lists(left->n, keff, s, &list)) return st;
+  int32_t* glist = nullptr;
+  if (grouped) {
+    if (int st = with_groups(left->n, keff, s, &glist)) {
+      (void)hipFreeAsync(list, s);
+      return st;
+    }
+  }
   unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  const int32_t* rg = grouped ? right_group : nullptr;
   int st = 0;
   switch (left->width) {
-    case 16: st = prune ? launch_jaccard_top_k<16, true>(left, right, p, list, out, out_count, sp, s)
-                        : launch_jaccard_top_k<16, false>(left, right, p, list, out, out_count, sp, s); break;
-    case 32: st = prune ? launch_jaccard_top_k<32, true>(left, right, p, list, out, out_count, sp, s)
-                        : launch_jaccard_top_k<32, false>(left, right, p, list, out, out_count, sp, s); break;
-    default: st = prune ? launch_jaccard_top_k<64, true>(left, right, p, list, out, out_count, sp, s)
-                        : launch_jaccard_top_k<64, false>(left, right, p, list, out, out_count, sp, s); break;
+    case 16: st = prune ? launch_jaccard_top_k<16, true>(left, right, rg, p, list, glist, out, out_count, sp, s)
+                        : launch_jaccard_top_k<16, false>(left, right, rg, p, list, glist, out, out_count, sp, s); break;
+    case 32: st = prune ? launch_jaccard_top_k<32, true>(left, right, rg, p, list, glist, out, out_count, sp, s)
+                        : launch_jaccard_top_k<32, false>(left, right, rg, p, list, glist, out, out_count, sp, s); break;
+    default: st = prune ? launch_jaccard_top_k<64, true>(left, right, rg, p, list, glist, out, out_count, sp, s)
+                        : launch_jaccard_top_k<64, false>(left, right, rg, p, list, glist, out, out_count, sp, s); break;
   }
-  const int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
+  int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
+  if (grouped) {
+    const int gst = hip_status(hipFreeAsync(glist, s), "top_k group scratch");
+    fst = fst ? fst : gst;
+  }
   return st ? st : fst;
+}
+
+}  // namespace nsm
+
+extern "C" int nsm_indel_raw_top_k(const nsm_str_table* left, const nsm_str_table* right, double threshold, int32_t k,
+                                   uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream) {
+  return nsm::indel_raw_top_k("nsm_indel_raw_top_k", false, left, right, nullptr, threshold, k, flags, out, out_count, stats,
+                              stream);
+}
+
+extern "C" int nsm_indel_raw_top_k_grouped(const nsm_str_table* left, const nsm_str_table* right, const int32_t* right_group,
+                                           double threshold, int32_t k, uint32_t flags, nsm_hit* out,
+                                           unsigned long long* out_count, uint64_t* stats, void* stream) {
+  return nsm::indel_raw_top_k("nsm_indel_raw_top_k_grouped", true, left, right, right_group, threshold, k, flags, out,
+                              out_count, stats, stream);
+}
+
+extern "C" int nsm_jaccard_raw_top_k(const nsm_set_table* left, const nsm_set_table* right, double threshold, int32_t k,
+                                     uint32_t flags, nsm_hit* out, unsigned long long* out_count, uint64_t* stats,
+                                     void* stream) {
+  return nsm::jaccard_raw_top_k("nsm_jaccard_raw_top_k", false, left, right, nullptr, threshold, k, flags, out, out_count,
+                                stats, stream);
+}
+
+extern "C" int nsm_jaccard_raw_top_k_grouped(const nsm_set_table* left, const nsm_set_table* right, const int32_t* right_group,
+                                             double threshold, int32_t k, uint32_t flags, nsm_hit* out,
+                                             unsigned long long* out_count, uint64_t* stats, void* stream) {
+  return nsm::jaccard_raw_top_k("nsm_jaccard_raw_top_k_grouped", true, left, right, right_group, threshold, k, flags, out,
+                                out_count, stats, stream);
 }

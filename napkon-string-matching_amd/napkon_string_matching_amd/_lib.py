@@ -114,6 +114,8 @@ EXPORTS = (
     "nsm_jaccard_raw_top_k",
     "nsm_indel_levels_top_k",
     "nsm_jaccard_levels_top_k",
+    "nsm_indel_raw_top_k_grouped",
+    "nsm_jaccard_raw_top_k_grouped",
 )
 
 _lib = None
@@ -162,6 +164,9 @@ def load() -> ctypes.CDLL:
                   ctypes.c_void_p]
     lib.nsm_indel_raw_top_k.argtypes = [P(NsmStrTable), P(NsmStrTable)] + top_k_tail
     lib.nsm_jaccard_raw_top_k.argtypes = [P(NsmSetTable), P(NsmSetTable)] + top_k_tail
+    # (right_group in front of the tail)
+    lib.nsm_indel_raw_top_k_grouped.argtypes = [P(NsmStrTable), P(NsmStrTable), ctypes.c_void_p] + top_k_tail
+    lib.nsm_jaccard_raw_top_k_grouped.argtypes = [P(NsmSetTable), P(NsmSetTable), ctypes.c_void_p] + top_k_tail
     # threshold, k, category_mode, flags, banned_start, banned_j, out, out_count, stats, stream
     levels_top_k_tail = [ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]

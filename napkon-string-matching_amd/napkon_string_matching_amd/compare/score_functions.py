@@ -11,7 +11,9 @@ Same names, call convention and error behaviour as the reference's
   ``ComparableData.gen_comparable`` score N x M pairs in one launch;
 * ``plugin.top_k(left_items, right_items, k, threshold)`` keeps the ``k`` best right items of every left item
   (score descending, right index ascending among equals) -- rapidfuzz's ``process.extract(query, choices, scorer,
-  limit, score_cutoff)`` for all queries at once; the output is bounded by N k records whatever the data.
+  limit, score_cutoff)`` for all queries at once; the output is bounded by N k records whatever the data.  With
+  ``groups=`` (one hashable per right item) it keeps the best item of every group and of those the ``k`` best: the
+  ``k`` best distinct candidates when the right side lists a candidate under several spellings.
 
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
@@ -21,6 +23,7 @@ from __future__ import annotations
 import re
 from typing import Iterable, List, Sequence, Union
 
+import numpy as np
 import torch
 
 from .. import grid, tables
@@ -68,6 +71,18 @@ def fuzzy_operand(value: Operand) -> str:
     return default_process(join_sorted(value) if isinstance(value, list) else value)
 
 
+def factorise_groups(groups, n_right: int):
+    """``groups`` of a grouped ``top_k`` (any sequence of hashables, one per right item) as an int32 array of dense ids;
+    ``None`` stays ``None``.  A wrong length is a ``ValueError``, before any device work."""
+    if groups is None:
+        return None
+    groups = list(groups)
+    if len(groups) != n_right:
+        raise ValueError(f"{len(groups)} groups for {n_right} right items")
+    ids = {}
+    return np.fromiter((ids.setdefault(g, len(ids)) for g in groups), dtype=np.int32, count=len(groups))
+
+
 def set_operand(value: Operand) -> Iterable[str]:
     """What ``intersection_vs_union`` turns one operand into (score_functions.py:10-11)."""
     return value if isinstance(value, list) else value.split()
@@ -110,17 +125,22 @@ class _IntersectionVsUnion:
 
     @staticmethod
     def top_k(left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
-              prune: bool = True) -> grid.Hits:
+              prune: bool = True, groups=None) -> grid.Hits:
         """Per left item the first ``k`` records of ``raw_grid(left_items, right_items, threshold)`` (score descending,
-        right index ascending), all of them in canonical order."""
+        right index ascending), all of them in canonical order.  ``groups`` (hashables, one per right item): right items
+        of one group are spellings of one candidate -- per left item only the best record of every group is kept, and of
+        those the first ``k``: the ``k`` best DISTINCT candidates."""
         from .. import wide
 
         k = grid.check_k(k)
+        gids = factorise_groups(groups, len(right_items))
         dev = device or _device()
         l_rows = [list(set_operand(v)) for v in left_items]
         r_rows = [list(set_operand(v)) for v in right_items]
         if any(not r for r in l_rows) and any(not r for r in r_rows):
             raise ZeroDivisionError("division by zero")  # (:13)
+
+        sub = lambda ri: None if gids is None else gids[np.asarray(ri, dtype=np.int64)]
 
         def fast(li, ri):
             vocab = tables.Vocabulary()
@@ -128,16 +148,18 @@ class _IntersectionVsUnion:
             width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
             lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
             rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
-            return grid.jaccard_raw_top_k(lt, rt, k, threshold, prune=prune)
+            return grid.jaccard_raw_top_k(lt, rt, k, threshold, prune=prune, groups=sub(ri))
 
         split = wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows])
         if split is None:
             return fast(range(len(l_rows)), range(len(r_rows)))
         # items of more than 64 distinct tokens: the general kernel at `threshold`; the parts are disjoint in j for every
-        # i, so the union of their per-row selections holds the answer
+        # i, so the union of their per-row selections holds the answer (grouped: a representative among the first k of
+        # the whole row is the best of its group in its own part, and fewer than k groups beat it there)
         general = lambda li, ri: grid.select_top_k(
-            wide.jaccard_any_grid([[l_rows[k_]] for k_ in li], [[r_rows[k_]] for k_ in ri], threshold, raw=True, device=dev), k)
-        return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)
+            wide.jaccard_any_grid([[l_rows[k_]] for k_ in li], [[r_rows[k_]] for k_ in ri], threshold, raw=True, device=dev), k,
+            sub(ri))
+        return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
 
 
 class _FuzzyMatch:
@@ -170,27 +192,32 @@ class _FuzzyMatch:
 
     @staticmethod
     def top_k(left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
-              prune: bool = True) -> grid.Hits:
+              prune: bool = True, groups=None) -> grid.Hits:
         """Per left item the first ``k`` records of ``raw_grid(left_items, right_items, threshold)`` (score descending,
-        right index ascending), all of them in canonical order."""
+        right index ascending), all of them in canonical order.  ``groups`` (hashables, one per right item): right items
+        of one group are spellings of one candidate -- per left item only the best record of every group is kept, and of
+        those the first ``k``: the ``k`` best DISTINCT candidates (``MeshProvider.get_matches``' one row per Id)."""
         from .. import wide
 
         k = grid.check_k(k)
+        gids = factorise_groups(groups, len(right_items))
         dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        sub = lambda ri: None if gids is None else gids[np.asarray(ri, dtype=np.int64)]
 
         def fast(li, ri):
             lt, rt = tables.encode_strings([l_ops[k_] for k_ in li], [r_ops[k_] for k_ in ri], dev)
-            return grid.indel_raw_top_k(lt, rt, k, threshold, prune=prune)
+            return grid.indel_raw_top_k(lt, rt, k, threshold, prune=prune, groups=sub(ri))
 
         split = wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops])
         if split is None:
             return fast(range(len(l_ops)), range(len(r_ops)))
         # strings beyond the fast kernels: the general kernel at `threshold`; the parts are disjoint in j for every i, so
-        # the union of their per-row selections holds the answer
+        # the union of their per-row selections holds the answer (grouped: as for intersection_vs_union.top_k)
         general = lambda li, ri: grid.select_top_k(
-            wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], threshold, raw=True, device=dev), k)
-        return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)
+            wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], threshold, raw=True, device=dev), k,
+            sub(ri))
+        return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
 
 
 intersection_vs_union = _IntersectionVsUnion()

@@ -189,18 +189,53 @@ def check_k(k) -> int:
     return int(k)
 
 
-def select_top_k(hits: Hits, k: int) -> Hits:
+def select_top_k(hits: Hits, k: int, groups=None) -> Hits:
     """The first ``k`` records of every left item (score descending, j ascending), returned in canonical order: the
-    definition of a top-k query in terms of a threshold grid's hits (also how per-part results are merged)."""
+    definition of a top-k query in terms of a threshold grid's hits (also how per-part results are merged).
+    ``groups`` (one id per right index, any integer array): first only the best record of every (left item, group) is
+    kept -- the group's representative, first in (score descending, j ascending) -- then the ``k`` best representatives
+    per left item: the grouped query of ``nsm_*_raw_top_k_grouped``."""
     if len(hits) == 0:
         return hits
     by_row = np.lexsort((hits.j, -hits.score, hits.i))
+    if groups is not None:
+        # ordered by (i, group, score descending, j): the first record of every (i, group) run is the representative
+        g = np.asarray(groups)[hits.j]
+        by_group = np.lexsort((hits.j, -hits.score, g, hits.i))
+        gi, gg = hits.i[by_group], g[by_group]
+        reps = by_group[np.r_[True, (gi[1:] != gi[:-1]) | (gg[1:] != gg[:-1])]]
+        by_row = reps[np.lexsort((hits.j[reps], -hits.score[reps], hits.i[reps]))]
     i_sorted = hits.i[by_row]
     start = np.r_[0, np.flatnonzero(i_sorted[1:] != i_sorted[:-1]) + 1]
     rank = np.arange(len(by_row)) - np.repeat(start, np.diff(np.r_[start, len(by_row)]))
     keep = by_row[rank < k]
     order = keep[np.lexsort((hits.j[keep], hits.i[keep], -hits.score[keep]))]
     return Hits(hits.score[order], hits.i[order], hits.j[order])
+
+
+def _device_groups(groups, n_right: int, orig: torch.Tensor, device, what: str) -> torch.Tensor:
+    """``groups`` of a grouped top-k query as the int32 device column the C entries read: one id per right caller index.
+    The length is checked before any device work (``ValueError``); the column must also cover every caller id of the table."""
+    if isinstance(groups, torch.Tensor):
+        if groups.dim() != 1 or groups.dtype != torch.int32:
+            raise ValueError(f"{what}: groups must be a one-dimensional int32 tensor")
+        n = int(groups.shape[0])
+    else:
+        groups = np.ascontiguousarray(groups)
+        if groups.ndim != 1 or not np.issubdtype(groups.dtype, np.integer):
+            raise ValueError(f"{what}: groups must be a one-dimensional integer array")
+        n = int(groups.shape[0])
+    if n != n_right:
+        raise ValueError(f"{what}: {n} group ids for {n_right} right items")
+    dev = _require_gpu(device)
+    if not isinstance(groups, torch.Tensor):
+        if groups.size and (groups.min() < -(1 << 31) or groups.max() >= (1 << 31)):
+            raise ValueError(f"{what}: group ids must fit int32")
+        groups = torch.from_numpy(groups.astype(np.int32))
+    groups = groups.to(dev).contiguous()
+    if n_right and int(orig.max().item()) >= n:  # (tables built with caller ids of their own)
+        raise ValueError(f"{what}: the right table reports ids up to {int(orig.max().item())}, beyond the {n} group ids")
+    return groups
 
 
 def _top_k(launch: Callable, n_left: int, n_right: int, k: int, device, what: str, stats: Optional[list] = None,
@@ -224,32 +259,53 @@ def _top_k(launch: Callable, n_left: int, n_right: int, k: int, device, what: st
 
 
 def indel_raw_top_k(left: StrTable, right: StrTable, k: int, threshold: float, prune: bool = True,
-                    stats: Optional[list] = None) -> Hits:
+                    stats: Optional[list] = None, groups=None) -> Hits:
     """For every left item the first ``min(k, #hits of its row)`` records of ``indel_raw_grid(left, right, threshold)``
     in the order (score descending, j ascending), all of them in canonical order.  ``stats``: a list that receives
-    [pairs in visited classes, pairs past the length bound, pairs past the histogram bound, exact LCS evaluations]."""
+    [pairs in visited classes, pairs past the length bound, pairs past the histogram bound, exact LCS evaluations].
+    ``groups``: an int32 device tensor or integer array with one group id per right caller index -- then a left item gets
+    the best record of every group (its representative) and of those the first ``k``: ``select_top_k(hits, k, groups)`` of
+    the threshold grid's hits, computed by ``nsm_indel_raw_top_k_grouped`` with lists of one record per group."""
     k = check_k(k)
+    flags = _lib.FLAG_PRUNE if prune else 0
+    if groups is not None:
+        what = "nsm_indel_raw_top_k_grouped"
+        gcol = _device_groups(groups, right.n, right.orig, left.codes.device, what)
+        lib = _lib.load()
+        ls, rs = left.struct(), right.struct()
+        return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_indel_raw_top_k_grouped(
+            ls, rs, gcol.data_ptr(), float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
+            left.n, right.n, k, left.codes.device, what, stats)
     lib = _lib.load()
     ls, rs = left.struct(), right.struct()
-    flags = _lib.FLAG_PRUNE if prune else 0
     return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_indel_raw_top_k(
         ls, rs, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
         left.n, right.n, k, left.codes.device, "nsm_indel_raw_top_k", stats)
 
 
 def jaccard_raw_top_k(left: SetTable, right: SetTable, k: int, threshold: float, prune: bool = True,
-                      stats: Optional[list] = None) -> Hits:
+                      stats: Optional[list] = None, groups=None) -> Hits:
     """``intersection_vs_union`` counterpart of ``indel_raw_top_k``; stats[2] counts the pairs past the signature bound,
-    stats[3] the exact merges."""
+    stats[3] the exact merges.  ``groups`` as there (``nsm_jaccard_raw_top_k_grouped``)."""
     k = check_k(k)
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    if groups is not None and len(groups) != right.n:
+        raise ValueError(f"nsm_jaccard_raw_top_k_grouped: {len(groups)} group ids for {right.n} right items")
     if left.has_empty and right.has_empty:
         raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
-    lib = _lib.load()
-    ls, rs = left.struct(), right.struct()
     flags = _lib.FLAG_PRUNE if prune else 0
     id_limit = max(left.id_limit, right.id_limit) if left.id_limit and right.id_limit else 0
+    if groups is not None:
+        what = "nsm_jaccard_raw_top_k_grouped"
+        gcol = _device_groups(groups, right.n, right.orig, left.ids.device, what)
+        lib = _lib.load()
+        ls, rs = left.struct(), right.struct()
+        return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_jaccard_raw_top_k_grouped(
+            ls, rs, gcol.data_ptr(), float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
+            left.n, right.n, k, left.ids.device, what, stats, id_limit)
+    lib = _lib.load()
+    ls, rs = left.struct(), right.struct()
     return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_jaccard_raw_top_k(
         ls, rs, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
         left.n, right.n, k, left.ids.device, "nsm_jaccard_raw_top_k", stats, id_limit)

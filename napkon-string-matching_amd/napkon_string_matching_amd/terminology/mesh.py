@@ -53,27 +53,31 @@ class MeshProvider:
     def get_matches_batch(self, terms: Sequence[Sequence[str]], score_threshold: float = 0.1,
                           limit: Optional[int] = None) -> List[List[Match]]:
         """``get_matches`` of every term in one grid.  With ``limit`` each list is the unlimited one cut after ``limit``
-        entries, from a top-k query instead of the threshold grid: the output is bounded by ``limit`` times the most
-        synonym rows of one Id per term, whatever the threshold (the first ``limit`` distinct Ids of a term always lie
-        among its first ``limit * s`` rows when no Id has more than ``s`` rows).  Where ``limit * s`` exceeds the 4096 records
-        the top-k kernels keep per row (``grid.TOP_K_MAX``), the threshold grid is cut instead: same lists, unbounded output."""
+        entries, from ONE grouped top-k query (``fuzzy_match.top_k(..., groups=Ids)``): the kernel's lists keep one row per
+        Id -- the Id's best synonym row, what the reference's sort + ``drop_duplicates(subset="Id")`` keeps -- so the output
+        is at most ``limit`` records per term whatever the threshold and however many synonym rows one Id has, and no
+        duplicate is dropped on the host.  Only where ``min(limit, number of distinct Ids)`` exceeds the 4096 records the
+        top-k kernels keep per row (``grid.TOP_K_MAX``) is the threshold grid cut instead: same lists, unbounded output.
+        ``limit=None`` is the threshold grid by definition."""
         syn = self.synonyms
         ids = list(syn[TERMINOLOGY_COLUMN_ID])
         syn_terms = list(syn[TERMINOLOGY_COLUMN_TERM])
         joined = [" ".join(term) for term in terms]  # mesh.py:207
-        if limit is None:
-            hits = score_functions.fuzzy_match.raw_grid(joined, syn_terms, score_threshold)
-        else:
-            limit = check_k(limit)
-            rows_per_id = int(syn[TERMINOLOGY_COLUMN_ID].value_counts().max()) if len(syn) else 1
-            if min(limit * rows_per_id, len(syn_terms)) > TOP_K_MAX:
-                # (beyond what the top-k kernels keep per row: the threshold grid, cut below -- the same lists)
-                hits = score_functions.fuzzy_match.raw_grid(joined, syn_terms, score_threshold)
-            else:
-                hits = score_functions.fuzzy_match.top_k(joined, syn_terms, limit * rows_per_id, score_threshold)
         out: List[List[Match]] = [[] for _ in terms]
-        # hits arrive ordered by (score desc, item, synonym row): per item that is already
-        # "score descending, table order among equals"
+        if limit is not None:
+            limit = check_k(limit)
+            gids = score_functions.factorise_groups(ids, len(ids))
+            distinct = int(gids.max()) + 1 if len(gids) else 0
+            if min(limit, distinct) <= TOP_K_MAX:
+                # one record per (term, Id), already the best row of the Id, ordered (score desc, term, synonym row)
+                hits = score_functions.fuzzy_match.top_k(joined, syn_terms, min(limit, max(distinct, 1)), score_threshold,
+                                                         groups=gids)
+                for score, i, j in zip(hits.score.tolist(), hits.i.tolist(), hits.j.tolist()):
+                    out[i].append((ids[j], syn_terms[j], score))
+                return out
+        # the threshold grid: every row >= score_threshold.  Hits arrive ordered by (score desc, item, synonym row): per
+        # item that is already "score descending, table order among equals"
+        hits = score_functions.fuzzy_match.raw_grid(joined, syn_terms, score_threshold)
         seen = [set() for _ in terms]
         for score, i, j in zip(hits.score.tolist(), hits.i.tolist(), hits.j.tolist()):
             if ids[j] in seen[i]:

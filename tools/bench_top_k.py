@@ -2,6 +2,7 @@
 
     python tools/bench_top_k.py [--reps 20] [--c3 200000] [--term 20000] [--c2 50000]
     python tools/bench_top_k.py --levels [--reps 5] [--term 20000] [--c5w 100000]
+    python tools/bench_top_k.py --grouped [--reps 20] [--c3 200000] [--term 20000] [--syn 200000]
 
 Cases: synthetic.c3_corpus() fuzzy at k in {1, 10, 100} x thresholds {0, 0.5, 0.8}; Term-shaped fuzzy operands
 (synthetic.term_cohort, the reference's default configuration) at 0.5; c2_corpus() Jaccard at {0, 0.1, 0.5}, k = 10.
@@ -13,6 +14,14 @@ and, separately, the host-side per-row selection of those hits; else "n/a" and t
 reference's default configuration) at 0.5 and 0 with k in {1, 10}; a c5w-shaped grid (configs[4] on word-like text, list
 categories) at 0.5 and 0, k = 10, for both score functions; and ComparableData.compare(..., top_k=10) end to end against
 compare() on Term-shaped cohorts (one call each, wall clock).
+
+--grouped: the grouped queries (nsm_indel_raw_top_k_grouped).  (a) c3_corpus() at k = 10, thresholds 0.8 / 0.5 / 0 with
+identity groups and with groups j // 8, the ungrouped nsm_indel_raw_top_k beside them in the same process, the three calls
+alternating; per call the median and the min .. max of its per-call times (the ungrouped spread is the yardstick of the
+ratios).  (b) a terminology-shaped case: --term Term-shaped items against --syn synonym-like rows whose Ids have a skewed
+multiplicity (most 1-10 rows, a few several hundred), limit = 10 at threshold 0.1 through the grouped query, next to what
+get_matches_batch(limit=10) needed before it: limit x (most rows of one Id) rows per item, or -- beyond 4096 -- the
+threshold grid, whose records are counted on a sample of the left items.
 """
 import argparse
 import json
@@ -140,6 +149,110 @@ def main_levels(args) -> None:
     print(json.dumps({"bench": "top_k_levels", "device": torch.cuda.get_device_name(0), "reps": args.reps, "cases": rows}))
 
 
+def per_call_ms(fns, reps):
+    """The calls of ``fns`` alternating, ``reps`` rounds after one warm-up round: per call the list of its times (ms)."""
+    for fn in fns:
+        fn()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for q, fn in enumerate(fns):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            fn()
+            stop.record()
+            stop.synchronize()
+            times[q].append(start.elapsed_time(stop))
+    return times
+
+
+def spread(ts):
+    ts = sorted(ts)
+    return {"median_ms": round(ts[len(ts) // 2], 3), "min_ms": round(ts[0], 3), "max_ms": round(ts[-1], 3)}
+
+
+def skewed_ids(rng, m):
+    """Ids of m synonym rows: most Ids have 1-10 rows, about one in 500 has 200-600 (rows of an Id are scattered)."""
+    import numpy as np
+
+    ids, q = [], 0
+    while len(ids) < m:
+        rows = int(rng.integers(200, 601)) if rng.random() < 0.002 else int(rng.integers(1, 11))
+        ids += [q] * rows
+        q += 1
+    ids = np.array(ids[:m], dtype=np.int32)
+    rng.shuffle(ids)
+    return ids
+
+
+def main_grouped(args) -> None:
+    import numpy as np
+
+    dev = torch.device("cuda:0")
+    rows = []
+    (lc, ll), (rc, rl) = synthetic.c3_corpus(args.c3, args.c3)
+    alpha = len(synthetic.STRING_ALPHABET)
+    lt, rt = tables.StrTable.from_codes(lc, ll, alpha, dev), tables.StrTable.from_codes(rc, rl, alpha, dev)
+    identity = torch.arange(args.c3, dtype=torch.int32, device=dev)
+    eights = (torch.arange(args.c3, dtype=torch.int32, device=dev) // 8).contiguous()
+    k = 10
+    for thr in (0.8, 0.5, 0.0):
+        stats = [[], [], []]
+        outs = [None, None, None]
+
+        def call(q, groups):
+            def fn():
+                outs[q] = grid.indel_raw_top_k(lt, rt, k, thr, stats=stats[q], groups=groups)
+            return fn
+
+        times = per_call_ms([call(0, None), call(1, identity), call(2, eights)], args.reps)
+        base = spread(times[0])
+        row = {"case": "c3_fuzzy", "k": k, "threshold": thr, "n": args.c3, "m": args.c3, "ungrouped": base}
+        for q, label in ((1, "grouped_identity"), (2, "grouped_j_div_8")):
+            row[label] = dict(spread(times[q]), ratio_to_ungrouped=round(spread(times[q])["median_ms"] / base["median_ms"], 4),
+                              records=len(outs[q]), stats_per_pair=[v / (args.c3 * args.c3) for v in stats[q]])
+        row["ungrouped"]["records"] = len(outs[0])
+        row["ungrouped"]["stats_per_pair"] = [v / (args.c3 * args.c3) for v in stats[0]]
+        row["identity_same_records"] = outs[0].as_tuples() == outs[1].as_tuples()
+        rows.append(row)
+
+    # (b) terminology-shaped: Term-shaped items against synonym-like rows with skewed Ids
+    rng = np.random.default_rng(42)
+    a = synthetic.term_cohort(args.term, 7)
+    b = synthetic.term_cohort(args.syn, 8, plant_from=a)
+    la = [sf.fuzzy_operand(t) for it in synthetic.term_levels(a) for t in it[:1]]
+    lb = [sf.fuzzy_operand(t) for it in synthetic.term_levels(b) for t in it[:1]]
+    ids = skewed_ids(rng, len(lb))
+    most = int(np.bincount(ids).max())
+    limit, thr = 10, 0.1
+    lt, rt = tables.encode_strings(la, lb, dev)
+    st = []
+    out = [None]
+
+    def grouped():
+        out[0] = grid.indel_raw_top_k(lt, rt, limit, thr, stats=st, groups=ids)
+
+    ts = per_call_ms([grouped], max(3, args.reps // 4))[0]
+    n, m = len(la), len(lb)
+    row = {"case": "terminology", "limit": limit, "threshold": thr, "n": n, "m": m, "distinct_ids": int(ids.max()) + 1,
+           "most_rows_of_one_id": most,
+           "grouped": dict(spread(ts), records=len(out[0]), bound_records=n * limit, stats_per_pair=[v / (n * m) for v in st])}
+    need = limit * most  # rows per item the ungrouped route asks for
+    if min(need, m) <= grid.TOP_K_MAX:
+        st2 = []
+        ts2 = per_call_ms([lambda: out.__setitem__(0, grid.indel_raw_top_k(lt, rt, need, thr, stats=st2))], 3)[0]
+        row["before"] = dict(spread(ts2), route=f"top-k of {need} rows per item + host loop", records=len(out[0]))
+    else:
+        sample = np.sort(rng.choice(n, min(n, 200), replace=False))
+        ls, rs = tables.encode_strings([la[q] for q in sample], lb, dev)
+        hits = grid.indel_raw_grid(ls, rs, thr, capacity=len(sample) * m + 1)
+        per_item = len(hits) / len(sample)
+        row["before"] = {"route": f"{need} rows per item exceed {grid.TOP_K_MAX}: the threshold grid", "time": "n/a",
+                         "sampled_left_items": int(len(sample)), "grid_records_per_item": round(per_item, 1),
+                         "grid_records": int(per_item * n), "grid_bytes": int(per_item * n) * grid.HIT_BYTES}
+    rows.append(row)
+    print(json.dumps({"bench": "top_k_grouped", "device": torch.cuda.get_device_name(0), "reps": args.reps, "cases": rows}))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -148,9 +261,13 @@ def main() -> None:
     ap.add_argument("--c2", type=int, default=50_000)
     ap.add_argument("--levels", action="store_true", help="the levels-mode queries instead (see above)")
     ap.add_argument("--c5w", type=int, default=100_000)
+    ap.add_argument("--grouped", action="store_true", help="the grouped queries instead (see above)")
+    ap.add_argument("--syn", type=int, default=200_000, help="synonym rows of the terminology case (--grouped)")
     args = ap.parse_args()
     if args.levels:
         return main_levels(args)
+    if args.grouped:
+        return main_grouped(args)
     dev = torch.device("cuda:0")
     rows = []
 

@@ -26,7 +26,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=300.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--family", default=None, help="only this kernel family (jaccard_raw, indel_raw, jaccard_levels, indel_levels, indel_split, wide; "
-                    "indel_top_k, jaccard_top_k, indel_levels_top_k, jaccard_levels_top_k, wide_levels_indel and wide_levels_jaccard are "
+                    "indel_top_k, jaccard_top_k, indel_raw_top_k_grouped, jaccard_raw_top_k_grouped, indel_levels_top_k, jaccard_levels_top_k, wide_levels_indel and wide_levels_jaccard are "
                     "drawn only when named here)")
     args = ap.parse_args()
 
@@ -241,6 +241,46 @@ def main():
             want = sorted((h for lst in rows.values() for h in sorted(lst, key=lambda t: (-t[0], t[2]))[:k]),
                           key=lambda t: (-t[0], t[1], t[2]))
             check(got, want, what)
+            continue
+        if family in ("indel_raw_top_k_grouped", "jaccard_raw_top_k_grouped"):
+            # grouped top-k (nsm_*_raw_top_k_grouped) against the definition (tests/support/grouped.py): the oracle's full
+            # grid at the threshold, per left item the best row of every group, of those the first k.  Shapes, alphabets,
+            # empty rows, k, threshold, prune and the group pattern are drawn.  Only through --family.
+            from support.grouped import GROUP_PATTERNS, draw_groups, group_cut
+
+            thr = rng.choice(thresholds + [-1.0, 0.0, -0.5])
+            n, m = rng.randint(1, 160), rng.randint(1, 300)
+            k = rng.choice([1, 1, 2, 3, 5, 10, rng.randint(1, m + 8), m, m + 3])
+            prune = rng.random() < 0.75
+            pattern = rng.choice(GROUP_PATTERNS)
+            groups = draw_groups(rng, m, pattern)
+            if family == "indel_raw_top_k_grouped":
+                hi = rng.choice([4, 8, 30, 64, 64, 100, 128, 200, 256, 400, 512])
+                alphabet = rng.choice(["ab", "abc", "abcdefgh ", "abcdefghijklmnopqrstuvwxyz0123456789 ", "".join(chr(0x100 + c) for c in range(150))])
+                left = [rand_string(rng, alphabet, 0 if rng.random() < 0.2 else 1, hi) for _ in range(n)]
+                right = [rand_string(rng, alphabet, 0 if rng.random() < 0.2 else 1, hi) for _ in range(m)]
+                dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda s_: "".join(s_))  # exact copies: ties
+                lt, rt = tables.encode_strings(left, right, dev)
+                cp = lambda ss: native.csr([[ord(c) for c in s_] for s_ in ss])
+                full = native.indel_raw(cp(left), cp(right), thr, cap=n * m + 1)
+                what = f"{family} hi={hi} |alphabet|={len(alphabet)} thr={thr} k={k} prune={prune} groups={pattern} {n}x{m}"
+                got = grid.indel_raw_top_k(lt, rt, k, thr, prune=prune, groups=groups)
+            else:
+                width = rng.choice([16, 16, 32, 64])
+                kmax = rng.randint(1, width)
+                vocab = rng.choice([kmax + 1, 3 * kmax, 50 * kmax])
+                left_empty = rng.random() < 0.2
+                left = rand_sets(rng, n, kmax, vocab, allow_empty=left_empty)
+                right = rand_sets(rng, m, kmax, vocab, allow_empty=rng.random() < 0.2 and not left_empty)
+                mutate = (lambda r: list(r)) if not any(not r for r in left) else (lambda r: list(r) or [0])
+                dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), mutate)
+                pad = lambda rr: np.array([r + [-1] * (width - len(r)) for r in rr], dtype=np.int32).reshape(len(rr), width)
+                lt = tables.SetTable.from_padded(pad(left), "left", dev, width=width)
+                rt = tables.SetTable.from_padded(pad(right), "right", dev, width=width)
+                full = native.jaccard_raw(native.csr(left), native.csr(right), thr, cap=n * m + 1)
+                what = f"{family} W={width} kmax={kmax} vocab={vocab} thr={thr} k={k} prune={prune} groups={pattern} {n}x{m}"
+                got = grid.jaccard_raw_top_k(lt, rt, k, thr, prune=prune, groups=groups)
+            check(got, group_cut(full, groups.tolist(), k), what)
             continue
         if family in ("indel_top_k", "jaccard_top_k"):
             # per-item top-k (nsm_*_raw_top_k) against the definition: the oracle's threshold grid, cut per left item after
