@@ -63,7 +63,6 @@ __global__ __launch_bounds__(kBlock) void jaccard_levels_global_kernel(
   const int wave = threadIdx.x >> 6;
   const int first_wave = blockIdx.x * kWavesPerBlock + wave;
   const int n_waves = gridDim.x * kWavesPerBlock;
-  constexpr uint64_t kCollBits = ~((1ull << 58) - 1);
   const int sub = lane >> kSlotShift, slot = lane & (W - 1);
   const bool use_cat = p.cat_mode != NSM_CAT_NONE;
 
@@ -176,10 +175,10 @@ __global__ __launch_bounds__(kBlock) void jaccard_levels_global_kernel(
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const uint32_t la = l[4 * q + e];
-            uint32_t mm = lev_min3u(la ^ r[0], la ^ r[1], 255u);
+            uint32_t mm = min3_u32(la ^ r[0], la ^ r[1], 255u);
 #pragma unroll
             for (int b = 2; b < W; b += 2)
-              if (b < nr_max) mm = lev_min3u(mm, la ^ r[b], la ^ r[b + 1]);  // wave-uniform
+              if (b < nr_max) mm = min3_u32(mm, la ^ r[b], la ^ r[b + 1]);  // wave-uniform
             word |= mm << (8 * e);
             if (mm < 64u && first == W) first = 4 * q + e;
           }

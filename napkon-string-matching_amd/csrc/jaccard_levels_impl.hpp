@@ -51,12 +51,6 @@ struct JacLevScalars {
 template <int W>
 constexpr bool kQuotTable = (W <= 32);
 
-__device__ __forceinline__ uint32_t lev_min3u(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t d;
-  asm("v_min3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-
 template <int W, int NB>
 __device__ __forceinline__ void levels_wave(
     const int32_t* __restrict__ lids, const int32_t* __restrict__ lcnt, const uint64_t* __restrict__ lsig,
@@ -96,9 +90,9 @@ __device__ __forceinline__ void levels_wave(
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const uint32_t la = l[4 * q + e];
-          uint32_t m = lev_min3u(la ^ r[0], la ^ r[1], 255u);
+          uint32_t m = min3_u32(la ^ r[0], la ^ r[1], 255u);
 #pragma unroll
-          for (int b = 2; b < NB; b += 2) m = lev_min3u(m, la ^ r[b], la ^ r[b + 1]);
+          for (int b = 2; b < NB; b += 2) m = min3_u32(m, la ^ r[b], la ^ r[b + 1]);
           word |= m << (8 * e);  // m <= 255: the position of the match, or >= 64
         }
         posw[q] = word;
@@ -283,7 +277,6 @@ __global__ __launch_bounds__(kBlock) void jaccard_levels_kernel(
     r[4 * q + 3] = (v.w << 6) | (4 * q + 3);
   }
   const int nrj = valid ? rcnt[jc] : 0;
-  constexpr uint64_t kCollBits = ~((1ull << 58) - 1);  // top 6 bits: the OTHER side's unary collision count
   const uint64_t sr = valid ? (rsig[jc] | kCollBits) : 0ull;
   const uint32_t* rf = rfilt + static_cast<size_t>(jc) * 8;
   const uint64_t sr1 = valid ? (((static_cast<uint64_t>(rf[6]) << 32) | rf[5]) | kCollBits) : 0ull;

@@ -101,9 +101,9 @@ __global__ __launch_bounds__(kBlock) void jaccard_levels_index_kernel(
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const uint32_t la = l[4 * q + e];
-          uint32_t m = lev_min3u(la ^ r[0], la ^ r[1], 255u);
+          uint32_t m = min3_u32(la ^ r[0], la ^ r[1], 255u);
 #pragma unroll
-          for (int b = 2; b < W; b += 2) m = lev_min3u(m, la ^ r[b], la ^ r[b + 1]);
+          for (int b = 2; b < W; b += 2) m = min3_u32(m, la ^ r[b], la ^ r[b + 1]);
           word |= m << (8 * e);
         }
         posw[q] = word;

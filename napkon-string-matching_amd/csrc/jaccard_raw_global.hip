@@ -76,7 +76,6 @@ __global__ __launch_bounds__(kBlock) void jaccard_raw_global_kernel(
   const int wave = threadIdx.x >> 6;
   const int first_wave = blockIdx.x * kWavesPerBlock + wave;
   const int n_waves = gridDim.x * kWavesPerBlock;
-  constexpr uint64_t kCollBits = ~((1ull << 58) - 1);  // the top 6 bits of a signature word hold cA (unary)
   const int sub = lane >> p.slot_shift;                // row of the batch
   const int slot = lane & ((1 << p.slot_shift) - 1);   // prefix position probed by this lane
 

@@ -69,13 +69,7 @@ __device__ __forceinline__ uint32_t to_vgpr(uint32_t uniform) {
   return v;
 }
 
-// hipcc re-associates nested umin() into v_min_u32 pairs and turns umin(x, 1) into cmp + cndmask;
-// the matrix wants exactly one v_min3_u32 per two id pairs, so it is spelled out.
-__device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t d;
-  asm("v_min3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
+// min3_u32(a, b, 1) with the constant inline: hipcc turns umin(x, 1) into cmp + cndmask
 __device__ __forceinline__ uint32_t min3u_one(uint32_t a, uint32_t b) {
   uint32_t d;
   asm("v_min3_u32 %0, %1, %2, 1" : "=v"(d) : "v"(a), "v"(b));
@@ -97,7 +91,7 @@ __device__ __forceinline__ int nonmatches(const int32_t* __restrict__ lrow, cons
     const uint32_t la = to_vgpr(l[a]);
     uint32_t m = min3u_one(la ^ r[0], la ^ r[1]);
 #pragma unroll
-    for (int b = 2; b < NB; b += 2) m = min3u(m, la ^ r[b], la ^ r[b + 1]);
+    for (int b = 2; b < NB; b += 2) m = min3_u32(m, la ^ r[b], la ^ r[b + 1]);
     nm += m;
   }
   return static_cast<int>(nm);
@@ -283,7 +277,6 @@ __global__ __launch_bounds__(kBlock) NSM_JAC_OCC void jaccard_raw_kernel(
     r[4 * q + 3] = v.w;
   }
   const int nrj = valid ? rcnt[jc] : 0;
-  constexpr uint64_t kCollBits = ~((1ull << 58) - 1);  // the top 6 bits of a signature word hold cA (unary)
   const uint64_t sr = (PRUNE && valid) ? (rsig[jc] | kCollBits) : 0ull;
   const uint64_t sr2 = (PRUNE && valid && rsig2 != nullptr) ? (rsig2[jc] | kCollBits) : 0ull;
   if (rsig2 == nullptr) lsig2 = nullptr;

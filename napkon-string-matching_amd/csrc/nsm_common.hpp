@@ -45,6 +45,29 @@ __device__ __forceinline__ void emit_hit(nsm_hit* __restrict__ hits, unsigned lo
 
 __device__ __forceinline__ int wave_first(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// A 64-bit value of lane `lane` (wave-uniform), as two v_readlane.
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int lane) {
+  const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), lane));
+  const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v >> 32), lane));
+  return (static_cast<unsigned long long>(hi) << 32) | lo;
+}
+
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+  return __longlong_as_double(static_cast<long long>(readlane_u64(__double_as_longlong(v), lane)));
+}
+
+// The top 6 bits of a signature word (nsm_hip.h: sig) hold c in unary, the ids that collided inside the row.  A kernel
+// forces them to one in the OTHER side's word, so that popcount(a & b) = common hash bits + c >= |A n B|.
+constexpr uint64_t kCollBits = ~((1ull << 58) - 1);
+
+// hipcc re-associates nested umin() into v_min_u32 pairs; the equality / position matrices of the Jaccard kernels want
+// exactly one v_min3_u32 per two id pairs, so it is spelled out.
+__device__ __forceinline__ uint32_t min3_u32(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t d;
+  asm("v_min3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+
 // Append the hits of a whole wavefront with ONE atomic on the counter: every lane calls this (all 64 enabled),
 // `hit` says whether the lane has a record.  At low thresholds millions of pairs hit (the reference's default
 // configuration keeps 2.6 % of them at cache_threshold 0.5) and one same-address atomic per record is then what
@@ -58,9 +81,7 @@ __device__ __forceinline__ void emit_hits_wave(nsm_hit* __restrict__ hits, unsig
   const int lane = static_cast<int>(threadIdx.x & (kWave - 1));
   unsigned long long base = 0;
   if (lane == leader) base = atomicAdd(count, static_cast<unsigned long long>(__popcll(who)));
-  const uint32_t lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(base), leader);
-  const uint32_t hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(base >> 32), leader);
-  base = (static_cast<unsigned long long>(hi) << 32) | lo;
+  base = readlane_u64(base, leader);
   if (hit) {
     const unsigned long long pos = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(who >> 32),
                                                                      __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(who), 0u));

@@ -53,12 +53,12 @@ __device__ __forceinline__ bool lev_top_banned(const int32_t* __restrict__ banne
 __device__ __forceinline__ double lev_top_tail(int S) { return 0.5 - __builtin_ldexp(1.0, -S); }
 
 // Offer the lanes' finished pairs to the wave's list (all 64 lanes enabled).
-__device__ __forceinline__ void lev_top_offer(TopLists& L, bool ok, double score, double thr, int io, int jo,
+__device__ __forceinline__ void lev_top_offer(TopLists<false>& L, bool ok, double score, double thr, int io, int jo,
                                               const int32_t* __restrict__ banned_start,
                                               const int32_t* __restrict__ banned_j) {
   ok = ok && score >= thr && L.beats(0, score, jo);
   if (ok && banned_start) ok = !lev_top_banned(banned_start, banned_j, io, jo);
-  L.offer_lanes(0, ok, score, io, jo);
+  L.offer_lanes(0, ok, score, io, jo, 0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ Indel
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(kWave) void indel_levels_top_k_kernel(
   const int lf = lfirst[row];
   const int io = lorig[row];
   const uint64_t catl = use_cat ? lcat[row] : 0ull;
-  TopLists L{list, p.k, row, lane};
+  TopLists<false> L{list, nullptr, p.k, row, lane};
   unsigned long long st[4] = {0, 0, 0, 0};
 
   // the text image starts as code 0 (a real symbol): a lane that never stored a row still reads defined masks
@@ -190,12 +190,6 @@ struct TopLevJacParams {
   double threshold;
 };
 
-__device__ __forceinline__ uint32_t lev_top_min3u(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t d;
-  asm("v_min3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-
 // Upper bound of |A n B| / |A u B| for sets of a and b ids that share at most `inter` (inter <= min(a, b)).
 __device__ __forceinline__ double lev_top_jac(int a, int b, int inter) {
   const int uni = a + b - inter;
@@ -211,7 +205,6 @@ __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
     const uint32_t* __restrict__ rfilt, const int32_t* __restrict__ rorig, const int32_t* __restrict__ banned_start,
     const int32_t* __restrict__ banned_j, nsm_hit* __restrict__ list, nsm_hit* __restrict__ out,
     unsigned long long* __restrict__ out_count, unsigned long long* __restrict__ stats, const TopLevJacParams p) {
-  constexpr uint64_t kCollBits = ~((1ull << 58) - 1);  // the top 6 bits of a signature word hold c (unary)
   __shared__ uint32_t s_ids[W];                        // the left item's ids << 6
   const int lane = threadIdx.x;
   const int row = blockIdx.x;
@@ -232,7 +225,7 @@ __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
     sl = (static_cast<uint64_t>(f[1]) << 32) | f[0];
     sl1 = (static_cast<uint64_t>(f[6]) << 32) | f[5];
   }
-  TopLists L{list, p.k, row, lane};
+  TopLists<false> L{list, nullptr, p.k, row, lane};
   unsigned long long st[4] = {0, 0, 0, 0};
 
   if (ll > 0) {
@@ -288,9 +281,9 @@ __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const uint32_t la = s_ids[4 * q + e];
-            uint32_t mm = lev_top_min3u(la ^ r[0], la ^ r[1], 255u);
+            uint32_t mm = min3_u32(la ^ r[0], la ^ r[1], 255u);
 #pragma unroll
-            for (int b = 2; b < W; b += 2) mm = lev_top_min3u(mm, la ^ r[b], la ^ r[b + 1]);
+            for (int b = 2; b < W; b += 2) mm = min3_u32(mm, la ^ r[b], la ^ r[b + 1]);
             word |= mm << (8 * e);  // mm <= 255: the position of the match, or >= 64
           }
           posw[q] = word;
@@ -330,43 +323,30 @@ __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch
-template <int K, bool PRUNE>
-static int launch_indel_levels_top_k(const nsm_level_items* li, const nsm_str_table* ls, const nsm_level_items* ri,
-                                     const nsm_str_table* rs, const int32_t* bs, const int32_t* bj,
-                                     const TopLevIndelParams& p, nsm_hit* list, nsm_hit* out,
-                                     unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
-  const size_t lds = static_cast<size_t>(p.pm_stride) * kPmWords<K> * 8 + static_cast<size_t>(16 * K) * kWave * 4;
-  hipLaunchKernelGGL((indel_levels_top_k_kernel<K, PRUNE>), dim3(p.n_left), dim3(kWave), lds, s, li->first, li->nlev,
-                     li->orig, li->cat, ls->codes, ls->len, ls->hist, ri->first, ri->nlev, ri->orig, ri->cat, rs->codes,
-                     rs->len, rs->hist, bs, bj, list, out, out_count, stats, p);
-  return hip_status(hipGetLastError(), "indel_levels_top_k_kernel launch");
-}
-
 template <int K>
 static int dispatch_indel_levels(bool prune, const nsm_level_items* li, const nsm_str_table* ls, const nsm_level_items* ri,
                                  const nsm_str_table* rs, const int32_t* bs, const int32_t* bj, const TopLevIndelParams& p,
-                                 nsm_hit* list, nsm_hit* out, unsigned long long* out_count, unsigned long long* stats,
-                                 hipStream_t s) {
-  return prune ? launch_indel_levels_top_k<K, true>(li, ls, ri, rs, bs, bj, p, list, out, out_count, stats, s)
-               : launch_indel_levels_top_k<K, false>(li, ls, ri, rs, bs, bj, p, list, out, out_count, stats, s);
-}
-
-template <int W, bool PRUNE>
-static int launch_jaccard_levels_top_k(const nsm_set_table* l, const nsm_set_table* r, const int32_t* bs, const int32_t* bj,
-                                       const TopLevJacParams& p, nsm_hit* list, nsm_hit* out,
-                                       unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
-  hipLaunchKernelGGL((jaccard_levels_top_k_kernel<W, PRUNE>), dim3(p.n_left), dim3(kWave), 0, s, l->ids, l->cnt, l->nlev,
-                     l->plen, l->cat, l->filt, l->orig, r->ids, r->cnt, r->nlev, r->plen, r->cat, r->filt, r->orig, bs, bj,
-                     list, out, out_count, stats, p);
-  return hip_status(hipGetLastError(), "jaccard_levels_top_k_kernel launch");
+                                 const TopOut& o) {
+  auto launch = [&](auto pruned) {
+    const size_t lds = static_cast<size_t>(p.pm_stride) * kPmWords<K> * 8 + static_cast<size_t>(16 * K) * kWave * 4;
+    hipLaunchKernelGGL((indel_levels_top_k_kernel<K, decltype(pruned)::value>), dim3(p.n_left), dim3(kWave), lds, o.sc.s,
+                       li->first, li->nlev, li->orig, li->cat, ls->codes, ls->len, ls->hist, ri->first, ri->nlev, ri->orig,
+                       ri->cat, rs->codes, rs->len, rs->hist, bs, bj, o.sc.list, o.out, o.out_count, o.stats, p);
+    return hip_status(hipGetLastError(), "indel_levels_top_k_kernel launch");
+  };
+  return prune ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
 template <int W>
 static int dispatch_jaccard_levels(bool prune, const nsm_set_table* l, const nsm_set_table* r, const int32_t* bs,
-                                   const int32_t* bj, const TopLevJacParams& p, nsm_hit* list, nsm_hit* out,
-                                   unsigned long long* out_count, unsigned long long* stats, hipStream_t s) {
-  return prune ? launch_jaccard_levels_top_k<W, true>(l, r, bs, bj, p, list, out, out_count, stats, s)
-               : launch_jaccard_levels_top_k<W, false>(l, r, bs, bj, p, list, out, out_count, stats, s);
+                                   const int32_t* bj, const TopLevJacParams& p, const TopOut& o) {
+  auto launch = [&](auto pruned) {
+    hipLaunchKernelGGL((jaccard_levels_top_k_kernel<W, decltype(pruned)::value>), dim3(p.n_left), dim3(kWave), 0, o.sc.s, l->ids,
+                       l->cnt, l->nlev, l->plen, l->cat, l->filt, l->orig, r->ids, r->cnt, r->nlev, r->plen, r->cat, r->filt,
+                       r->orig, bs, bj, o.sc.list, o.out, o.out_count, o.stats, p);
+    return hip_status(hipGetLastError(), "jaccard_levels_top_k_kernel launch");
+  };
+  return prune ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
 static int check_common(const char* who, int32_t category_mode, bool has_cat, const int32_t* bs, const int32_t* bj) {
@@ -398,21 +378,8 @@ extern "C" int nsm_indel_levels_top_k(const nsm_level_items* left, const nsm_str
     set_error("%s: null argument", who);
     return NSM_E_BADARG;
   }
-  int keff = 0;
-  if (k < 1) return clamp_k(who, k, right->n, &keff);
-  if (left_strings->stride != right_strings->stride) {
-    set_error("%s: strides differ (%d, %d)", who, left_strings->stride, right_strings->stride);
-    return NSM_E_BADARG;
-  }
-  const int stride = left_strings->stride;
-  if (stride != 64 && stride != 128 && stride != 256 && stride != 512) {
-    set_error("%s: stride %d unsupported (64, 128, 256 or 512 code units)", who, stride);
-    return NSM_E_UNSUPPORTED;
-  }
-  if (left_strings->alphabet != right_strings->alphabet || left_strings->alphabet < 1 || left_strings->alphabet > 255) {
-    set_error("%s: alphabets differ or exceed 255 (%d, %d)", who, left_strings->alphabet, right_strings->alphabet);
-    return NSM_E_BADARG;
-  }
+  if (int st = check_k(who, k)) return st;
+  if (int st = check_str_tables(who, left_strings, right_strings)) return st;
   if (left->seg || left->seg_start || right->seg || right->seg_start) {
     set_error("%s: partitioned item tables are not supported (an item must be one row: encode with partition=False)", who);
     return NSM_E_UNSUPPORTED;
@@ -427,6 +394,7 @@ extern "C" int nsm_indel_levels_top_k(const nsm_level_items* left, const nsm_str
     return NSM_E_BADARG;
   }
   if (int st = check_common(who, category_mode, left->cat && right->cat, banned_start, banned_j)) return st;
+  int keff = 0;
   if (int st = clamp_k(who, k, right->n, &keff)) return st;
   if (left->n == 0 || right->n == 0) return 0;
   TopLevIndelParams p;
@@ -437,20 +405,17 @@ extern "C" int nsm_indel_levels_top_k(const nsm_level_items* left, const nsm_str
   p.cat_mode = category_mode;
   p.hist = (left_strings->hist && right_strings->hist) ? 1 : 0;
   p.threshold = threshold;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool prune = (flags & NSM_FLAG_PRUNE) != 0;
-  nsm_hit* list = nullptr;
-  if (int st = with_lists(left->n, keff, s, &list)) return st;
-  unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
+  if (int st = o.sc.alloc(left->n, keff, false)) return st;
   int st = 0;
-  switch (stride) {
-    case 64: st = dispatch_indel_levels<1>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, list, out, out_count, sp, s); break;
-    case 128: st = dispatch_indel_levels<2>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, list, out, out_count, sp, s); break;
-    case 256: st = dispatch_indel_levels<4>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, list, out, out_count, sp, s); break;
-    default: st = dispatch_indel_levels<8>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, list, out, out_count, sp, s); break;
+  switch (left_strings->stride) {
+    case 64: st = dispatch_indel_levels<1>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
+    case 128: st = dispatch_indel_levels<2>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
+    case 256: st = dispatch_indel_levels<4>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
+    default: st = dispatch_indel_levels<8>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
   }
-  const int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
-  return st ? st : fst;
+  return o.sc.release(st);
 }
 
 extern "C" int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set_table* right, double threshold, int32_t k,
@@ -463,12 +428,8 @@ extern "C" int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set
     set_error("%s: null argument", who);
     return NSM_E_BADARG;
   }
-  int keff = 0;
-  if (k < 1) return clamp_k(who, k, right->n, &keff);
-  if (left->width != right->width || (left->width != 16 && left->width != 32 && left->width != 64)) {
-    set_error("%s: width %d/%d unsupported (both sides 16, 32 or 64)", who, left->width, right->width);
-    return NSM_E_BADARG;
-  }
+  if (int st = check_k(who, k)) return st;
+  if (int st = check_set_tables(who, left, right)) return st;
   if (left->seg || left->seg_start || right->seg || right->seg_start) {
     set_error("%s: partitioned tables are not supported (an item must be one row: encode with partition=False)", who);
     return NSM_E_UNSUPPORTED;
@@ -483,6 +444,7 @@ extern "C" int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set
     return NSM_E_BADARG;
   }
   if (int st = check_common(who, category_mode, left->cat && right->cat, banned_start, banned_j)) return st;
+  int keff = 0;
   if (int st = clamp_k(who, k, right->n, &keff)) return st;
   if (left->n == 0 || right->n == 0) return 0;
   TopLevJacParams p;
@@ -493,17 +455,14 @@ extern "C" int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set
   p.lev_stride_r = right->max_levels;
   p.cat_mode = category_mode;
   p.threshold = threshold;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool prune = (flags & NSM_FLAG_PRUNE) != 0;
-  nsm_hit* list = nullptr;
-  if (int st = with_lists(left->n, keff, s, &list)) return st;
-  unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
+  if (int st = o.sc.alloc(left->n, keff, false)) return st;
   int st = 0;
   switch (left->width) {
-    case 16: st = dispatch_jaccard_levels<16>(prune, left, right, banned_start, banned_j, p, list, out, out_count, sp, s); break;
-    case 32: st = dispatch_jaccard_levels<32>(prune, left, right, banned_start, banned_j, p, list, out, out_count, sp, s); break;
-    default: st = dispatch_jaccard_levels<64>(prune, left, right, banned_start, banned_j, p, list, out, out_count, sp, s); break;
+    case 16: st = dispatch_jaccard_levels<16>(prune, left, right, banned_start, banned_j, p, o); break;
+    case 32: st = dispatch_jaccard_levels<32>(prune, left, right, banned_start, banned_j, p, o); break;
+    default: st = dispatch_jaccard_levels<64>(prune, left, right, banned_start, banned_j, p, o); break;
   }
-  const int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
-  return st ? st : fst;
+  return o.sc.release(st);
 }

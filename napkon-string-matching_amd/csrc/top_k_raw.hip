@@ -22,12 +22,10 @@
 //
 // Grouped variants (GROUPED, nsm_*_raw_top_k_grouped): right row j belongs to group right_group[j] and a list keeps at most
 // one record per group, the group's best row -- terminology/mesh.py:207-220's sort + drop_duplicates(subset="Id") + limit.
-// Everything above is unchanged; the difference is the list object (GroupedTopLists, top_k_lists.hpp).
+// Everything above is unchanged; the difference is the list object (TopLists<true>, top_k_lists.hpp).
 #include "indel_score.hpp"
 #include "indel_wide.hpp"
 #include "top_k_lists.hpp"
-
-#include <type_traits>
 
 namespace nsm {
 
@@ -66,21 +64,6 @@ __device__ __forceinline__ int jaccard_need(int a, int b, double eff) {
 struct ClassWalk {
   int hi, lo;
 };
-
-// The lists of a wave: TopLists, or (GROUPED) the lists that keep one record per group of right rows.
-template <bool GROUPED>
-using TopListsOf = std::conditional_t<GROUPED, GroupedTopLists, TopLists>;
-
-template <bool GROUPED>
-__device__ __forceinline__ TopListsOf<GROUPED> make_lists(nsm_hit* list, int32_t* glist, int k, int row0, int lane) {
-  if constexpr (GROUPED) {
-    GroupedTopLists L{{list, k, row0, lane}};
-    L.grp = glist;
-    return L;
-  } else {
-    return TopLists{list, k, row0, lane};
-  }
-}
 
 // ------------------------------------------------------------------------------------------------------------------ Indel
 struct TopIndelParams {
@@ -130,7 +113,7 @@ __global__ __launch_bounds__(kWave) void indel_top_k_kernel(
   }
   __syncthreads();
 
-  TopListsOf<GROUPED> L = make_lists<GROUPED>(list, glist, p.k, row0, lane);
+  TopLists<GROUPED> L{list, glist, p.k, row0, lane};
   unsigned long long st[4] = {0, 0, 0, 0};
 
   // upper bound of a pair of row g with a right row of length lb: all of the shorter string in common
@@ -227,10 +210,8 @@ __global__ __launch_bounds__(kWave) void indel_top_k_kernel(
         }
         st[3] += mine ? 1u : 0u;
         const double sc = indel_score(a, lb, lcs);
-        if constexpr (GROUPED)
-          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo, rgroup[jo]);
-        else
-          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
+        L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo,
+                      L.group_of(rgroup, jo));
       }
     }
   }
@@ -252,7 +233,6 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
     unsigned long long* __restrict__ out_count, unsigned long long* __restrict__ stats, const TopJacParams p,
     const int32_t* __restrict__ rgroup, int32_t* __restrict__ glist) {
   constexpr int G = kTopG;
-  constexpr uint64_t kCollBits = ~((1ull << 58) - 1);  // the top 6 bits of a signature word hold c (unary)
   __shared__ int32_t s_ids[G * W];
   const int lane = threadIdx.x;
   const int row0 = blockIdx.x * G;
@@ -273,7 +253,7 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
   for (int e = lane; e < G * W; e += kWave) s_ids[e] = (e / W < rows) ? lids[static_cast<size_t>(row0) * W + e] : -1;
   __syncthreads();
 
-  TopListsOf<GROUPED> L = make_lists<GROUPED>(list, glist, p.k, row0, lane);
+  TopLists<GROUPED> L{list, glist, p.k, row0, lane};
   unsigned long long st[4] = {0, 0, 0, 0};
 
   // upper bound with a set of b ids: min / max -- 0 when exactly one side is empty; two empty sets never score
@@ -364,10 +344,8 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
         }
         st[3] += mine ? 1u : 0u;
         const double sc = mine ? topk_jaccard_score(a, b, inter) : 0.0;
-        if constexpr (GROUPED)
-          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo, rgroup[jo]);
-        else
-          L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo);
+        L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo,
+                      L.group_of(rgroup, jo));
       }
     }
   }
@@ -378,83 +356,66 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
 // rgroup == nullptr: the ungrouped kernels (rgroup and glist unused); else the grouped ones
 template <int W, bool PRUNE, bool HIST>
 static int launch_indel_top_k(const nsm_str_table* l, const nsm_str_table* r, const int32_t* rgroup, const TopIndelParams& p,
-                              nsm_hit* list, int32_t* glist, nsm_hit* out, unsigned long long* out_count,
-                              unsigned long long* stats, hipStream_t s) {
-  const size_t lds = static_cast<size_t>(kTopG) * p.pm_stride * W * 8;
-  const void* kern = rgroup ? reinterpret_cast<const void*>(indel_top_k_kernel<W, PRUNE, HIST, true>)
-                            : reinterpret_cast<const void*>(indel_top_k_kernel<W, PRUNE, HIST, false>);
-  if (lds > 64 * 1024) {
-    const int st = hip_status(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)),
-                              "indel_top_k_kernel LDS");
-    if (st) return st;
-  }
-  const dim3 grid((p.n_left + kTopG - 1) / kTopG);
-  const uint32_t* lh = reinterpret_cast<const uint32_t*>(l->hist);
-  const uint32_t* rh = reinterpret_cast<const uint32_t*>(r->hist);
-  if (rgroup)
-    hipLaunchKernelGGL((indel_top_k_kernel<W, PRUNE, HIST, true>), grid, dim3(kWave), lds, s, l->codes, l->len, l->orig, lh,
-                       r->codes, r->len_start, r->orig, rh, list, out, out_count, stats, p, rgroup, glist);
-  else
-    hipLaunchKernelGGL((indel_top_k_kernel<W, PRUNE, HIST, false>), grid, dim3(kWave), lds, s, l->codes, l->len, l->orig, lh,
-                       r->codes, r->len_start, r->orig, rh, list, out, out_count, stats, p, rgroup, glist);
-  return hip_status(hipGetLastError(), "indel_top_k_kernel launch");
+                              const TopOut& o) {
+  return by_grouped(rgroup != nullptr, [&](auto grouped) {
+    auto* kern = indel_top_k_kernel<W, PRUNE, HIST, decltype(grouped)::value>;
+    const size_t lds = static_cast<size_t>(kTopG) * p.pm_stride * W * 8;
+    if (lds > 64 * 1024) {
+      const int st = hip_status(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                    static_cast<int>(lds)), "indel_top_k_kernel LDS");
+      if (st) return st;
+    }
+    hipLaunchKernelGGL(kern, dim3((p.n_left + kTopG - 1) / kTopG), dim3(kWave), lds, o.sc.s, l->codes, l->len, l->orig,
+                       reinterpret_cast<const uint32_t*>(l->hist), r->codes, r->len_start, r->orig,
+                       reinterpret_cast<const uint32_t*>(r->hist), o.sc.list, o.out, o.out_count, o.stats, p, rgroup, o.sc.glist);
+    return hip_status(hipGetLastError(), "indel_top_k_kernel launch");
+  });
 }
 
 template <int W>
 static int dispatch_indel(bool prune, bool hist, const nsm_str_table* l, const nsm_str_table* r, const int32_t* rgroup,
-                          const TopIndelParams& p, nsm_hit* list, int32_t* glist, nsm_hit* out, unsigned long long* out_count,
-                          unsigned long long* stats, hipStream_t s) {
-  if (!prune) return launch_indel_top_k<W, false, false>(l, r, rgroup, p, list, glist, out, out_count, stats, s);
-  if (hist) return launch_indel_top_k<W, true, true>(l, r, rgroup, p, list, glist, out, out_count, stats, s);
-  return launch_indel_top_k<W, true, false>(l, r, rgroup, p, list, glist, out, out_count, stats, s);
+                          const TopIndelParams& p, const TopOut& o) {
+  if (!prune) return launch_indel_top_k<W, false, false>(l, r, rgroup, p, o);
+  if (hist) return launch_indel_top_k<W, true, true>(l, r, rgroup, p, o);
+  return launch_indel_top_k<W, true, false>(l, r, rgroup, p, o);
 }
 
-template <int W, bool PRUNE>
-static int launch_jaccard_top_k(const nsm_set_table* l, const nsm_set_table* r, const int32_t* rgroup, const TopJacParams& p,
-                                nsm_hit* list, int32_t* glist, nsm_hit* out, unsigned long long* out_count,
-                                unsigned long long* stats, hipStream_t s) {
-  const dim3 grid((p.n_left + kTopG - 1) / kTopG);
-  if (rgroup)
-    hipLaunchKernelGGL((jaccard_top_k_kernel<W, PRUNE, true>), grid, dim3(kWave), 0, s, l->ids, l->cnt, l->sig, l->sig2, l->orig,
-                       r->ids, r->size_start, r->sig, r->sig2, r->orig, list, out, out_count, stats, p, rgroup, glist);
-  else
-    hipLaunchKernelGGL((jaccard_top_k_kernel<W, PRUNE, false>), grid, dim3(kWave), 0, s, l->ids, l->cnt, l->sig, l->sig2, l->orig,
-                       r->ids, r->size_start, r->sig, r->sig2, r->orig, list, out, out_count, stats, p, rgroup, glist);
-  return hip_status(hipGetLastError(), "jaccard_top_k_kernel launch");
+template <int W>
+static int dispatch_jaccard(bool prune, const nsm_set_table* l, const nsm_set_table* r, const int32_t* rgroup,
+                            const TopJacParams& p, const TopOut& o) {
+  auto launch = [&](auto pruned) {
+    return by_grouped(rgroup != nullptr, [&](auto grouped) {
+      hipLaunchKernelGGL((jaccard_top_k_kernel<W, decltype(pruned)::value, decltype(grouped)::value>),
+                         dim3((p.n_left + kTopG - 1) / kTopG), dim3(kWave), 0, o.sc.s, l->ids, l->cnt, l->sig, l->sig2, l->orig,
+                         r->ids, r->size_start, r->sig, r->sig2, r->orig, o.sc.list, o.out, o.out_count, o.stats, p, rgroup,
+                         o.sc.glist);
+      return hip_status(hipGetLastError(), "jaccard_top_k_kernel launch");
+    });
+  };
+  return prune ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
-// Scratch for the group ids of the lists' records (grouped queries only), stream-ordered like the lists.
-static int with_groups(int n_left, int k, hipStream_t s, int32_t** glist) {
-  const size_t bytes = static_cast<size_t>(n_left) * static_cast<size_t>(k) * sizeof(int32_t);
-  return hip_status(hipMallocAsync(reinterpret_cast<void**>(glist), bytes ? bytes : 1, s), "top_k group scratch");
+// The checks both RAW entries start with, in this order: null arguments, k < 1, the group column.
+static int check_raw_args(const char* who, const void* left, const void* right, const void* out, const void* out_count,
+                          int32_t k, bool grouped, const int32_t* right_group) {
+  if (!left || !right || !out_count || !out) {
+    set_error("%s: null argument", who);
+    return NSM_E_BADARG;
+  }
+  if (int st = check_k(who, k)) return st;
+  if (grouped && !right_group) {
+    set_error("%s: right_group is null", who);
+    return NSM_E_BADARG;
+  }
+  return 0;
 }
 
 // Both Indel entries: `grouped` asks for right_group (one record per group, top_k_lists.hpp).
 static int indel_raw_top_k(const char* who, bool grouped, const nsm_str_table* left, const nsm_str_table* right,
                            const int32_t* right_group, double threshold, int32_t k, uint32_t flags, nsm_hit* out,
                            unsigned long long* out_count, uint64_t* stats, void* stream) {
-  if (!left || !right || !out_count || !out) {
-    set_error("%s: null argument", who);
-    return NSM_E_BADARG;
-  }
-  int keff = 0;
-  if (k < 1) return clamp_k(who, k, right->n, &keff);
-  if (grouped && !right_group) {
-    set_error("%s: right_group is null", who);
-    return NSM_E_BADARG;
-  }
-  if (left->stride != right->stride) {
-    set_error("%s: strides differ (%d, %d)", who, left->stride, right->stride);
-    return NSM_E_BADARG;
-  }
-  if (left->stride != 64 && left->stride != 128 && left->stride != 256 && left->stride != 512) {
-    set_error("%s: stride %d unsupported (64, 128, 256 or 512 code units)", who, left->stride);
-    return NSM_E_UNSUPPORTED;
-  }
-  if (left->alphabet != right->alphabet || left->alphabet < 1 || left->alphabet > 255) {
-    set_error("%s: alphabets differ or exceed 255 (%d, %d)", who, left->alphabet, right->alphabet);
-    return NSM_E_BADARG;
-  }
+  if (int st = check_raw_args(who, left, right, out, out_count, k, grouped, right_group)) return st;
+  if (int st = check_str_tables(who, left, right)) return st;
   if (left->n < 0 || right->n < 0) {
     set_error("%s: negative row count", who);
     return NSM_E_BADARG;
@@ -463,6 +424,7 @@ static int indel_raw_top_k(const char* who, bool grouped, const nsm_str_table* l
     set_error("%s: table has a null column (the right table needs len_start)", who);
     return NSM_E_BADARG;
   }
+  int keff = 0;
   if (int st = clamp_k(who, k, right->n, &keff)) return st;
   if (left->n == 0 || right->n == 0) return 0;
   TopIndelParams p;
@@ -471,53 +433,27 @@ static int indel_raw_top_k(const char* who, bool grouped, const nsm_str_table* l
   p.k = keff;
   p.pm_stride = ((left->alphabet + 1) + 63) / 64 * 64;
   p.threshold = threshold;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool prune = (flags & NSM_FLAG_PRUNE) != 0;
   // (a 32-bucket count saturates at 255: the histogram bound holds for rows of at most 255 code units)
   const bool hist = prune && left->hist && right->hist && left->stride <= 128;
-  nsm_hit* list = nullptr;
-  if (int st = with_lists(left->n, keff, s, &list)) return st;
-  int32_t* glist = nullptr;
-  if (grouped) {
-    if (int st = with_groups(left->n, keff, s, &glist)) {
-      (void)hipFreeAsync(list, s);
-      return st;
-    }
-  }
-  unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
+  if (int st = o.sc.alloc(left->n, keff, grouped)) return st;
   const int32_t* rg = grouped ? right_group : nullptr;
   int st = 0;
   switch (left->stride) {
-    case 64: st = dispatch_indel<1>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
-    case 128: st = dispatch_indel<2>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
-    case 256: st = dispatch_indel<4>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
-    default: st = dispatch_indel<8>(prune, hist, left, right, rg, p, list, glist, out, out_count, sp, s); break;
+    case 64: st = dispatch_indel<1>(prune, hist, left, right, rg, p, o); break;
+    case 128: st = dispatch_indel<2>(prune, hist, left, right, rg, p, o); break;
+    case 256: st = dispatch_indel<4>(prune, hist, left, right, rg, p, o); break;
+    default: st = dispatch_indel<8>(prune, hist, left, right, rg, p, o); break;
   }
-  int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
-  if (grouped) {
-    const int gst = hip_status(hipFreeAsync(glist, s), "top_k group scratch");
-    fst = fst ? fst : gst;
-  }
-  return st ? st : fst;
+  return o.sc.release(st);
 }
 
 static int jaccard_raw_top_k(const char* who, bool grouped, const nsm_set_table* left, const nsm_set_table* right,
                              const int32_t* right_group, double threshold, int32_t k, uint32_t flags, nsm_hit* out,
                              unsigned long long* out_count, uint64_t* stats, void* stream) {
-  if (!left || !right || !out_count || !out) {
-    set_error("%s: null argument", who);
-    return NSM_E_BADARG;
-  }
-  int keff = 0;
-  if (k < 1) return clamp_k(who, k, right->n, &keff);
-  if (grouped && !right_group) {
-    set_error("%s: right_group is null", who);
-    return NSM_E_BADARG;
-  }
-  if (left->width != right->width || (left->width != 16 && left->width != 32 && left->width != 64)) {
-    set_error("%s: width %d/%d unsupported (both sides 16, 32 or 64)", who, left->width, right->width);
-    return NSM_E_BADARG;
-  }
+  if (int st = check_raw_args(who, left, right, out, out_count, k, grouped, right_group)) return st;
+  if (int st = check_set_tables(who, left, right)) return st;
   if (left->n < 0 || right->n < 0) {
     set_error("%s: negative row count", who);
     return NSM_E_BADARG;
@@ -526,6 +462,7 @@ static int jaccard_raw_top_k(const char* who, bool grouped, const nsm_set_table*
     set_error("%s: table has a null column (the right table needs size_start)", who);
     return NSM_E_BADARG;
   }
+  int keff = 0;
   if (int st = clamp_k(who, k, right->n, &keff)) return st;
   if (left->n == 0 || right->n == 0) return 0;
   TopJacParams p;
@@ -533,34 +470,17 @@ static int jaccard_raw_top_k(const char* who, bool grouped, const nsm_set_table*
   p.n_right = right->n;
   p.k = keff;
   p.threshold = threshold;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const bool prune = (flags & NSM_FLAG_PRUNE) && left->sig && right->sig;
-  nsm_hit* list = nullptr;
-  if (int st = with_lists(left->n, keff, s, &list)) return st;
-  int32_t* glist = nullptr;
-  if (grouped) {
-    if (int st = with_groups(left->n, keff, s, &glist)) {
-      (void)hipFreeAsync(list, s);
-      return st;
-    }
-  }
-  unsigned long long* sp = reinterpret_cast<unsigned long long*>(stats);
+  TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
+  if (int st = o.sc.alloc(left->n, keff, grouped)) return st;
   const int32_t* rg = grouped ? right_group : nullptr;
   int st = 0;
   switch (left->width) {
-    case 16: st = prune ? launch_jaccard_top_k<16, true>(left, right, rg, p, list, glist, out, out_count, sp, s)
-                        : launch_jaccard_top_k<16, false>(left, right, rg, p, list, glist, out, out_count, sp, s); break;
-    case 32: st = prune ? launch_jaccard_top_k<32, true>(left, right, rg, p, list, glist, out, out_count, sp, s)
-                        : launch_jaccard_top_k<32, false>(left, right, rg, p, list, glist, out, out_count, sp, s); break;
-    default: st = prune ? launch_jaccard_top_k<64, true>(left, right, rg, p, list, glist, out, out_count, sp, s)
-                        : launch_jaccard_top_k<64, false>(left, right, rg, p, list, glist, out, out_count, sp, s); break;
+    case 16: st = dispatch_jaccard<16>(prune, left, right, rg, p, o); break;
+    case 32: st = dispatch_jaccard<32>(prune, left, right, rg, p, o); break;
+    default: st = dispatch_jaccard<64>(prune, left, right, rg, p, o); break;
   }
-  int fst = hip_status(hipFreeAsync(list, s), "top_k list scratch");
-  if (grouped) {
-    const int gst = hip_status(hipFreeAsync(glist, s), "top_k group scratch");
-    fst = fst ? fst : gst;
-  }
-  return st ? st : fst;
+  return o.sc.release(st);
 }
 
 }  // namespace nsm

@@ -258,6 +258,21 @@ def _top_k(launch: Callable, n_left: int, n_right: int, k: int, device, what: st
     return sort_hits_device(buf, n, id_limit)
 
 
+def _raw_top_k(entry: str, left, right, device, k: int, threshold: float, prune: bool, stats: Optional[list], groups,
+               id_limit: int = 0) -> Hits:
+    """A RAW top-k query through the C entry ``entry``, or with ``groups`` through ``entry + "_grouped"`` (the same
+    arguments with the group column in front of the threshold)."""
+    what = entry if groups is None else entry + "_grouped"
+    gcol = None if groups is None else _device_groups(groups, right.n, right.orig, device, what)
+    fn = getattr(_lib.load(), what)
+    ls, rs = left.struct(), right.struct()
+    flags = _lib.FLAG_PRUNE if prune else 0
+    group_arg = () if gcol is None else (gcol.data_ptr(),)
+    return _top_k(lambda out, cnt, st, kk, stream: fn(
+        ls, rs, *group_arg, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
+        left.n, right.n, k, device, what, stats, id_limit)
+
+
 def indel_raw_top_k(left: StrTable, right: StrTable, k: int, threshold: float, prune: bool = True,
                     stats: Optional[list] = None, groups=None) -> Hits:
     """For every left item the first ``min(k, #hits of its row)`` records of ``indel_raw_grid(left, right, threshold)``
@@ -267,20 +282,7 @@ def indel_raw_top_k(left: StrTable, right: StrTable, k: int, threshold: float, p
     the best record of every group (its representative) and of those the first ``k``: ``select_top_k(hits, k, groups)`` of
     the threshold grid's hits, computed by ``nsm_indel_raw_top_k_grouped`` with lists of one record per group."""
     k = check_k(k)
-    flags = _lib.FLAG_PRUNE if prune else 0
-    if groups is not None:
-        what = "nsm_indel_raw_top_k_grouped"
-        gcol = _device_groups(groups, right.n, right.orig, left.codes.device, what)
-        lib = _lib.load()
-        ls, rs = left.struct(), right.struct()
-        return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_indel_raw_top_k_grouped(
-            ls, rs, gcol.data_ptr(), float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
-            left.n, right.n, k, left.codes.device, what, stats)
-    lib = _lib.load()
-    ls, rs = left.struct(), right.struct()
-    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_indel_raw_top_k(
-        ls, rs, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
-        left.n, right.n, k, left.codes.device, "nsm_indel_raw_top_k", stats)
+    return _raw_top_k("nsm_indel_raw_top_k", left, right, left.codes.device, k, threshold, prune, stats, groups)
 
 
 def jaccard_raw_top_k(left: SetTable, right: SetTable, k: int, threshold: float, prune: bool = True,
@@ -290,25 +292,12 @@ def jaccard_raw_top_k(left: SetTable, right: SetTable, k: int, threshold: float,
     k = check_k(k)
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    if groups is not None and len(groups) != right.n:
+    if groups is not None and len(groups) != right.n:  # (a wrong length is reported before the division by zero)
         raise ValueError(f"nsm_jaccard_raw_top_k_grouped: {len(groups)} group ids for {right.n} right items")
     if left.has_empty and right.has_empty:
         raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
-    flags = _lib.FLAG_PRUNE if prune else 0
     id_limit = max(left.id_limit, right.id_limit) if left.id_limit and right.id_limit else 0
-    if groups is not None:
-        what = "nsm_jaccard_raw_top_k_grouped"
-        gcol = _device_groups(groups, right.n, right.orig, left.ids.device, what)
-        lib = _lib.load()
-        ls, rs = left.struct(), right.struct()
-        return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_jaccard_raw_top_k_grouped(
-            ls, rs, gcol.data_ptr(), float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
-            left.n, right.n, k, left.ids.device, what, stats, id_limit)
-    lib = _lib.load()
-    ls, rs = left.struct(), right.struct()
-    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_jaccard_raw_top_k(
-        ls, rs, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
-        left.n, right.n, k, left.ids.device, "nsm_jaccard_raw_top_k", stats, id_limit)
+    return _raw_top_k("nsm_jaccard_raw_top_k", left, right, left.ids.device, k, threshold, prune, stats, groups, id_limit)
 
 
 # ------------------------------------------------------------------------------- levels top-k
@@ -338,6 +327,22 @@ def _left_id_limit(orig: torch.Tensor, n: int) -> int:
     return int(orig[:n].max().item()) + 1 if n else 0
 
 
+def _levels_top_k(entry: str, tables: tuple, left, right, device, k: int, threshold: float, category_mode: int, prune: bool,
+                  banned, stats: Optional[list]) -> Hits:
+    """A levels top-k query through the C entry ``entry``: ``tables`` in the entry's argument order, ``left`` / ``right``
+    the two item tables among them (row counts, caller ids, the encoder's category predicate)."""
+    fn = getattr(_lib.load(), entry)
+    if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
+        category_mode = left.category_mode
+    structs = [t.struct() for t in tables]
+    flags = _lib.FLAG_PRUNE if prune else 0
+    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), device)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    return _top_k(lambda out, cnt, st, kk, stream: fn(
+        *structs, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
+        st.data_ptr(), stream), left.n, right.n, k, device, entry, stats)
+
+
 def indel_levels_top_k(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, k: int,
                        threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
                        stats: Optional[list] = None) -> Hits:
@@ -347,17 +352,8 @@ def indel_levels_top_k(left: LevelItems, left_strings: StrTable, right: LevelIte
     ``partition=False``.  ``stats``: a list that receives [pairs visited, pairs past the category predicate and the
     length bound, pairs past the histogram bound, pairs that got an exact level score]."""
     k = check_k(k)
-    lib = _lib.load()
-    if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
-        category_mode = left.category_mode
-    li, ls, ri, rs = left.struct(), left_strings.struct(), right.struct(), right_strings.struct()
-    flags = _lib.FLAG_PRUNE if prune else 0
-    dev = left.first.device
-    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), dev)
-    ptr = lambda t: 0 if t is None else t.data_ptr()
-    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_indel_levels_top_k(
-        li, ls, ri, rs, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
-        st.data_ptr(), stream), left.n, right.n, k, dev, "nsm_indel_levels_top_k", stats)
+    return _levels_top_k("nsm_indel_levels_top_k", (left, left_strings, right, right_strings), left, right, left.first.device,
+                         k, threshold, category_mode, prune, banned, stats)
 
 
 def jaccard_levels_top_k(left: SetTable, right: SetTable, k: int, threshold: float, category_mode: int = _lib.CAT_NONE,
@@ -369,17 +365,8 @@ def jaccard_levels_top_k(left: SetTable, right: SetTable, k: int, threshold: flo
         raise ValueError("levels top-k needs tables built with SetTable.from_levels")
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    lib = _lib.load()
-    if left.category_mode is not None:
-        category_mode = left.category_mode
-    ls, rs = left.struct(), right.struct()
-    flags = _lib.FLAG_PRUNE if prune else 0
-    dev = left.ids.device
-    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), dev)
-    ptr = lambda t: 0 if t is None else t.data_ptr()
-    return _top_k(lambda out, cnt, st, kk, stream: lib.nsm_jaccard_levels_top_k(
-        ls, rs, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
-        st.data_ptr(), stream), left.n, right.n, k, dev, "nsm_jaccard_levels_top_k", stats)
+    return _levels_top_k("nsm_jaccard_levels_top_k", (left, right), left, right, left.ids.device, k, threshold,
+                         category_mode, prune, banned, stats)
 
 
 # ------------------------------------------------------------------------------- levels grids

@@ -530,15 +530,15 @@ class ComparableData:
         if keep_l.size and keep_r.size and top_k is not None:
             # per-item lists on the device: categories and blacklist go to the kernel, which keeps each item's best
             on_device = cats is not None
-            hits = _levels_top_k(
+            hits = _levels_grid(
                 plugin,
                 [levels_l[k] for k in keep_l],
                 [levels_r[k] for k in keep_r],
                 score_threshold,
-                top_k,
                 cats.left_mask[keep_l] if on_device else None,
                 cats.right_mask[keep_r] if on_device else None,
                 cats.mode if on_device else _lib.CAT_NONE,
+                top_k=top_k,
                 banned=_local_banned(banned, keep_l, keep_r),
             )
         elif keep_l.size and keep_r.size:
@@ -763,11 +763,18 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
     return grid.jaccard_levels_grid(lt, rt, threshold, category_mode=cat_mode, index=use_index, defer=defer)
 
 
-def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_lib.CAT_NONE, defer: bool = False):
+def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_lib.CAT_NONE, defer: bool = False, top_k=None,
+                 banned=None):
     """Encode both sides' levels for ``plugin`` and run the levels grid on the current device.  ``defer``: when the
     whole grid goes through ONE fast kernel call, return its hits still on the device (``grid.PendingHits``: the sharded
     ``gen_comparable`` exchanges them without a host detour); grids that are split (wide / irregular items) return
-    ``grid.Hits`` as always."""
+    ``grid.Hits`` as always.
+
+    ``top_k``: per left item only the first ``top_k`` records (score descending, right index ascending) of that grid
+    without the ``banned`` pairs ((left, right) positions in these lists, or None); ``defer`` is then ignored.  Items the
+    fast kernels take go through ``nsm_*_levels_top_k`` (tables without a category partition or an inverted index: an item
+    must stay one row to keep one list); wide or irregular items through the general kernels at the threshold, cut per
+    item on the host; the parts are disjoint in j for every i, so the per-item selection over their union is the answer."""
     import torch
 
     if not torch.cuda.is_available():
@@ -775,26 +782,36 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
     dev = torch.device("cuda", torch.cuda.current_device())
     from .. import wide
 
-    sub = lambda seq, idx: [seq[k] for k in idx]
-    cut = lambda cat, idx: None if cat is None else np.asarray(cat)[np.asarray(idx, dtype=np.int64)]
+    # (idx None: the whole side)
+    sub = lambda seq, idx: seq if idx is None else [seq[k] for k in idx]
+    cut = lambda cat, idx: cat if cat is None or idx is None else np.asarray(cat)[np.asarray(idx, dtype=np.int64)]
+
+    def split_grid(split, fast, general):
+        """The parts of a split grid, merged; a top-k query cuts the general parts and the merged result per item."""
+        if top_k is None:
+            return wide.split_grid(split[0], split[1], fast, general)
+        cut_general = lambda li, ri: grid.select_top_k(_drop_banned(general(li, ri), banned, li, ri), top_k)
+        return grid.select_top_k(wide.split_grid(split[0], split[1], fast, cut_general), top_k)
+
     if plugin.kind == "sets":
         as_set_levels = lambda it: [lv if isinstance(lv, list) else lv.split() for lv in it]
         def split_route(split):
             # items of more than 64 distinct tokens / more than 64 levels / levels that are not suffix-nested leave the fast
             # path (wide.py: general kernel, every step's level sets scored on their own); the rest is scored as always
             fast = lambda li, ri: _levels_grid(plugin, sub(levels_l, li), sub(levels_r, ri), threshold, cut(cat_l, li),
-                                               cut(cat_r, ri), cat_mode)
+                                               cut(cat_r, ri), cat_mode, top_k=top_k, banned=_restrict_banned(banned, li, ri))
             general = lambda li, ri: wide.jaccard_any_grid(
                 [as_set_levels(levels_l[k]) for k in li], [as_set_levels(levels_r[k]) for k in ri], threshold, cut(cat_l, li),
                 cut(cat_r, ri), cat_mode, device=dev)
-            return wide.split_grid(split[0], split[1], fast, general)
+            return split_grid(split, fast, general)
 
         split = wide.wide_set_items([as_set_levels(it) for it in levels_l], [as_set_levels(it) for it in levels_r]) \
             if _may_be_wide_sets(levels_l, levels_r) else None
         if split is not None:
             return split_route(split)
         try:
-            return _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, defer)
+            return _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev,
+                                        defer and top_k is None, top_k, banned)
         except tables.IrregularLevels:
             # the reference scores whatever its tokenizer yields per level (:283-299): find the items the nested layout
             # cannot hold and route only them
@@ -806,18 +823,23 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
     prep = lambda items: ComparableData._memoised(
         "fuzzy", items, lambda it: [score_functions.fuzzy_operand(lv) for lv in it])
     ops_l, ops_r = prep(levels_l), prep(levels_r)
-    split = wide.wide_string_items(ops_l, ops_r)
-    if split is not None:
-        # level strings of more than 512 code units / a grid of more than 255 distinct code units (wide.py)
-        def fast(li, ri):
-            a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode)
-            return grid.indel_levels_grid(a, b, c, d, threshold, category_mode=cat_mode)
 
-        general = lambda li, ri: wide.indel_any_grid(sub(ops_l, li), sub(ops_r, ri), threshold, cut(cat_l, li), cut(cat_r, ri),
-                                                     cat_mode, device=dev)
-        return wide.split_grid(split[0], split[1], fast, general)
-    li, ls, ri, rs = tables.encode_level_strings(ops_l, ops_r, dev, cat_l, cat_r, cat_mode)
-    return grid.indel_levels_grid(li, ls, ri, rs, threshold, category_mode=cat_mode, defer=defer)
+    def fast(li, ri, defer=False):
+        if top_k is None:
+            a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode)
+            return grid.indel_levels_grid(a, b, c, d, threshold, category_mode=cat_mode, defer=defer)
+        a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
+                                                 partition=False)
+        return grid.indel_levels_top_k(a, b, c, d, top_k, threshold, category_mode=cat_mode,
+                                       banned=_restrict_banned(banned, li, ri))
+
+    split = wide.wide_string_items(ops_l, ops_r)
+    if split is None:
+        return fast(None, None, defer)
+    # level strings of more than 512 code units / a grid of more than 255 distinct code units (wide.py)
+    general = lambda li, ri: wide.indel_any_grid(sub(ops_l, li), sub(ops_r, ri), threshold, cut(cat_l, li), cut(cat_r, ri),
+                                                 cat_mode, device=dev)
+    return split_grid(split, fast, general)
 
 
 # =============================================================================== per-item top-k
@@ -835,9 +857,10 @@ def _local_banned(banned: set, keep_l: np.ndarray, keep_r: np.ndarray):
 
 
 def _restrict_banned(banned, li, ri):
-    """``banned`` (positions in the parent lists) restricted to the sub-grid ``li`` x ``ri``, in positions of the sub-lists."""
-    if banned is None:
-        return None
+    """``banned`` (positions in the parent lists) restricted to the sub-grid ``li`` x ``ri`` (None: the whole grid), in
+    positions of the sub-lists."""
+    if banned is None or li is None:
+        return banned
     li, ri = np.asarray(li, dtype=np.int64), np.asarray(ri, dtype=np.int64)
     bi, bj = banned
     size = lambda idx, b: int(max(idx.max(initial=-1), b.max(initial=-1))) + 1
@@ -856,60 +879,3 @@ def _drop_banned(hits: grid.Hits, banned, li, ri) -> grid.Hits:
     n_r = int(max(ri.max(initial=-1), banned[1].max(initial=-1))) + 1
     ok = ~np.isin(li[hits.i] * n_r + ri[hits.j], banned[0] * n_r + banned[1])
     return grid.Hits(hits.score[ok], hits.i[ok], hits.j[ok])
-
-
-def _levels_top_k(plugin, levels_l, levels_r, threshold, k, cat_l, cat_r, cat_mode=_lib.CAT_NONE, banned=None) -> grid.Hits:
-    """Per left item the first ``k`` records (score descending, right index ascending) of ``_levels_grid`` without the
-    ``banned`` pairs ((left, right) positions in these lists, or None).  Items the fast kernels take go through
-    ``nsm_*_levels_top_k`` (tables without a category partition: an item must stay one row to keep one list); wide or
-    irregular items through the general kernels at the threshold, cut per item on the host; the parts are disjoint in j
-    for every i, so the per-item selection over their union is the answer."""
-    import torch
-
-    if not torch.cuda.is_available():
-        raise _lib.NsmLibraryError("the match loop runs on an MI355X (HIP device); there is no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    from .. import wide
-
-    sub = lambda seq, idx: [seq[q] for q in idx]
-    cut = lambda cat, idx: None if cat is None else np.asarray(cat)[np.asarray(idx, dtype=np.int64)]
-    if plugin.kind == "sets":
-        as_set_levels = lambda it: [lv if isinstance(lv, list) else lv.split() for lv in it]
-
-        def split_route(split):
-            fast = lambda li, ri: _levels_top_k(plugin, sub(levels_l, li), sub(levels_r, ri), threshold, k, cut(cat_l, li),
-                                                cut(cat_r, ri), cat_mode, _restrict_banned(banned, li, ri))
-            general = lambda li, ri: grid.select_top_k(_drop_banned(wide.jaccard_any_grid(
-                [as_set_levels(levels_l[q]) for q in li], [as_set_levels(levels_r[q]) for q in ri], threshold, cut(cat_l, li),
-                cut(cat_r, ri), cat_mode, device=dev), banned, li, ri), k)
-            return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)
-
-        split = wide.wide_set_items([as_set_levels(it) for it in levels_l], [as_set_levels(it) for it in levels_r]) \
-            if _may_be_wide_sets(levels_l, levels_r) else None
-        if split is not None:
-            return split_route(split)
-        try:
-            return _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, top_k=k,
-                                        banned=banned)
-        except tables.IrregularLevels:
-            split = wide.wide_set_items([as_set_levels(it) for it in levels_l], [as_set_levels(it) for it in levels_r],
-                                        nesting=True)
-            if split is None:
-                raise
-            return split_route(split)
-    prep = lambda items: ComparableData._memoised(
-        "fuzzy", items, lambda it: [score_functions.fuzzy_operand(lv) for lv in it])
-    ops_l, ops_r = prep(levels_l), prep(levels_r)
-
-    def fast(li, ri):
-        a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
-                                                 partition=False)
-        return grid.indel_levels_top_k(a, b, c, d, k, threshold, category_mode=cat_mode, banned=_restrict_banned(banned, li, ri))
-
-    split = wide.wide_string_items(ops_l, ops_r)
-    if split is None:
-        return fast(range(len(ops_l)), range(len(ops_r)))
-    # level strings of more than 512 code units / a grid of more than 255 distinct code units (wide.py)
-    general = lambda li, ri: grid.select_top_k(_drop_banned(wide.indel_any_grid(
-        sub(ops_l, li), sub(ops_r, ri), threshold, cut(cat_l, li), cut(cat_r, ri), cat_mode, device=dev), banned, li, ri), k)
-    return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k)

@@ -5,6 +5,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from support.top_k_entry_errors import BADARG, NULL, OK, UNSUPPORTED, check_table
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -85,3 +87,122 @@ def test_select_top_k_is_the_rank_cut():
     got = grid.select_top_k(hits, 2).as_tuples()
     assert got == [(0.9, 0, 4), (0.9, 1, 2), (0.7, 1, 5), (0.5, 0, 1)]
     assert grid.select_top_k(hits, 10).as_tuples() == hits.as_tuples()
+
+
+# ---------------------------------------------------------------------------------------------- the entries' error surface
+# (label, arguments of support.top_k_entry_errors.call, status, nsm_last_error()): recorded from the library before the
+# entries' host code was unified; a case with two faults pins which check speaks first
+S = dict
+INDEL_RAW_CASES = [
+    ('null left', S(left=NULL),
+     BADARG, '{who}: null argument'),
+    ('null right', S(right=NULL),
+     BADARG, '{who}: null argument'),
+    ('null out', S(out=False),
+     BADARG, '{who}: null argument'),
+    ('null out_count', S(out_count=False),
+     BADARG, '{who}: null argument'),
+    ('k = 0', S(k=0),
+     BADARG, '{who}: k = 0 (must be >= 1)'),
+    ('k = -1', S(k=-1),
+     BADARG, '{who}: k = -1 (must be >= 1)'),
+    ('k beyond 4096 after clamping', S(k=4097),
+     UNSUPPORTED, '{who}: k = 4097 exceeds the supported 4096'),
+    ('k clamped to the right rows, empty left side', S(k=4097, left=S(n=0), right=S(n=30)),
+     OK, None),
+    ('k beyond 4096, empty left side', S(k=4097, left=S(n=0)),
+     UNSUPPORTED, '{who}: k = 4097 exceeds the supported 4096'),
+    ('strides differ', S(right=S(stride=128)),
+     BADARG, '{who}: strides differ (64, 128)'),
+    ('stride 32', S(left=S(stride=32), right=S(stride=32)),
+     UNSUPPORTED, '{who}: stride 32 unsupported (64, 128, 256 or 512 code units)'),
+    ('stride 1024', S(left=S(stride=1024), right=S(stride=1024)),
+     UNSUPPORTED, '{who}: stride 1024 unsupported (64, 128, 256 or 512 code units)'),
+    ('alphabets differ', S(right=S(alphabet=11)),
+     BADARG, '{who}: alphabets differ or exceed 255 (10, 11)'),
+    ('alphabet 0', S(left=S(alphabet=0), right=S(alphabet=0)),
+     BADARG, '{who}: alphabets differ or exceed 255 (0, 0)'),
+    ('alphabet 256', S(left=S(alphabet=256), right=S(alphabet=256)),
+     BADARG, '{who}: alphabets differ or exceed 255 (256, 256)'),
+    ('negative left n', S(left=S(n=-1)),
+     BADARG, '{who}: negative row count'),
+    ('negative right n', S(right=S(n=-2)),
+     BADARG, '{who}: negative row count'),
+    ('no len_start', S(right=S(len_start=NULL)),
+     BADARG, '{who}: table has a null column (the right table needs len_start)'),
+    ('no left codes', S(left=S(codes=NULL)),
+     BADARG, '{who}: table has a null column (the right table needs len_start)'),
+    ('no left len_start (not needed), empty right side', S(left=S(len_start=NULL), right=S(n=0)),
+     OK, None),
+    ('null left + k = 0', S(left=NULL, k=0),
+     BADARG, '{who}: null argument'),
+    ('k = 0 + strides differ', S(k=0, right=S(stride=128)),
+     BADARG, '{who}: k = 0 (must be >= 1)'),
+    ('k = -1 + no len_start', S(k=-1, right=S(len_start=NULL)),
+     BADARG, '{who}: k = -1 (must be >= 1)'),
+    ('strides differ + alphabets differ', S(right=S(stride=128, alphabet=11)),
+     BADARG, '{who}: strides differ (64, 128)'),
+    ('stride 32 + alphabets differ', S(left=S(stride=32), right=S(stride=32, alphabet=11)),
+     UNSUPPORTED, '{who}: stride 32 unsupported (64, 128, 256 or 512 code units)'),
+    ('alphabets differ + negative n', S(left=S(n=-1), right=S(alphabet=11)),
+     BADARG, '{who}: alphabets differ or exceed 255 (10, 11)'),
+    ('negative n + no len_start', S(left=S(n=-1), right=S(len_start=NULL)),
+     BADARG, '{who}: negative row count'),
+    ('no len_start + k beyond 4096', S(k=4097, right=S(len_start=NULL)),
+     BADARG, '{who}: table has a null column (the right table needs len_start)'),
+    ('negative right n + k = 5', S(k=5, right=S(n=-2)),
+     BADARG, '{who}: negative row count'),
+]
+JACCARD_RAW_CASES = [
+    ('null left', S(left=NULL),
+     BADARG, '{who}: null argument'),
+    ('null right', S(right=NULL),
+     BADARG, '{who}: null argument'),
+    ('null out', S(out=False),
+     BADARG, '{who}: null argument'),
+    ('null out_count', S(out_count=False),
+     BADARG, '{who}: null argument'),
+    ('k = 0', S(k=0),
+     BADARG, '{who}: k = 0 (must be >= 1)'),
+    ('k = -1', S(k=-1),
+     BADARG, '{who}: k = -1 (must be >= 1)'),
+    ('k beyond 4096 after clamping', S(k=4097),
+     UNSUPPORTED, '{who}: k = 4097 exceeds the supported 4096'),
+    ('k clamped to the right rows, empty left side', S(k=4097, left=S(n=0), right=S(n=30)),
+     OK, None),
+    ('widths differ', S(right=S(width=32)),
+     BADARG, '{who}: width 16/32 unsupported (both sides 16, 32 or 64)'),
+    ('width 8', S(left=S(width=8), right=S(width=8)),
+     BADARG, '{who}: width 8/8 unsupported (both sides 16, 32 or 64)'),
+    ('width 128', S(left=S(width=128), right=S(width=128)),
+     BADARG, '{who}: width 128/128 unsupported (both sides 16, 32 or 64)'),
+    ('negative left n', S(left=S(n=-1)),
+     BADARG, '{who}: negative row count'),
+    ('negative right n', S(right=S(n=-2)),
+     BADARG, '{who}: negative row count'),
+    ('no size_start', S(right=S(size_start=NULL)),
+     BADARG, '{who}: table has a null column (the right table needs size_start)'),
+    ('no left cnt', S(left=S(cnt=NULL)),
+     BADARG, '{who}: table has a null column (the right table needs size_start)'),
+    ('no left size_start (not needed), empty right side', S(left=S(size_start=NULL), right=S(n=0)),
+     OK, None),
+    ('null right + k = -1', S(right=NULL, k=-1),
+     BADARG, '{who}: null argument'),
+    ('k = 0 + widths differ', S(k=0, right=S(width=32)),
+     BADARG, '{who}: k = 0 (must be >= 1)'),
+    ('widths differ + negative n', S(left=S(n=-1), right=S(width=32)),
+     BADARG, '{who}: width 16/32 unsupported (both sides 16, 32 or 64)'),
+    ('negative n + no size_start', S(left=S(n=-1), right=S(size_start=NULL)),
+     BADARG, '{who}: negative row count'),
+    ('no size_start + k beyond 4096', S(k=4097, right=S(size_start=NULL)),
+     BADARG, '{who}: table has a null column (the right table needs size_start)'),
+]
+
+
+def test_raw_entries_answer_malformed_calls_exactly_as_recorded():
+    from napkon_string_matching_amd import _lib
+
+    if not _lib.LIB_PATH.exists():
+        pytest.skip("libnsm_hip.so not built")
+    check_table(["nsm_indel_raw_top_k", "nsm_indel_raw_top_k_grouped"], INDEL_RAW_CASES)
+    check_table(["nsm_jaccard_raw_top_k", "nsm_jaccard_raw_top_k_grouped"], JACCARD_RAW_CASES)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from support.grouped import group_cut
+from support.top_k_entry_errors import NULL, check_table
 
 BADARG = 10001
 
@@ -124,3 +125,44 @@ def test_grouped_top_k_without_gpu_raises_library_error():
         fuzzy_match.top_k(["abc"], ["abd", "x"], 1, groups=["g", "g"])
     with pytest.raises(_lib.NsmLibraryError):
         intersection_vs_union.top_k(["a b"], ["a", "b c"], 2, 0.5, groups=[1, 2])
+
+
+# ---------------------------------------------------------------------------------------------- the entries' error surface
+# (label, arguments of support.top_k_entry_errors.call, status, nsm_last_error()): recorded from the library before the
+# entries' host code was unified; a case with two faults pins which check speaks first
+S = dict
+INDEL_GROUP_CASES = [
+    ('null right_group', S(group=NULL),
+     BADARG, '{who}: right_group is null'),
+    ('null right_group + null out', S(group=NULL, out=False),
+     BADARG, '{who}: null argument'),
+    ('null right_group + k = 0', S(group=NULL, k=0),
+     BADARG, '{who}: k = 0 (must be >= 1)'),
+    ('null right_group + strides differ', S(group=NULL, right=S(stride=128)),
+     BADARG, '{who}: right_group is null'),
+    ('null right_group + k beyond 4096', S(group=NULL, k=4097),
+     BADARG, '{who}: right_group is null'),
+    ('null right_group + empty left side', S(group=NULL, left=S(n=0)),
+     BADARG, '{who}: right_group is null'),
+]
+JACCARD_GROUP_CASES = [
+    ('null right_group', S(group=NULL),
+     BADARG, '{who}: right_group is null'),
+    ('null right_group + null out_count', S(group=NULL, out_count=False),
+     BADARG, '{who}: null argument'),
+    ('null right_group + k = -1', S(group=NULL, k=-1),
+     BADARG, '{who}: k = -1 (must be >= 1)'),
+    ('null right_group + widths differ', S(group=NULL, right=S(width=32)),
+     BADARG, '{who}: right_group is null'),
+    ('null right_group + k beyond 4096', S(group=NULL, k=4097),
+     BADARG, '{who}: right_group is null'),
+]
+
+
+def test_grouped_entries_answer_a_null_group_column_exactly_as_recorded():
+    from napkon_string_matching_amd import _lib
+
+    if not _lib.LIB_PATH.exists():
+        pytest.skip("libnsm_hip.so not built")
+    check_table(["nsm_indel_raw_top_k_grouped"], INDEL_GROUP_CASES)
+    check_table(["nsm_jaccard_raw_top_k_grouped"], JACCARD_GROUP_CASES)
