@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--family", default=None, help="only this kernel family (jaccard_raw, indel_raw, jaccard_levels, indel_levels, indel_split, wide; "
                     "indel_top_k, jaccard_top_k, indel_raw_top_k_grouped, jaccard_raw_top_k_grouped, indel_levels_top_k, jaccard_levels_top_k, wide_levels_indel and wide_levels_jaccard are "
                     "drawn only when named here)")
+    ap.add_argument("--on-score", action="store_true", help="in about one round in four, whatever the family, take the threshold "
+                    "from the oracle's own score list of that round: a score s, or nextafter(s, 2.0)")
     args = ap.parse_args()
 
     import numpy as np
@@ -78,6 +80,17 @@ def main():
     def rand_string(rng, alphabet, lo, hi):
         return "".join(rng.choice(alphabet) for _ in range(rng.randint(lo, hi))).strip()
 
+    def on_score(thr, oracle):
+        """The round's threshold: in an on-score round a positive score ``s`` of the round's own oracle list (``oracle(t)`` = the
+        list at threshold t), or one ulp above it; else ``thr`` as drawn.  Every family passes its oracle call through here."""
+        if not score_round:
+            return thr
+        positive = [h[0] for h in oracle(0.0) if h[0] > 0.0]
+        if not positive:
+            return thr
+        s = score_rng.choice(positive)
+        return s if score_rng.random() < 0.5 else math.nextafter(s, 2.0)
+
     next_report = time.time() + 60.0
     while time.time() < t_end:
         rnd += 1
@@ -94,6 +107,11 @@ def main():
             family = args.family
         counts[family] = counts.get(family, 0) + 1
         thr = rng.choice(thresholds)
+        # (--on-score) a generator of its own decides, so that the rounds' other draws stay what they are without the option
+        score_rng = random.Random(rnd * 104729 + 3)
+        score_round = args.on_score and score_rng.random() < 0.25
+        if score_round:
+            counts["on_score"] = counts.get("on_score", 0) + 1
         n, m = rng.randint(1, 400), rng.randint(1, 600)
         if family in ("wide_levels_indel", "wide_levels_jaccard"):
             # the general kernels (csrc/any_grids.hip) called directly, levels mode: depths up to 300 in one wave, string
@@ -163,6 +181,7 @@ def main():
                 thr = rng.choice(full)[0]
                 if rng.random() < 0.3:
                     thr = math.nextafter(thr, 2.0)
+            thr = on_score(thr, lambda t: ao.oracle_call(g, t))  # (besides this family's own, older draw on a score)
             want = ao.oracle_call(g, thr)
             kl, kr = ao.kernel_operands(g)
             fn = wide.indel_any_grid if g.kind == "indel" else wide.jaccard_any_grid
@@ -204,6 +223,7 @@ def main():
                                                  partition=False, index=False)
                 rt = tables.SetTable.from_levels(right, "right", dev, vocabulary, width=width, categories=rcat, category_mode=mode,
                                                  partition=False, index=False)
+                thr = on_score(thr, lambda t: native.levels(False, left, right, t, lcat, rcat, mode, cap=n * m + 1))
                 full = native.levels(False, left, right, thr, lcat, rcat, mode, cap=n * m + 1)
                 what = f"W={width} vocab={vocab} levels<={max_levels} new<={max_new}"
             else:
@@ -216,6 +236,7 @@ def main():
                 dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda it: list(it))  # exact copies: ties
                 li, ls, ri, rs = tables.encode_level_strings(left, right, dev, lcat, rcat, mode, partition=False)
                 cps = lambda items: [[[ord(c) for c in s_] for s_ in it] for it in items]
+                thr = on_score(thr, lambda t: native.levels(True, cps(left), cps(right), t, lcat, rcat, mode, cap=n * m + 1))
                 full = native.levels(True, cps(left), cps(right), thr, lcat, rcat, mode, cap=n * m + 1)
                 what = f"hi={hi} stride={ls.stride} |alphabet|={len(alphabet)} levels<={max_levels}"
             # banned: random pairs and, per row, often its best pair (what the list would otherwise keep first)
@@ -262,6 +283,7 @@ def main():
                 dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda s_: "".join(s_))  # exact copies: ties
                 lt, rt = tables.encode_strings(left, right, dev)
                 cp = lambda ss: native.csr([[ord(c) for c in s_] for s_ in ss])
+                thr = on_score(thr, lambda t: native.indel_raw(cp(left), cp(right), t, cap=n * m + 1))
                 full = native.indel_raw(cp(left), cp(right), thr, cap=n * m + 1)
                 what = f"{family} hi={hi} |alphabet|={len(alphabet)} thr={thr} k={k} prune={prune} groups={pattern} {n}x{m}"
                 got = grid.indel_raw_top_k(lt, rt, k, thr, prune=prune, groups=groups)
@@ -277,6 +299,7 @@ def main():
                 pad = lambda rr: np.array([r + [-1] * (width - len(r)) for r in rr], dtype=np.int32).reshape(len(rr), width)
                 lt = tables.SetTable.from_padded(pad(left), "left", dev, width=width)
                 rt = tables.SetTable.from_padded(pad(right), "right", dev, width=width)
+                thr = on_score(thr, lambda t: native.jaccard_raw(native.csr(left), native.csr(right), t, cap=n * m + 1))
                 full = native.jaccard_raw(native.csr(left), native.csr(right), thr, cap=n * m + 1)
                 what = f"{family} W={width} kmax={kmax} vocab={vocab} thr={thr} k={k} prune={prune} groups={pattern} {n}x{m}"
                 got = grid.jaccard_raw_top_k(lt, rt, k, thr, prune=prune, groups=groups)
@@ -297,6 +320,7 @@ def main():
                 dup_some(rng, left, right, rng.choice([0.0, 0.1, 0.5]), lambda s_: "".join(s_))  # exact copies: ties
                 lt, rt = tables.encode_strings(left, right, dev)
                 cp = lambda ss: native.csr([[ord(c) for c in s_] for s_ in ss])
+                thr = on_score(thr, lambda t: native.indel_raw(cp(left), cp(right), t, cap=n * m + 1))
                 full = native.indel_raw(cp(left), cp(right), thr, cap=n * m + 1)
                 what = f"indel_top_k hi={hi} |alphabet|={len(alphabet)} thr={thr} k={k} prune={prune} {n}x{m}"
                 got = grid.indel_raw_top_k(lt, rt, k, thr, prune=prune)
@@ -319,6 +343,7 @@ def main():
                         continue
                     print(json.dumps({"FAIL": what + " (no ZeroDivisionError for empty x empty)", "round_seed": rnd}))
                     sys.exit(1)
+                thr = on_score(thr, lambda t: native.jaccard_raw(native.csr(left), native.csr(right), t, cap=n * m + 1))
                 full = native.jaccard_raw(native.csr(left), native.csr(right), thr, cap=n * m + 1)
                 what = f"jaccard_top_k W={width} kmax={kmax} vocab={vocab} thr={thr} k={k} prune={prune} {n}x{m}"
                 got = grid.jaccard_raw_top_k(lt, rt, k, thr, prune=prune)
@@ -340,8 +365,8 @@ def main():
                 left = [rng.sample(range(vocab), min(vocab, size())) for _ in range(n)]
                 right = [rng.sample(range(vocab), min(vocab, size())) for _ in range(m)]
                 dup_some(rng, left, right, 0.1, lambda r: list(dict.fromkeys(r[: max(1, len(r) - rng.randint(0, 3))] + [rng.randrange(vocab)])))
-                want = native.jaccard_raw(native.csr([sorted(set(r)) for r in left]), native.csr([sorted(set(r)) for r in right]), thr,
-                                          cap=1 << 16)
+                thr = on_score(thr, lambda t: native.jaccard_raw(native.csr([sorted(set(r)) for r in left]), native.csr([sorted(set(r)) for r in right]), t, cap=1 << 16))
+                want = native.jaccard_raw(native.csr([sorted(set(r)) for r in left]), native.csr([sorted(set(r)) for r in right]), thr, cap=1 << 16)
                 names = lambda rows: [[f"t{v}" for v in r] for r in rows]
                 check(sf.intersection_vs_union.raw_grid(names(left), names(right), thr), want, f"wide jaccard_raw vocab={vocab} thr={thr} {n}x{m}")
             else:
@@ -351,6 +376,7 @@ def main():
                 right = [rand_string(rng, alphabet, 0, length()) for _ in range(m)]
                 dup_some(rng, left, right, 0.1, lambda s_: ("".join(s_)[:-1] + rng.choice(alphabet)).strip())
                 cp = lambda ss: native.csr([[ord(c) for c in sf.fuzzy_operand(s_)] for s_ in ss])
+                thr = on_score(thr, lambda t: native.indel_raw(cp(left), cp(right), t, cap=1 << 16))
                 want = native.indel_raw(cp(left), cp(right), thr, cap=1 << 16)
                 check(sf.fuzzy_match.raw_grid(left, right, thr), want, f"wide indel_raw |alphabet|={len(alphabet)} thr={thr} {n}x{m}")
             continue
@@ -376,6 +402,7 @@ def main():
             pad = lambda rr: np.array([r + [-1] * (width - len(r)) for r in rr], dtype=np.int32).reshape(len(rr), width)
             lt = tables.SetTable.from_padded(pad(left), "left", dev, width=width)
             rt = tables.SetTable.from_padded(pad(right), "right", dev, width=width)
+            thr = on_score(thr, lambda t: native.jaccard_raw(native.csr(left), native.csr(right), t, cap=1 << 19))
             want = native.jaccard_raw(native.csr(left), native.csr(right), thr, cap=1 << 19)
             prune = rng.random() < 0.7
             check(grid.jaccard_raw_grid(lt, rt, thr, prune=prune, capacity=rng.choice([64, 4096, 1 << 16]), index=index), want,
@@ -397,6 +424,7 @@ def main():
             dup_some(rng, left, right, 0.1, mutate)
             lt, rt = tables.encode_strings(left, right, dev)
             cp = lambda ss: native.csr([[ord(c) for c in s] for s in ss])
+            thr = on_score(thr, lambda t: native.indel_raw(cp(left), cp(right), t, cap=1 << 18))
             want = native.indel_raw(cp(left), cp(right), thr, cap=1 << 18)
             prune = rng.random() < 0.7
             two_stage = rng.random() < 0.7  # (64-unit tables: the 16-bucket first stage of the histogram filter, or not)
@@ -431,6 +459,7 @@ def main():
                                                  partition=partition)
                 rt = tables.SetTable.from_levels(right, "right", dev, vocabulary, width=width, categories=rcat, category_mode=mode,
                                                  partition=partition)
+                thr = on_score(thr, lambda t: native.levels(False, left, right, t, lcat, rcat, mode, cap=1 << 19))
                 want = native.levels(False, left, right, thr, lcat, rcat, mode, cap=1 << 19)
                 # the inverted-index kernel forced / forbidden / chosen by the library (W <= 32, positive thresholds)
                 index = rng.choice([None, True, True, False] + (["tile"] if width <= 32 else [])) if thr > 0 else None
@@ -462,6 +491,7 @@ def main():
                 dup_some(rng, left, right, 0.1, mutate)
                 li, ls, ri, rs = tables.encode_level_strings(left, right, dev, lcat, rcat, mode, partition=partition)
                 cps = lambda items: [[[ord(c) for c in s] for s in it] for it in items]
+                thr = on_score(thr, lambda t: native.levels(True, cps(left), cps(right), t, lcat, rcat, mode, cap=1 << 18))
                 want = native.levels(True, cps(left), cps(right), thr, lcat, rcat, mode, cap=1 << 18)
                 # multi-word strings: the shared-tile kernel (default) or the round-2 park kernel
                 # (one-word strings: the split path at thresholds >= 0.7, else -- and with park -- the fused park kernel)
