@@ -362,6 +362,45 @@ int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set_table* rig
                              const int32_t* banned_start, const int32_t* banned_j,
                              nsm_hit* out, unsigned long long* out_count, uint64_t* stats, void* stream);
 
+/* Threshold profiles: what a whole ladder of thresholds would do, without the hits (csrc/profile_raw.hip,
+ * profile_levels.hip, score_tally.hpp).  For thresholds t[0] < ... < t[T-1], 1 <= T <= 64, take the hit list of the
+ * matching grid (nsm_*_raw_grid / nsm_*_levels_grid; levels: after the category predicate, without the banned pairs) at
+ * t[0] -- the same pairs and the same doubles, bit for bit.  Then
+ *   pairs[k]       the number of hits with score >= t[k]: the length of the grid's hit list at t[k]
+ *   left_best[i]   the largest score among the hits of the left item with caller id i (left->orig), -1.0 if it has none
+ *   right_best[j]  the same per right caller id
+ * The output is O(left->n + right->n + T) whatever the data.  The call initialises its outputs itself: pairs[0 .. T), and
+ * the entry of every caller id the tables hold (the arrays reach to the largest caller id + 1; other entries stay as
+ * they are).  During the call right_best holds integers; it is valid when the stream has passed the call.
+ * The caller ids of a table (its orig column) must be DISTINCT, as every builder and encoder of this library makes them:
+ * an entry is initialised, written and converted once per table row, so two rows sharing an id would race on it (and
+ * the in-place conversion of right_best would run twice on one word).  This is not checked.
+ * A table without rows (n == 0) is fine as long as its columns are not NULL: the outputs are initialised (pairs to 0, the
+ * other side's entries to -1.0) and no sweep is launched.
+ *   thresholds, n_thresholds  HOST array; T outside 1 .. 64, a NaN, or thresholds not strictly ascending: NSM_E_BADARG
+ *   operands, category_mode, banned_start, banned_j  as for the matching nsm_*_top_k entry, with its table checks
+ *   stats, flags   as for the matching nsm_*_top_k entry.  NSM_FLAG_PRUNE skips a pair only when an upper bound of its
+ *              score is strictly below t[0] (there is no floor); without it every pair is scored.  Same results
+ * Every NSM_E_BADARG is reported before anything is launched.  The sweep is the top-k kernels' with a tally in place of the
+ * per-row lists; counts are integers and bests are maxima, so the results do not depend on scheduling. */
+int nsm_indel_raw_profile(const nsm_str_table* left, const nsm_str_table* right, const double* thresholds /*host*/,
+                          int32_t n_thresholds, uint32_t flags, uint64_t* pairs /*device [T]*/,
+                          double* left_best /*device, one per left caller id*/,
+                          double* right_best /*device, one per right caller id*/, uint64_t* stats /*device [4] or NULL*/,
+                          void* stream);
+int nsm_jaccard_raw_profile(const nsm_set_table* left, const nsm_set_table* right, const double* thresholds,
+                            int32_t n_thresholds, uint32_t flags, uint64_t* pairs, double* left_best, double* right_best,
+                            uint64_t* stats, void* stream);
+int nsm_indel_levels_profile(const nsm_level_items* left, const nsm_str_table* left_strings,
+                             const nsm_level_items* right, const nsm_str_table* right_strings,
+                             const double* thresholds, int32_t n_thresholds, int32_t category_mode, uint32_t flags,
+                             const int32_t* banned_start, const int32_t* banned_j, uint64_t* pairs, double* left_best,
+                             double* right_best, uint64_t* stats, void* stream);
+int nsm_jaccard_levels_profile(const nsm_set_table* left, const nsm_set_table* right, const double* thresholds,
+                               int32_t n_thresholds, int32_t category_mode, uint32_t flags, const int32_t* banned_start,
+                               const int32_t* banned_j, uint64_t* pairs, double* left_best, double* right_best,
+                               uint64_t* stats, void* stream);
+
 /* Destroy the side stream and events the library created for `stream` on the current device.  The caller makes sure no nsm_indel_levels_grid work is still queued on that stream.  Returns 0. */
 int nsm_release(void* stream);
 int nsm_release_all(void); /* the same for every stream of every device */

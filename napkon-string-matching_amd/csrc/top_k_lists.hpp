@@ -10,6 +10,19 @@ namespace nsm {
 
 constexpr int kTopMaxK = 4096;   // largest k (after clamping to the right table's rows)
 
+// add a wave's counters to stats (one atomic per counter)
+__device__ __forceinline__ void wave_add_stats(unsigned long long* __restrict__ stats, const unsigned long long (&st)[4], int lane) {
+  if (stats) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      unsigned long long v = st[c];
+#pragma unroll
+      for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off);
+      if (lane == 0 && v) atomicAdd(stats + c, v);
+    }
+  }
+}
+
 // The lists of the wave's G rows.  Row g's records are list[(row0 + g) k .. + cnt(g)); only this wave reads or writes
 // them, so a workgroup-scope fence orders lane 0's store before the wave's reloads (nothing else is needed).  The rows'
 // state is held "one row per lane" -- lane g of cnt_v is row g's count -- and read with v_readlane: a loop over the rows
@@ -25,8 +38,16 @@ constexpr int kTopMaxK = 4096;   // largest k (after clamping to the right table
 // groups, so the final k-th best representative is never below it.  A candidate that would improve its own group's
 // record comes before a record of the list, hence before (or in place of) the worst one: beats() in front of an offer
 // drops nothing that matters.
+//
+// TopLists is one of the two SINKS the kernels are templates over (the other: ScoreTally, score_tally.hpp).  A sink is
+// opened from the kernel's list arguments plus its own `Extra` kernel argument (nothing here).
 template <bool GROUPED>
 struct TopLists {
+  struct Extra {};
+  __device__ static TopLists open(nsm_hit* list, int32_t* grp, int k, int row0, int lane, const Extra&) {
+    return TopLists{list, grp, k, row0, lane};
+  }
+
   nsm_hit* list;
   int32_t* grp;
   int k;
@@ -143,15 +164,7 @@ struct TopLists {
       for (int q = lane; q < n; q += kWave) out[base + q] = row[q];
       base += n;
     }
-    if (stats) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        unsigned long long v = st[c];
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off);
-        if (lane == 0 && v) atomicAdd(stats + c, v);
-      }
-    }
+    wave_add_stats(stats, st, lane);
   }
 };
 
@@ -215,6 +228,91 @@ static int check_set_tables(const char* who, const nsm_set_table* l, const nsm_s
     set_error("%s: width %d/%d unsupported (both sides 16, 32 or 64)", who, l->width, r->width);
     return NSM_E_BADARG;
   }
+  return 0;
+}
+
+// ---- the table checks of a whole query, shared by the top-k entries and the profile entries (profile_*.hip)
+static int check_raw_str_query(const char* who, const nsm_str_table* left, const nsm_str_table* right) {
+  if (int st = check_str_tables(who, left, right)) return st;
+  if (left->n < 0 || right->n < 0) {
+    set_error("%s: negative row count", who);
+    return NSM_E_BADARG;
+  }
+  if (!left->codes || !left->len || !left->orig || !right->codes || !right->len_start || !right->orig) {
+    set_error("%s: table has a null column (the right table needs len_start)", who);
+    return NSM_E_BADARG;
+  }
+  return 0;
+}
+
+static int check_raw_set_query(const char* who, const nsm_set_table* left, const nsm_set_table* right) {
+  if (int st = check_set_tables(who, left, right)) return st;
+  if (left->n < 0 || right->n < 0) {
+    set_error("%s: negative row count", who);
+    return NSM_E_BADARG;
+  }
+  if (!left->ids || !left->cnt || !left->orig || !right->ids || !right->size_start || !right->orig) {
+    set_error("%s: table has a null column (the right table needs size_start)", who);
+    return NSM_E_BADARG;
+  }
+  return 0;
+}
+
+// category predicate and blacklist of a levels query
+static int check_common(const char* who, int32_t category_mode, bool has_cat, const int32_t* bs, const int32_t* bj) {
+  if (category_mode != NSM_CAT_NONE && category_mode != NSM_CAT_INTERSECT && category_mode != NSM_CAT_INTERSECT_OR_BOTH_EMPTY) {
+    set_error("%s: unknown category_mode %d", who, category_mode);
+    return NSM_E_BADARG;
+  }
+  if (category_mode != NSM_CAT_NONE && !has_cat) {
+    set_error("%s: a category predicate needs `cat` on both sides", who);
+    return NSM_E_BADARG;
+  }
+  if ((bs == nullptr) != (bj == nullptr)) {
+    set_error("%s: banned_start and banned_j go together", who);
+    return NSM_E_BADARG;
+  }
+  return 0;
+}
+
+static int check_levels_str_query(const char* who, const nsm_level_items* left, const nsm_str_table* left_strings,
+                                  const nsm_level_items* right, const nsm_str_table* right_strings, int32_t category_mode,
+                                  const int32_t* banned_start, const int32_t* banned_j) {
+  if (int st = check_str_tables(who, left_strings, right_strings)) return st;
+  if (left->seg || left->seg_start || right->seg || right->seg_start) {
+    set_error("%s: partitioned item tables are not supported (an item must be one row: encode with partition=False)", who);
+    return NSM_E_UNSUPPORTED;
+  }
+  if (left->n < 0 || right->n < 0) {
+    set_error("%s: negative item count", who);
+    return NSM_E_BADARG;
+  }
+  if (!left->first || !left->nlev || !left->orig || !right->first || !right->nlev || !right->orig || !left_strings->codes ||
+      !left_strings->len || !right_strings->codes || !right_strings->len) {
+    set_error("%s: table has a null column", who);
+    return NSM_E_BADARG;
+  }
+  if (int st = check_common(who, category_mode, left->cat && right->cat, banned_start, banned_j)) return st;
+  return 0;
+}
+
+static int check_levels_set_query(const char* who, const nsm_set_table* left, const nsm_set_table* right, int32_t category_mode,
+                                  const int32_t* banned_start, const int32_t* banned_j) {
+  if (int st = check_set_tables(who, left, right)) return st;
+  if (left->seg || left->seg_start || right->seg || right->seg_start) {
+    set_error("%s: partitioned tables are not supported (an item must be one row: encode with partition=False)", who);
+    return NSM_E_UNSUPPORTED;
+  }
+  if (left->n < 0 || right->n < 0) {
+    set_error("%s: negative row count", who);
+    return NSM_E_BADARG;
+  }
+  if (!left->ids || !left->cnt || !left->nlev || !left->plen || !left->orig || !right->ids || !right->cnt || !right->nlev ||
+      !right->plen || !right->orig || left->max_levels < 1 || right->max_levels < 1) {
+    set_error("%s: table has a null column (levels tables need nlev and plen)", who);
+    return NSM_E_BADARG;
+  }
+  if (int st = check_common(who, category_mode, left->cat && right->cat, banned_start, banned_j)) return st;
   return 0;
 }
 

@@ -116,6 +116,10 @@ EXPORTS = (
     "nsm_jaccard_levels_top_k",
     "nsm_indel_raw_top_k_grouped",
     "nsm_jaccard_raw_top_k_grouped",
+    "nsm_indel_raw_profile",
+    "nsm_jaccard_raw_profile",
+    "nsm_indel_levels_profile",
+    "nsm_jaccard_levels_profile",
 )
 
 _lib = None
@@ -172,6 +176,16 @@ def load() -> ctypes.CDLL:
                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.nsm_indel_levels_top_k.argtypes = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable)] + levels_top_k_tail
     lib.nsm_jaccard_levels_top_k.argtypes = [P(NsmSetTable), P(NsmSetTable)] + levels_top_k_tail
+    # thresholds (host), n_thresholds, flags, pairs, left_best, right_best, stats, stream
+    profile_tail = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                    ctypes.c_void_p, ctypes.c_void_p]
+    lib.nsm_indel_raw_profile.argtypes = [P(NsmStrTable), P(NsmStrTable)] + profile_tail
+    lib.nsm_jaccard_raw_profile.argtypes = [P(NsmSetTable), P(NsmSetTable)] + profile_tail
+    # thresholds (host), n_thresholds, category_mode, flags, banned_start, banned_j, pairs, left_best, right_best, stats, stream
+    levels_profile_tail = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.nsm_indel_levels_profile.argtypes = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable)] + levels_profile_tail
+    lib.nsm_jaccard_levels_profile.argtypes = [P(NsmSetTable), P(NsmSetTable)] + levels_profile_tail
     # hits, scratch, capacity, hit_count, n_hint, id_limit, stream
     lib.nsm_sort_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_u64, ctypes.c_void_p, c_u64, ctypes.c_uint32,
                                   ctypes.c_void_p]

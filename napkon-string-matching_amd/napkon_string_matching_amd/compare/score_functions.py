@@ -15,6 +15,9 @@ Same names, call convention and error behaviour as the reference's
   ``groups=`` (one hashable per right item) it keeps the best item of every group and of those the ``k`` best: the
   ``k`` best distinct candidates when the right side lists a candidate under several spellings.
 
+* ``plugin.profile(left_items, right_items, thresholds)`` answers what a whole ladder of thresholds would do -- hit counts
+  per threshold and every item's best score -- without the hits (``grid.ThresholdProfile``).
+
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
 """
@@ -162,6 +165,36 @@ class _IntersectionVsUnion:
         return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
 
 
+    @staticmethod
+    def profile(left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,
+                prune: bool = True) -> grid.ThresholdProfile:
+        """``grid.profile_of_hits(raw_grid(left_items, right_items, thresholds[0]), thresholds, ...)`` without the hits:
+        per threshold the number of pairs scoring at least that, per item its best score (``-1.0``: none at
+        ``thresholds[0]``).  Wide items are routed as ``top_k`` routes them."""
+        from .. import wide
+
+        t = grid.check_thresholds(thresholds)
+        dev = device or _device()
+        l_rows = [list(set_operand(v)) for v in left_items]
+        r_rows = [list(set_operand(v)) for v in right_items]
+        if any(not r for r in l_rows) and any(not r for r in r_rows):
+            raise ZeroDivisionError("division by zero")  # (:13)
+
+        def fast(li, ri):
+            vocab = tables.Vocabulary()
+            ls, rs = [l_rows[k_] for k_ in li], [r_rows[k_] for k_ in ri]
+            width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
+            lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
+            rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
+            return grid.jaccard_raw_profile(lt, rt, t, prune=prune)
+
+        general = lambda li, ri: grid.profile_of_hits(
+            wide.jaccard_any_grid([[l_rows[k_]] for k_ in li], [[r_rows[k_]] for k_ in ri], float(t[0]), raw=True, device=dev),
+            t, len(li), len(ri))
+        return wide.split_profile(wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]), len(l_rows), len(r_rows),
+                                  t, fast, general)
+
+
 class _FuzzyMatch:
     __name__ = "fuzzy_match"
     kind = "strings"
@@ -218,6 +251,30 @@ class _FuzzyMatch:
             wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], threshold, raw=True, device=dev), k,
             sub(ri))
         return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
+
+
+    @staticmethod
+    def profile(left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,
+                prune: bool = True) -> grid.ThresholdProfile:
+        """``grid.profile_of_hits(raw_grid(left_items, right_items, thresholds[0]), thresholds, ...)`` without the hits:
+        per threshold the number of pairs scoring at least that, per item its best score (``-1.0``: none at
+        ``thresholds[0]``) -- at 0.0 every pair counts, which no hit list could hold.  Wide items are routed as ``top_k``
+        routes them."""
+        from .. import wide
+
+        t = grid.check_thresholds(thresholds)
+        dev = device or _device()
+        l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+
+        def fast(li, ri):
+            lt, rt = tables.encode_strings([l_ops[k_] for k_ in li], [r_ops[k_] for k_ in ri], dev)
+            return grid.indel_raw_profile(lt, rt, t, prune=prune)
+
+        general = lambda li, ri: grid.profile_of_hits(
+            wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], float(t[0]), raw=True, device=dev),
+            t, len(li), len(ri))
+        return wide.split_profile(wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]), len(l_ops), len(r_ops),
+                                  t, fast, general)
 
 
 intersection_vs_union = _IntersectionVsUnion()

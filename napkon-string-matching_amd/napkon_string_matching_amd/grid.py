@@ -369,6 +369,154 @@ def jaccard_levels_top_k(left: SetTable, right: SetTable, k: int, threshold: flo
                          category_mode, prune, banned, stats)
 
 
+# ------------------------------------------------------------------------------- threshold profiles
+PROFILE_MAX_THRESHOLDS = 64  # one threshold per lane of the tally (csrc/score_tally.hpp)
+
+
+def check_thresholds(thresholds) -> np.ndarray:
+    """The ladder of a profile as float64: 1 .. 64 numbers, strictly ascending, no NaN -- else ``ValueError``, before any
+    device work."""
+    t = np.array(list(thresholds), dtype=np.float64).reshape(-1)
+    if not 1 <= len(t) <= PROFILE_MAX_THRESHOLDS:
+        raise ValueError(f"a profile takes 1 .. {PROFILE_MAX_THRESHOLDS} thresholds, got {len(t)}")
+    if np.isnan(t).any():
+        raise ValueError("thresholds must not be NaN")
+    if (np.diff(t) <= 0).any():
+        raise ValueError("thresholds must be strictly ascending")
+    return t
+
+
+@dataclass
+class ThresholdProfile:
+    """What a ladder of thresholds would do to one grid, without the hits.  With the grid's hit list at ``thresholds[0]``:
+    ``pairs[k]`` = the number of hits scoring ``>= thresholds[k]`` (the length of the grid's hit list at that threshold),
+    ``left_best[i]`` / ``right_best[j]`` = the item's largest score among the hits, ``-1.0`` for an item without one."""
+
+    thresholds: np.ndarray  # float64, ascending
+    pairs: np.ndarray       # uint64, one per threshold
+    left_best: np.ndarray   # float64, by the caller's left index
+    right_best: np.ndarray  # float64, by the caller's right index
+
+    def matched_left(self) -> np.ndarray:
+        """Per threshold the number of left items with at least one hit at it."""
+        return (self.left_best[None, :] >= self.thresholds[:, None]).sum(axis=1).astype(np.int64)
+
+    def matched_right(self) -> np.ndarray:
+        return (self.right_best[None, :] >= self.thresholds[:, None]).sum(axis=1).astype(np.int64)
+
+
+def profile_of_hits(hits: Hits, thresholds, n_left: int, n_right: int) -> ThresholdProfile:
+    """The definition of a profile, from the hits of a threshold grid run at (or below) ``thresholds[0]``: hits below
+    ``thresholds[0]`` do not count."""
+    t = check_thresholds(thresholds)
+    keep = hits.score >= t[0]
+    score, i, j = hits.score[keep], hits.i[keep], hits.j[keep]
+    # (ascending scores: searchsorted left = number of scores < t[k])
+    pairs = (len(score) - np.searchsorted(np.sort(score), t, side="left")).astype(np.uint64)
+    left_best, right_best = np.full(int(n_left), -1.0), np.full(int(n_right), -1.0)
+    np.maximum.at(left_best, i, score)
+    np.maximum.at(right_best, j, score)
+    return ThresholdProfile(t, pairs, left_best, right_best)
+
+
+def merge_profiles(parts, thresholds, n_left: int, n_right: int) -> ThresholdProfile:
+    """``parts``: (profile of a sub-grid, its left indices, its right indices), the sub-grids disjoint in pairs and all at
+    the same ladder.  Counts add, bests take the maximum."""
+    t = check_thresholds(thresholds)
+    out = ThresholdProfile(t, np.zeros(len(t), np.uint64), np.full(int(n_left), -1.0), np.full(int(n_right), -1.0))
+    for prof, li, ri in parts:
+        if not np.array_equal(prof.thresholds, t):
+            raise ValueError("profiles of different ladders cannot be merged")
+        out.pairs += prof.pairs
+        np.maximum.at(out.left_best, np.asarray(li, dtype=np.int64), prof.left_best)
+        np.maximum.at(out.right_best, np.asarray(ri, dtype=np.int64), prof.right_best)
+    return out
+
+
+def _profile(launch: Callable, t: np.ndarray, left_orig: torch.Tensor, n_left: int, right_orig: torch.Tensor, n_right: int,
+             device, what: str, stats: Optional[list]) -> ThresholdProfile:
+    """Run a profile launch ``launch(thresholds, T, pairs, left_best, right_best, stats, stream)``.  The best arrays go by
+    the tables' caller ids and reach to the largest one; the entry initialises what its tables name, the rest is -1.0."""
+    import ctypes
+
+    dev = _require_gpu(device)
+    ids_l, ids_r = _left_id_limit(left_orig, n_left), _left_id_limit(right_orig, n_right)
+    pairs = torch.zeros(len(t), dtype=torch.int64, device=dev)
+    left_best = torch.full((max(1, ids_l),), -1.0, dtype=torch.float64, device=dev)
+    right_best = torch.full((max(1, ids_r),), -1.0, dtype=torch.float64, device=dev)
+    st = torch.zeros(4, dtype=torch.int64, device=dev)
+    ladder = (ctypes.c_double * len(t))(*t.tolist())
+    _lib.check(launch(ladder, len(t), pairs.data_ptr(), left_best.data_ptr(), right_best.data_ptr(), st.data_ptr(),
+                      torch.cuda.current_stream(dev).cuda_stream), what)
+    if stats is not None:
+        stats[:] = [int(v) for v in st.tolist()]
+    return ThresholdProfile(t, pairs.cpu().numpy().view(np.uint64), left_best[:ids_l].cpu().numpy(),
+                            right_best[:ids_r].cpu().numpy())
+
+
+def indel_raw_profile(left: StrTable, right: StrTable, thresholds, prune: bool = True,
+                      stats: Optional[list] = None) -> ThresholdProfile:
+    """``profile_of_hits(indel_raw_grid(left, right, thresholds[0]), thresholds, ...)`` without the hits, in one sweep of
+    ``nsm_indel_raw_profile`` (the top-k kernel with a tally in place of its lists).  ``stats`` as for ``indel_raw_top_k``."""
+    t = check_thresholds(thresholds)
+    lib = _lib.load()
+    ls, rs = left.struct(), right.struct()
+    flags = _lib.FLAG_PRUNE if prune else 0
+    return _profile(lambda lad, n, pairs, lb, rb, st, stream: lib.nsm_indel_raw_profile(ls, rs, lad, n, flags, pairs, lb, rb, st, stream),
+                    t, left.orig, left.n, right.orig, right.n, left.codes.device, "nsm_indel_raw_profile", stats)
+
+
+def jaccard_raw_profile(left: SetTable, right: SetTable, thresholds, prune: bool = True,
+                        stats: Optional[list] = None) -> ThresholdProfile:
+    """``intersection_vs_union`` counterpart of ``indel_raw_profile``; preconditions as for ``jaccard_raw_top_k``."""
+    t = check_thresholds(thresholds)
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    if left.has_empty and right.has_empty:
+        raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
+    lib = _lib.load()
+    ls, rs = left.struct(), right.struct()
+    flags = _lib.FLAG_PRUNE if prune else 0
+    return _profile(lambda lad, n, pairs, lb, rb, st, stream: lib.nsm_jaccard_raw_profile(ls, rs, lad, n, flags, pairs, lb, rb, st, stream),
+                    t, left.orig, left.n, right.orig, right.n, left.ids.device, "nsm_jaccard_raw_profile", stats)
+
+
+def _levels_profile(entry: str, tables: tuple, left, right, device, t: np.ndarray, category_mode: int, prune: bool, banned,
+                    stats: Optional[list]) -> ThresholdProfile:
+    fn = getattr(_lib.load(), entry)
+    if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
+        category_mode = left.category_mode
+    structs = [tab.struct() for tab in tables]
+    flags = _lib.FLAG_PRUNE if prune else 0
+    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), device)
+    ptr = lambda x: 0 if x is None else x.data_ptr()
+    return _profile(lambda lad, n, pairs, lb, rb, st, stream: fn(*structs, lad, n, int(category_mode), flags, ptr(bs), ptr(bj),
+                                                                 pairs, lb, rb, st, stream),
+                    t, left.orig, left.n, right.orig, right.n, device, entry, stats)
+
+
+def indel_levels_profile(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, thresholds,
+                         category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
+                         stats: Optional[list] = None) -> ThresholdProfile:
+    """The profile of ``indel_levels_grid(...)`` without the ``banned`` pairs (``indel_levels_top_k``'s arguments and
+    preconditions: tables encoded with ``partition=False``)."""
+    t = check_thresholds(thresholds)
+    return _levels_profile("nsm_indel_levels_profile", (left, left_strings, right, right_strings), left, right,
+                           left.first.device, t, category_mode, prune, banned, stats)
+
+
+def jaccard_levels_profile(left: SetTable, right: SetTable, thresholds, category_mode: int = _lib.CAT_NONE, prune: bool = True,
+                           banned=None, stats: Optional[list] = None) -> ThresholdProfile:
+    """``intersection_vs_union`` counterpart of ``indel_levels_profile`` (``jaccard_levels_top_k``'s preconditions)."""
+    t = check_thresholds(thresholds)
+    if left.nlev is None or right.nlev is None:
+        raise ValueError("levels profile needs tables built with SetTable.from_levels")
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    return _levels_profile("nsm_jaccard_levels_profile", (left, right), left, right, left.ids.device, t, category_mode, prune,
+                           banned, stats)
+
+
 # ------------------------------------------------------------------------------- levels grids
 def jaccard_levels_grid(
     left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True,

@@ -23,6 +23,7 @@ import logging
 from contextlib import contextmanager
 from hashlib import md5
 from pathlib import Path
+from types import SimpleNamespace
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -419,6 +420,41 @@ class ComparableData:
         result.sort_by_score()
         return result
 
+    def compare_profile(self, other, thresholds, existing_mappings_whitelist=None, existing_mappings_blacklist=None,
+                        compare_column: str = None, identifier_column_left: Optional[str] = None,
+                        identifier_column_right: Optional[str] = None, **kwargs) -> grid.ThresholdProfile:
+        """What ``compare(other, score_threshold=t, ...)`` would return for every ``t`` of ``thresholds`` (1 .. 64, strictly
+        ascending), without the pairs: ``pairs[k] == len(compare(score_threshold=thresholds[k]))`` (no cache involved), and
+        per item -- by position in the compared frames, i.e. after ``dropna`` on the compare column and the whitelist --
+        its best score among the pairs at ``thresholds[0]`` (``-1.0``: none).  Takes the keyword arguments of ``compare``
+        (``score_func``, ``left_name``, ``filter_categories``, ...; thresholds and cache arguments are ignored) and runs the
+        same prelude: whitelist, blacklist, categories, the reference's exceptions in pair order, zero-level pairs scoring
+        0.  Categories and blacklist run in the kernel (``nsm_*_levels_profile``), so more than 64 category labels are a
+        ``NotImplementedError``, as for ``top_k``; so is a sharded run."""
+        t = grid.check_thresholds(thresholds)
+        if distributed.world()[1] > 1:
+            raise NotImplementedError("compare_profile on more than one rank (sharded profiles are not implemented)")
+        for name in ("score_threshold", "cached", "cache_threshold", "cache_dir", "top_k"):
+            kwargs.pop(name, None)
+        pre = self._compare_prelude(
+            other, existing_mappings_whitelist, existing_mappings_blacklist, kwargs.get("score_func"), compare_column,
+            kwargs.get("category_column", "Category"), kwargs.get("left_name"), kwargs.get("right_name"),
+            kwargs.get("filter_categories", False), identifier_column_left, identifier_column_right, per_item="a threshold profile")
+        parts = []
+        if pre.keep_l.size and pre.keep_r.size:
+            on_device = pre.cats is not None
+            parts.append((_levels_grid(
+                pre.plugin, [pre.levels_l[k] for k in pre.keep_l], [pre.levels_r[k] for k in pre.keep_r], float(t[0]),
+                pre.cats.left_mask[pre.keep_l] if on_device else None, pre.cats.right_mask[pre.keep_r] if on_device else None,
+                pre.cats.mode if on_device else _lib.CAT_NONE, banned=_local_banned(pre.banned, pre.keep_l, pre.keep_r),
+                profile=t), pre.keep_l, pre.keep_r))
+        if pre.extra_hits:  # zero-level x zero-level pairs score 0
+            ei = np.array([p[0] for p in pre.extra_hits], dtype=np.int32)
+            ej = np.array([p[1] for p in pre.extra_hits], dtype=np.int32)
+            parts.append((grid.profile_of_hits(grid.Hits(np.zeros(len(ei)), ei, ej), t, pre.n_l, pre.n_r), np.arange(pre.n_l),
+                          np.arange(pre.n_r)))
+        return grid.merge_profiles(parts, t, pre.n_l, pre.n_r)
+
     def _hash_compare_args(self, other, whitelist, blacklist, compare_column, cache_threshold, kwargs, top_k=None) -> str:
         other_csv = other.to_csv() if hasattr(other, "to_csv") else pd.DataFrame(other).to_csv(index=False)
         parts = [
@@ -433,28 +469,13 @@ class ComparableData:
             parts.append(f"top_k={int(top_k)}")
         return md5("\x1f".join(parts).encode("utf-8"), usedforsecurity=False).hexdigest()
 
-    def gen_comparable(
-        self,
-        right,
-        existing_mappings_whitelist=None,
-        existing_mappings_blacklist=None,
-        score_func: str = None,
-        compare_column: str = None,
-        category_column: str = "Category",
-        score_threshold: float = 0.1,
-        left_name: str = None,
-        right_name: str = None,
-        filter_categories: bool = False,
-        identifier_column_left: Optional[str] = None,
-        identifier_column_right: Optional[str] = None,
-        *args,
-        top_k: Optional[int] = None,
-        **kwargs,
-    ) -> Comparable:
-        """:133-246 (steps 1-12 of SURVEY.md 3.2), the per-pair part on the GPU.  ``top_k``: per left item only the
-        first ``top_k`` pairs (score descending, right item ascending) of what would be returned (``compare``)."""
-        if top_k is not None:
-            top_k = grid.check_k(top_k)
+    def _compare_prelude(self, right, existing_mappings_whitelist, existing_mappings_blacklist, score_func, compare_column,
+                         category_column, left_name, right_name, filter_categories, identifier_column_left,
+                         identifier_column_right, per_item: Optional[str] = None) -> SimpleNamespace:
+        """Everything of :133-222 that comes before the scores, shared by ``gen_comparable`` and ``compare_profile``:
+        whitelist, levels, blacklist as position pairs, categories, the reference's per-pair exceptions in pair order, the
+        zero-level pairs that score 0, and the items the device grid takes.  ``per_item``: the name of a query whose
+        category predicate must run on the device (``NotImplementedError`` beyond 64 labels)."""
         plugin = getattr(score_functions, score_func)  # AttributeError for an unknown name (:150)
         whitelist = _as_mapping(existing_mappings_whitelist)
         blacklist = _as_mapping(existing_mappings_blacklist)
@@ -493,9 +514,9 @@ class ComparableData:
                 raise IndexError("single positional indexer is out-of-bounds")  # df.iloc[0] at :465
             cl, cr = list(lf[category_column]), list(rf[category_column])
             cats = _Categories(cl, cr, cl[first[0]], cr[first[1]])
-            if top_k is not None and not cats.on_device:
-                raise NotImplementedError("top_k with more than 64 distinct category labels (the predicate must run on the "
-                                          "device, where each item keeps its list)")
+            if per_item is not None and not cats.on_device:
+                raise NotImplementedError(f"{per_item} with more than 64 distinct category labels (the predicate must run on "
+                                          "the device, where each item keeps its list)")
         elif n_l == 0 or n_r == 0:
             # the reference's blacklist step indexes the cross join with a list of booleans (:549-552); for
             # an EMPTY cross join that list is empty, pandas reads it as "no columns", and :223-232 then
@@ -516,6 +537,39 @@ class ComparableData:
         # ---- device grid over the items that have at least one level
         keep_l = np.flatnonzero(nlev_l > 0)
         keep_r = np.flatnonzero(nlev_r > 0)
+        return SimpleNamespace(plugin=plugin, lf=lf, rf=rf, lp=lp, rp=rp, n_l=n_l, n_r=n_r, levels_l=levels_l, levels_r=levels_r,
+                               argument_l=argument_l, argument_r=argument_r, banned=banned, cats=cats, nlev_l=nlev_l,
+                               nlev_r=nlev_r, extra_hits=extra_hits, keep_l=keep_l, keep_r=keep_r)
+
+    def gen_comparable(
+        self,
+        right,
+        existing_mappings_whitelist=None,
+        existing_mappings_blacklist=None,
+        score_func: str = None,
+        compare_column: str = None,
+        category_column: str = "Category",
+        score_threshold: float = 0.1,
+        left_name: str = None,
+        right_name: str = None,
+        filter_categories: bool = False,
+        identifier_column_left: Optional[str] = None,
+        identifier_column_right: Optional[str] = None,
+        *args,
+        top_k: Optional[int] = None,
+        **kwargs,
+    ) -> Comparable:
+        """:133-246 (steps 1-12 of SURVEY.md 3.2), the per-pair part on the GPU.  ``top_k``: per left item only the
+        first ``top_k`` pairs (score descending, right item ascending) of what would be returned (``compare``)."""
+        if top_k is not None:
+            top_k = grid.check_k(top_k)
+        pre = self._compare_prelude(right, existing_mappings_whitelist, existing_mappings_blacklist, score_func, compare_column,
+                                    category_column, left_name, right_name, filter_categories, identifier_column_left,
+                                    identifier_column_right, per_item=None if top_k is None else "top_k")
+        plugin, lf, rf, lp, rp, n_l, n_r = pre.plugin, pre.lf, pre.rf, pre.lp, pre.rp, pre.n_l, pre.n_r
+        levels_l, levels_r, argument_l, argument_r = pre.levels_l, pre.levels_r, pre.argument_l, pre.argument_r
+        banned, cats, nlev_l, nlev_r, extra_hits, keep_l, keep_r = (pre.banned, pre.cats, pre.nlev_l, pre.nlev_r, pre.extra_hits,
+                                                                     pre.keep_l, pre.keep_r)
         rank, world_size = distributed.world()
         if world_size > 1:  # left rows block-sharded over the ranks, right side replicated
             row_lo, row_hi = distributed.shard_bounds(n_l, rank, world_size)
@@ -721,12 +775,14 @@ def _may_be_wide_sets(*sides) -> bool:
 
 
 def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, defer=False, top_k=None,
-                         banned=None):
+                         banned=None, profile=None):
     """The suffix-nested fast layout of both sides + ``nsm_jaccard_levels_grid``; raises ``tables.IrregularLevels`` when an
     item does not fit it.  ``top_k``: ``nsm_jaccard_levels_top_k`` instead, without the ``banned`` pairs (tables without a
-    category partition and without an inverted index)."""
-    part = tables.partition_allowed(cat_mode, cat_l, cat_r) if top_k is None else False
-    index = None if top_k is None else False
+    category partition and without an inverted index).  ``profile`` (a ladder of thresholds): ``nsm_jaccard_levels_profile``
+    on the same tables."""
+    per_item = top_k is not None or profile is not None
+    part = False if per_item else tables.partition_allowed(cat_mode, cat_l, cat_r)
+    index = False if per_item else None
     memo = ComparableData._item_memo
     if memo is not None:
         # inside item_memo(): one vocabulary for the whole run, every item encoded once (tables.LevelPool,
@@ -754,6 +810,8 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
                                          category_mode=cat_mode, partition=part, index=index)
     if len(vocab) >= 1 << 25:
         raise NotImplementedError("vocabulary of 2^25 or more distinct tokens")
+    if profile is not None:
+        return grid.jaccard_levels_profile(lt, rt, profile, category_mode=cat_mode, banned=banned)
     if top_k is not None:
         return grid.jaccard_levels_top_k(lt, rt, top_k, threshold, category_mode=cat_mode, banned=banned)
     # the library picks the inverted-index kernel from the threshold alone (it cannot see the vocabulary); the host
@@ -764,7 +822,7 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
 
 
 def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_lib.CAT_NONE, defer: bool = False, top_k=None,
-                 banned=None):
+                 banned=None, profile=None):
     """Encode both sides' levels for ``plugin`` and run the levels grid on the current device.  ``defer``: when the
     whole grid goes through ONE fast kernel call, return its hits still on the device (``grid.PendingHits``: the sharded
     ``gen_comparable`` exchanges them without a host detour); grids that are split (wide / irregular items) return
@@ -774,7 +832,11 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
     without the ``banned`` pairs ((left, right) positions in these lists, or None); ``defer`` is then ignored.  Items the
     fast kernels take go through ``nsm_*_levels_top_k`` (tables without a category partition or an inverted index: an item
     must stay one row to keep one list); wide or irregular items through the general kernels at the threshold, cut per
-    item on the host; the parts are disjoint in j for every i, so the per-item selection over their union is the answer."""
+    item on the host; the parts are disjoint in j for every i, so the per-item selection over their union is the answer.
+
+    ``profile`` (a validated ladder, ``threshold`` its first entry): the grid's ``grid.ThresholdProfile`` without the
+    ``banned`` pairs instead of its hits, routed like a top-k query -- ``nsm_*_levels_profile`` for the items the fast
+    kernels take, ``grid.profile_of_hits`` of the general kernels' hits for the rest, merged."""
     import torch
 
     if not torch.cuda.is_available():
@@ -788,6 +850,9 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
 
     def split_grid(split, fast, general):
         """The parts of a split grid, merged; a top-k query cuts the general parts and the merged result per item."""
+        if profile is not None:
+            tally = lambda li, ri: grid.profile_of_hits(_drop_banned(general(li, ri), banned, li, ri), profile, len(li), len(ri))
+            return wide.split_profile(split, len(levels_l), len(levels_r), profile, fast, tally)
         if top_k is None:
             return wide.split_grid(split[0], split[1], fast, general)
         cut_general = lambda li, ri: grid.select_top_k(_drop_banned(general(li, ri), banned, li, ri), top_k)
@@ -799,7 +864,8 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
             # items of more than 64 distinct tokens / more than 64 levels / levels that are not suffix-nested leave the fast
             # path (wide.py: general kernel, every step's level sets scored on their own); the rest is scored as always
             fast = lambda li, ri: _levels_grid(plugin, sub(levels_l, li), sub(levels_r, ri), threshold, cut(cat_l, li),
-                                               cut(cat_r, ri), cat_mode, top_k=top_k, banned=_restrict_banned(banned, li, ri))
+                                               cut(cat_r, ri), cat_mode, top_k=top_k, banned=_restrict_banned(banned, li, ri),
+                                               profile=profile)
             general = lambda li, ri: wide.jaccard_any_grid(
                 [as_set_levels(levels_l[k]) for k in li], [as_set_levels(levels_r[k]) for k in ri], threshold, cut(cat_l, li),
                 cut(cat_r, ri), cat_mode, device=dev)
@@ -811,7 +877,7 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
             return split_route(split)
         try:
             return _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev,
-                                        defer and top_k is None, top_k, banned)
+                                        defer and top_k is None, top_k, banned, profile)
         except tables.IrregularLevels:
             # the reference scores whatever its tokenizer yields per level (:283-299): find the items the nested layout
             # cannot hold and route only them
@@ -825,6 +891,10 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
     ops_l, ops_r = prep(levels_l), prep(levels_r)
 
     def fast(li, ri, defer=False):
+        if profile is not None:
+            a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
+                                                     partition=False)
+            return grid.indel_levels_profile(a, b, c, d, profile, category_mode=cat_mode, banned=_restrict_banned(banned, li, ri))
         if top_k is None:
             a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode)
             return grid.indel_levels_grid(a, b, c, d, threshold, category_mode=cat_mode, defer=defer)

@@ -76,6 +76,28 @@ def split_grid(wide_l: np.ndarray, wide_r: np.ndarray, fast: Callable, general: 
     return merge(parts)
 
 
+def split_profile(split, n_left: int, n_right: int, thresholds, fast: Callable, general: Callable) -> grid.ThresholdProfile:
+    """The threshold profile of a grid that ``split`` ((wide_l, wide_r) or None) cuts as ``split_grid`` does: ``fast`` /
+    ``general`` return the ``grid.ThresholdProfile`` of a sub-grid, indexed relative to the index lists.  The parts are
+    disjoint in pairs: counts add, bests take the maximum (``grid.merge_profiles``)."""
+    if split is None:
+        if n_left and n_right:
+            return fast(range(n_left), range(n_right))
+        return grid.merge_profiles([], thresholds, n_left, n_right)
+    wide_l, wide_r = split
+    all_r = np.arange(len(wide_r))
+    reg_l, reg_r = np.flatnonzero(~wide_l), np.flatnonzero(~wide_r)
+    irr_l, irr_r = np.flatnonzero(wide_l), np.flatnonzero(wide_r)
+    parts = []
+    if len(reg_l) and len(reg_r):
+        parts.append((fast(reg_l, reg_r), reg_l, reg_r))
+    if len(irr_l) and len(all_r):
+        parts.append((general(irr_l, all_r), irr_l, all_r))
+    if len(reg_l) and len(irr_r):
+        parts.append((general(reg_l, irr_r), reg_l, irr_r))
+    return grid.merge_profiles(parts, thresholds, n_left, n_right)
+
+
 # ------------------------------------------------------------------------------------------------ strings
 def wide_string_items(items_l: Sequence[Sequence[str]], items_r: Sequence[Sequence[str]]):
     """Which items must leave the fast fuzzy path: a level string longer than 512 code units, or a code unit outside the
