@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "nsm_hip.h"
 
 namespace nsm {
@@ -14,6 +16,35 @@ constexpr uint8_t kNever = 255;      // "no count can reach the threshold"
 
 void set_error(const char* fmt, ...);
 int hip_status(hipError_t err, const char* what);
+
+// Host-side dispatch on a run-time property the kernels are templates over: f(tag) with the tag's ::value as the
+// template argument, one spelled-out launch per kernel family.  The entries' checks have already refused any other value.
+//   by_grouped: std::true_type for a grouped top-k query, std::false_type otherwise
+//   by_stride:  K = 1, 2, 4, 8 words per string row for a stride of 64, 128, 256, 512 code units
+//   by_width:   W = 16, 32, 64 ids per set row
+template <class F>
+static int by_grouped(bool grouped, F&& f) {
+  return grouped ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <class F>
+static int by_stride(int stride, F&& f) {
+  switch (stride) {
+    case 64: return f(std::integral_constant<int, 1>{});
+    case 128: return f(std::integral_constant<int, 2>{});
+    case 256: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
+template <class F>
+static int by_width(int width, F&& f) {
+  switch (width) {
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
+}
 
 // The posting-entry format a table declares (nsm_hip.h: post_format / post_row_bits) must be one the kernels can decode for
 // this many rows of this width: a struct filled for an older ABI, or by hand, would otherwise send them out of bounds.

@@ -66,12 +66,10 @@ extern "C" int nsm_indel_levels_profile(const nsm_level_items* left, const nsm_s
   const hipStream_t s = static_cast<hipStream_t>(stream);
   return run_profile(
       thresholds, n_thresholds, left->orig, left->n, right->orig, right->n, pairs, left_best, right_best, s, [&](const TallyOut& o) {
-        switch (left_strings->stride) {
-          case 64: return dispatch_indel_levels_profile<1>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o, st64, s);
-          case 128: return dispatch_indel_levels_profile<2>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o, st64, s);
-          case 256: return dispatch_indel_levels_profile<4>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o, st64, s);
-          default: return dispatch_indel_levels_profile<8>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o, st64, s);
-        }
+        return by_stride(left_strings->stride, [&](auto kc) {
+          return dispatch_indel_levels_profile<decltype(kc)::value>(prune, left, left_strings, right, right_strings, banned_start,
+                                                                    banned_j, p, o, st64, s);
+        });
       });
 }
 
@@ -100,10 +98,9 @@ extern "C" int nsm_jaccard_levels_profile(const nsm_set_table* left, const nsm_s
   const hipStream_t s = static_cast<hipStream_t>(stream);
   return run_profile(thresholds, n_thresholds, left->orig, left->n, right->orig, right->n, pairs, left_best, right_best, s,
                      [&](const TallyOut& o) {
-                       switch (left->width) {
-                         case 16: return dispatch_jaccard_levels_profile<16>(prune, left, right, banned_start, banned_j, p, o, st64, s);
-                         case 32: return dispatch_jaccard_levels_profile<32>(prune, left, right, banned_start, banned_j, p, o, st64, s);
-                         default: return dispatch_jaccard_levels_profile<64>(prune, left, right, banned_start, banned_j, p, o, st64, s);
-                       }
+                       return by_width(left->width, [&](auto wc) {
+                         return dispatch_jaccard_levels_profile<decltype(wc)::value>(prune, left, right, banned_start, banned_j, p, o,
+                                                                                     st64, s);
+                       });
                      });
 }

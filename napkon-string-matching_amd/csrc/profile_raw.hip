@@ -77,12 +77,9 @@ extern "C" int nsm_indel_raw_profile(const nsm_str_table* left, const nsm_str_ta
   const hipStream_t s = static_cast<hipStream_t>(stream);
   return run_profile(thresholds, n_thresholds, left->orig, left->n, right->orig, right->n, pairs, left_best, right_best, s,
                      [&](const TallyOut& o) {
-                       switch (left->stride) {
-                         case 64: return dispatch_indel_profile<1>(prune, hist, left, right, p, o, st64, s);
-                         case 128: return dispatch_indel_profile<2>(prune, hist, left, right, p, o, st64, s);
-                         case 256: return dispatch_indel_profile<4>(prune, hist, left, right, p, o, st64, s);
-                         default: return dispatch_indel_profile<8>(prune, hist, left, right, p, o, st64, s);
-                       }
+                       return by_stride(left->stride, [&](auto kc) {
+                         return dispatch_indel_profile<decltype(kc)::value>(prune, hist, left, right, p, o, st64, s);
+                       });
                      });
 }
 
@@ -107,10 +104,8 @@ extern "C" int nsm_jaccard_raw_profile(const nsm_set_table* left, const nsm_set_
   const hipStream_t s = static_cast<hipStream_t>(stream);
   return run_profile(thresholds, n_thresholds, left->orig, left->n, right->orig, right->n, pairs, left_best, right_best, s,
                      [&](const TallyOut& o) {
-                       switch (left->width) {
-                         case 16: return dispatch_jaccard_profile<16>(prune, left, right, p, o, st64, s);
-                         case 32: return dispatch_jaccard_profile<32>(prune, left, right, p, o, st64, s);
-                         default: return dispatch_jaccard_profile<64>(prune, left, right, p, o, st64, s);
-                       }
+                       return by_width(left->width, [&](auto wc) {
+                         return dispatch_jaccard_profile<decltype(wc)::value>(prune, left, right, p, o, st64, s);
+                       });
                      });
 }

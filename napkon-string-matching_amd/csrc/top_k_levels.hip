@@ -92,14 +92,9 @@ extern "C" int nsm_indel_levels_top_k(const nsm_level_items* left, const nsm_str
   const bool prune = (flags & NSM_FLAG_PRUNE) != 0;
   TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
   if (int st = o.sc.alloc(left->n, keff, false)) return st;
-  int st = 0;
-  switch (left_strings->stride) {
-    case 64: st = dispatch_indel_levels<1>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
-    case 128: st = dispatch_indel_levels<2>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
-    case 256: st = dispatch_indel_levels<4>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
-    default: st = dispatch_indel_levels<8>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o); break;
-  }
-  return o.sc.release(st);
+  return o.sc.release(by_stride(left_strings->stride, [&](auto kc) {
+    return dispatch_indel_levels<decltype(kc)::value>(prune, left, left_strings, right, right_strings, banned_start, banned_j, p, o);
+  }));
 }
 
 extern "C" int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set_table* right, double threshold, int32_t k,
@@ -128,11 +123,7 @@ extern "C" int nsm_jaccard_levels_top_k(const nsm_set_table* left, const nsm_set
   const bool prune = (flags & NSM_FLAG_PRUNE) != 0;
   TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
   if (int st = o.sc.alloc(left->n, keff, false)) return st;
-  int st = 0;
-  switch (left->width) {
-    case 16: st = dispatch_jaccard_levels<16>(prune, left, right, banned_start, banned_j, p, o); break;
-    case 32: st = dispatch_jaccard_levels<32>(prune, left, right, banned_start, banned_j, p, o); break;
-    default: st = dispatch_jaccard_levels<64>(prune, left, right, banned_start, banned_j, p, o); break;
-  }
-  return o.sc.release(st);
+  return o.sc.release(by_width(left->width, [&](auto wc) {
+    return dispatch_jaccard_levels<decltype(wc)::value>(prune, left, right, banned_start, banned_j, p, o);
+  }));
 }

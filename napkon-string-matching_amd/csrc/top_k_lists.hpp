@@ -4,8 +4,6 @@
 #pragma once
 #include "nsm_common.hpp"
 
-#include <type_traits>
-
 namespace nsm {
 
 constexpr int kTopMaxK = 4096;   // largest k (after clamping to the right table's rows)
@@ -199,12 +197,6 @@ struct TopOut {
   unsigned long long* out_count;
   unsigned long long* stats;
 };
-
-// f(std::true_type) for a grouped query, f(std::false_type) otherwise: one spelled-out launch per kernel
-template <class F>
-static int by_grouped(bool grouped, F&& f) {
-  return grouped ? f(std::true_type{}) : f(std::false_type{});
-}
 
 // Both string tables of a query: equal strides, a stride the kernels have, equal alphabets of at most 255 symbols.
 static int check_str_tables(const char* who, const nsm_str_table* l, const nsm_str_table* r) {

@@ -107,14 +107,9 @@ static int indel_raw_top_k(const char* who, bool grouped, const nsm_str_table* l
   TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
   if (int st = o.sc.alloc(left->n, keff, grouped)) return st;
   const int32_t* rg = grouped ? right_group : nullptr;
-  int st = 0;
-  switch (left->stride) {
-    case 64: st = dispatch_indel<1>(prune, hist, left, right, rg, p, o); break;
-    case 128: st = dispatch_indel<2>(prune, hist, left, right, rg, p, o); break;
-    case 256: st = dispatch_indel<4>(prune, hist, left, right, rg, p, o); break;
-    default: st = dispatch_indel<8>(prune, hist, left, right, rg, p, o); break;
-  }
-  return o.sc.release(st);
+  return o.sc.release(by_stride(left->stride, [&](auto kc) {
+    return dispatch_indel<decltype(kc)::value>(prune, hist, left, right, rg, p, o);
+  }));
 }
 
 static int jaccard_raw_top_k(const char* who, bool grouped, const nsm_set_table* left, const nsm_set_table* right,
@@ -134,13 +129,9 @@ static int jaccard_raw_top_k(const char* who, bool grouped, const nsm_set_table*
   TopOut o{{static_cast<hipStream_t>(stream)}, out, out_count, reinterpret_cast<unsigned long long*>(stats)};
   if (int st = o.sc.alloc(left->n, keff, grouped)) return st;
   const int32_t* rg = grouped ? right_group : nullptr;
-  int st = 0;
-  switch (left->width) {
-    case 16: st = dispatch_jaccard<16>(prune, left, right, rg, p, o); break;
-    case 32: st = dispatch_jaccard<32>(prune, left, right, rg, p, o); break;
-    default: st = dispatch_jaccard<64>(prune, left, right, rg, p, o); break;
-  }
-  return o.sc.release(st);
+  return o.sc.release(by_width(left->width, [&](auto wc) {
+    return dispatch_jaccard<decltype(wc)::value>(prune, left, right, rg, p, o);
+  }));
 }
 
 }  // namespace nsm
