@@ -19,6 +19,8 @@
  *                            drop_duplicates(subset="Id") + limit (terminology/mesh.py:207-220)
  *   nsm_*_levels_top_k       the levels grids (compare_terms, categories, blacklist) when only the k best candidates of each
  *                            left item are wanted (types/comparable_data.py:195-243 followed by a per-item rank cut)
+ *   nsm_*_pairs              the same score_funcs / compare_terms for a caller's LIST of (i, j) pairs, one score per record
+ *                            (compare/score_functions.py:6-27, types/comparable_data.py:248-265; rapidfuzz's process.cpdist)
  *   nsm_sort_hits            Comparable.sort_by_score (types/comparable.py:69-70), made deterministic:
  *                            (score descending, i ascending, j ascending)
  *
@@ -400,6 +402,48 @@ int nsm_jaccard_levels_profile(const nsm_set_table* left, const nsm_set_table* r
                                int32_t n_thresholds, int32_t category_mode, uint32_t flags, const int32_t* banned_start,
                                const int32_t* banned_j, uint64_t* pairs, double* left_best, double* right_best,
                                uint64_t* stats, void* stream);
+
+/* Listed pairs (ABI 5, additive; csrc/pairs.hip): the score of every record of a caller's list, written in place --
+ * rapidfuzz's process.cpdist beside extract (nsm_*_top_k) and the threshold grids.  It stands in for one `score_func(a, b)`
+ * / `compare_terms(a, b)` call per listed pair (compare/score_functions.py:6-27, types/comparable_data.py:248-265): the
+ * scores of a validated mapping, of a whitelist, of another score function's hits.  O(n_pairs) in and out.
+ *   pairs      device, n_pairs records.  pairs[p].i and pairs[p].j are CALLER ids -- the values of the tables' `orig` -- and
+ *              are only read; the call writes pairs[p].score and nothing else.  The order is the caller's, duplicates are
+ *              fine (every record is scored on its own), and the records of any nsm_*_grid / nsm_*_top_k call can be handed
+ *              straight back in.  May be NULL only when n_pairs == 0
+ *   left_row, left_ids    device int32 [left_ids]: left_row[id] = the LEFT table's row (levels Indel: the item row of
+ *              `left`) of caller id `id`, or -1 for none -- the inverse of `orig`, which the sorted tables cannot supply
+ *              themselves; caller-owned like every other column.  May be NULL only when left_ids == 0
+ *   right_row, right_ids  the same for the right table
+ * The score is the double the matching nsm_*_grid reports for the pair, bit for bit (the RAW Indel ratio, the RAW Jaccard
+ * quotient, the levels sums over steps 1 .. max(Ll, Lr) accumulated in that order).  There is no threshold, no category
+ * predicate, no blacklist and no pruning: the caller has decided which pairs it wants.  An empty string against anything
+ * scores 0.0, as in the grids.
+ * "No score" is -1.0 (the profiles' "none"), written for: an id outside [0, ids); an id whose row is -1 (or not a row of
+ * the table); a RAW Jaccard pair of two empty sets; a levels pair in which either item has zero levels; a levels Jaccard
+ * pair that visits an empty-vs-empty level.  The last three are what a host resolves before a grid launch (the reference's
+ * ZeroDivisionError, IndexError, or the score 0 of two level-less items).
+ * Checks, all before the first HIP call, in this order: a null table, `pairs` (with n_pairs > 0) or row map (with ids > 0):
+ * NSM_E_BADARG; a negative left_ids / right_ids: NSM_E_BADARG; strides that differ or are not 64 / 128 / 256 / 512:
+ * NSM_E_UNSUPPORTED; alphabets that differ or exceed 255, widths that differ or are not 16 / 32 / 64: NSM_E_BADARG;
+ * partitioned tables (seg / seg_start; an item must be one row, as for nsm_*_top_k): NSM_E_UNSUPPORTED; a levels set
+ * table without nlev / plen (or max_levels < 1): NSM_E_BADARG; a negative n: NSM_E_BADARG; a table WITH rows that lacks a
+ * column the kernels read (codes, len; first, nlev; ids, cnt): NSM_E_BADARG.  Then n_pairs == 0 returns 0 without a launch.
+ * A table with n == 0 is fine (its columns may be NULL): every record gets -1.0.  len_start, size_start, hist, hist16, sig,
+ * sig2, filt, cat, orig and post are not read and may be NULL.  The entries allocate no device memory, launch one kernel
+ * on `stream` and can be captured. */
+int nsm_indel_raw_pairs(const nsm_str_table* left, const nsm_str_table* right,
+                        const int32_t* left_row /*device*/, int32_t left_ids, const int32_t* right_row /*device*/,
+                        int32_t right_ids, nsm_hit* pairs /*device, in: i, j; out: score*/, uint64_t n_pairs, void* stream);
+int nsm_jaccard_raw_pairs(const nsm_set_table* left, const nsm_set_table* right, const int32_t* left_row, int32_t left_ids,
+                          const int32_t* right_row, int32_t right_ids, nsm_hit* pairs, uint64_t n_pairs, void* stream);
+int nsm_indel_levels_pairs(const nsm_level_items* left, const nsm_str_table* left_strings,
+                           const nsm_level_items* right, const nsm_str_table* right_strings,
+                           const int32_t* left_row, int32_t left_ids, const int32_t* right_row, int32_t right_ids,
+                           nsm_hit* pairs, uint64_t n_pairs, void* stream);
+int nsm_jaccard_levels_pairs(const nsm_set_table* left, const nsm_set_table* right, const int32_t* left_row,
+                             int32_t left_ids, const int32_t* right_row, int32_t right_ids, nsm_hit* pairs, uint64_t n_pairs,
+                             void* stream);
 
 /* Destroy the side stream and events the library created for `stream` on the current device.  The caller makes sure no nsm_indel_levels_grid work is still queued on that stream.  Returns 0. */
 int nsm_release(void* stream);

@@ -120,6 +120,10 @@ EXPORTS = (
     "nsm_jaccard_raw_profile",
     "nsm_indel_levels_profile",
     "nsm_jaccard_levels_profile",
+    "nsm_indel_raw_pairs",
+    "nsm_jaccard_raw_pairs",
+    "nsm_indel_levels_pairs",
+    "nsm_jaccard_levels_pairs",
 )
 
 _lib = None
@@ -186,6 +190,12 @@ def load() -> ctypes.CDLL:
                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.nsm_indel_levels_profile.argtypes = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable)] + levels_profile_tail
     lib.nsm_jaccard_levels_profile.argtypes = [P(NsmSetTable), P(NsmSetTable)] + levels_profile_tail
+    # left_row, left_ids, right_row, right_ids, pairs, n_pairs, stream
+    pairs_tail = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, c_u64, ctypes.c_void_p]
+    lib.nsm_indel_raw_pairs.argtypes = [P(NsmStrTable), P(NsmStrTable)] + pairs_tail
+    lib.nsm_jaccard_raw_pairs.argtypes = [P(NsmSetTable), P(NsmSetTable)] + pairs_tail
+    lib.nsm_indel_levels_pairs.argtypes = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable)] + pairs_tail
+    lib.nsm_jaccard_levels_pairs.argtypes = [P(NsmSetTable), P(NsmSetTable)] + pairs_tail
     # hits, scratch, capacity, hit_count, n_hint, id_limit, stream
     lib.nsm_sort_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_u64, ctypes.c_void_p, c_u64, ctypes.c_uint32,
                                   ctypes.c_void_p]

@@ -15,6 +15,9 @@ Same names, call convention and error behaviour as the reference's
   ``groups=`` (one hashable per right item) it keeps the best item of every group and of those the ``k`` best: the
   ``k`` best distinct candidates when the right side lists a candidate under several spellings.
 
+* ``plugin.pairs(left_items, right_items, pairs)`` scores a LIST of ``(i, j)`` pairs in O(P) -- rapidfuzz's
+  ``process.cpdist``: what do these particular pairs score?
+
 * ``plugin.profile(left_items, right_items, thresholds)`` answers what a whole ladder of thresholds would do -- hit counts
   per threshold and every item's best score -- without the hits (``grid.ThresholdProfile``).
 
@@ -91,6 +94,15 @@ def set_operand(value: Operand) -> Iterable[str]:
     return value if isinstance(value, list) else value.split()
 
 
+def _padded_ids(rows, vocab, width: int) -> np.ndarray:
+    """Token rows as the int array ``SetTable.from_padded`` takes: distinct ids first, -1 behind them."""
+    ids = np.full((len(rows), width), -1, dtype=np.int32)
+    for k, row in enumerate(rows):
+        uniq = list(dict.fromkeys(vocab.id(tok) for tok in row))
+        ids[k, : len(uniq)] = uniq
+    return ids
+
+
 class _IntersectionVsUnion:
     __name__ = "intersection_vs_union"
     kind = "sets"
@@ -164,6 +176,41 @@ class _IntersectionVsUnion:
             sub(ri))
         return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
 
+
+    @staticmethod
+    def pairs(left_items: Sequence[Operand], right_items: Sequence[Operand], pairs, device=None) -> np.ndarray:
+        """The score of every listed pair: ``pairs`` is a sequence of ``(i, j)`` positions in the two item lists, or a
+        P x 2 integer array; the result is ``[plugin(left_items[i], right_items[j]) for i, j in pairs]`` as a float64 array,
+        in O(P) (``nsm_jaccard_raw_pairs``: tables of the listed items only, one launch).  A listed pair of two empty sets
+        raises ``ZeroDivisionError`` as the plugin does (:13) -- a per-pair check here, not the whole-grid one.  A pair
+        with an item of more than 64 distinct tokens goes through the general grid, one call per distinct left item of
+        such pairs over its listed partners: slow, and meant for the rare item that needs it."""
+        from .. import wide
+
+        i, j = wide.check_pair_positions(pairs, len(left_items), len(right_items))
+        l_rows = {int(k): list(set_operand(left_items[k])) for k in np.unique(i)}
+        r_rows = {int(k): list(set_operand(right_items[k])) for k in np.unique(j)}
+        if any(not l_rows[int(a)] and not r_rows[int(b)] for a, b in zip(i, j)):
+            raise ZeroDivisionError("division by zero")  # (:13)
+        if len(i) == 0:
+            return np.zeros(0, dtype=np.float64)
+        dev = device or _device()
+
+        def fast(li, ri, pi, pj):
+            vocab = tables.Vocabulary()
+            ls, rs = [l_rows[int(k)] for k in li], [r_rows[int(k)] for k in ri]
+            width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
+            lt = tables.SetTable.from_padded(_padded_ids(ls, vocab, width), "left", dev, width=width, validate=False, index=False)
+            rt = tables.SetTable.from_padded(_padded_ids(rs, vocab, width), "right", dev, width=width, validate=False, index=False)
+            return grid.jaccard_raw_pairs(lt, rt, pi, pj)
+
+        general = lambda li, ri: wide.jaccard_any_grid([[l_rows[int(k)]] for k in li], [[r_rows[int(k)]] for k in ri],
+                                                       float("-inf"), raw=True, device=dev)
+        n_l, n_r = len(left_items), len(right_items)
+        big = lambda rows, n: np.fromiter((len(set(rows.get(k, ()))) > wide.FAST_TOKENS for k in range(n)), dtype=bool, count=n)
+        wide_l, wide_r = big(l_rows, n_l), big(r_rows, n_r)
+        split = (wide_l, wide_r) if wide_l.any() or wide_r.any() else None
+        return wide.split_pairs(split, i, j, fast, general)
 
     @staticmethod
     def profile(left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,
@@ -252,6 +299,33 @@ class _FuzzyMatch:
             sub(ri))
         return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
 
+
+    @staticmethod
+    def pairs(left_items: Sequence[Operand], right_items: Sequence[Operand], pairs, device=None) -> np.ndarray:
+        """The score of every listed pair: ``pairs`` is a sequence of ``(i, j)`` positions in the two item lists, or a
+        P x 2 integer array; the result is ``[plugin(left_items[i], right_items[j]) for i, j in pairs]`` as a float64 array,
+        in O(P) -- rapidfuzz's ``process.cpdist`` (``nsm_indel_raw_pairs``: tables of the listed items only, one launch).
+        A pair with a string beyond the fast kernels (more than 512 code units, a code unit outside the 255 most frequent)
+        goes through the general grid, one call per distinct left item of such pairs over its listed partners: slow, and
+        meant for the rare item that needs it."""
+        from .. import wide
+
+        i, j = wide.check_pair_positions(pairs, len(left_items), len(right_items))
+        if len(i) == 0:
+            return np.zeros(0, dtype=np.float64)
+        dev = device or _device()
+        l_ops = {int(k): fuzzy_operand(left_items[k]) for k in np.unique(i)}
+        r_ops = {int(k): fuzzy_operand(right_items[k]) for k in np.unique(j)}
+
+        def fast(li, ri, pi, pj):
+            lt, rt = tables.encode_strings([l_ops[int(k)] for k in li], [r_ops[int(k)] for k in ri], dev)
+            return grid.indel_raw_pairs(lt, rt, pi, pj)
+
+        general = lambda li, ri: wide.indel_any_grid([[l_ops[int(k)]] for k in li], [[r_ops[int(k)]] for k in ri], float("-inf"),
+                                                     raw=True, device=dev)
+        n_l, n_r = len(left_items), len(right_items)
+        split = wide.wide_string_items([[l_ops.get(k, "")] for k in range(n_l)], [[r_ops.get(k, "")] for k in range(n_r)])
+        return wide.split_pairs(split, i, j, fast, general)
 
     @staticmethod
     def profile(left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,

@@ -517,6 +517,118 @@ def jaccard_levels_profile(left: SetTable, right: SetTable, thresholds, category
                            banned, stats)
 
 
+# ------------------------------------------------------------------------------- listed pairs
+NO_SCORE = -1.0  # what a listed pair without a score gets (the profiles' "none")
+
+
+def check_pair_ids(i, j):
+    """The two id columns of a pair list as int64 arrays: one-dimensional integer arrays of equal length, else
+    ``ValueError`` -- before any device work."""
+    i, j = np.asarray(i), np.asarray(j)
+    for name, a in (("i", i), ("j", j)):
+        if a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+            raise ValueError(f"pairs: {name} must be a one-dimensional integer array")
+    if i.shape != j.shape:
+        raise ValueError(f"pairs: {len(i)} left ids for {len(j)} right ids")
+    return i.astype(np.int64), j.astype(np.int64)
+
+
+def _pair_keys(i: np.ndarray, j: np.ndarray) -> np.ndarray:
+    return (i.astype(np.int64) << 32) | (j.astype(np.int64) & 0xFFFFFFFF)
+
+
+def lookup_pairs(hits, i, j) -> np.ndarray:
+    """The definition of a pairs query in terms of a grid's hits: for every listed pair ``(i[p], j[p])`` its score in
+    ``hits`` (a ``Hits``, or a sequence of ``(score, i, j)`` records), ``-1.0`` when the pair is not among them.  The order
+    is the caller's, duplicates get equal scores."""
+    i, j = check_pair_ids(i, j)
+    if not isinstance(hits, Hits):
+        rec = list(hits)
+        hits = Hits(np.array([r[0] for r in rec], dtype=np.float64), np.array([r[1] for r in rec], dtype=np.int32),
+                    np.array([r[2] for r in rec], dtype=np.int32))
+    out = np.full(len(i), NO_SCORE, dtype=np.float64)
+    if len(hits) == 0 or len(i) == 0:
+        return out
+    keys = _pair_keys(hits.i, hits.j)
+    order = np.argsort(keys, kind="stable")
+    keys = keys[order]
+    int32 = lambda a: (a >= -(1 << 31)) & (a < (1 << 31))
+    fits = int32(i) & int32(j)  # (an id beyond int32 is in no hit list)
+    want = _pair_keys(np.where(fits, i, 0), np.where(fits, j, 0))
+    at = np.minimum(np.searchsorted(keys, want), len(keys) - 1)
+    found = fits & (keys[at] == want)
+    out[found] = hits.score[order[at[found]]]
+    return out
+
+
+def _row_map(orig: torch.Tensor, n: int, device) -> torch.Tensor:
+    """The inverse of a table's ``orig`` column as the entries read it: row_map[id] = the row of caller id ``id``, -1 for
+    an id no row carries -- one scatter of ``arange`` by ``orig``."""
+    ids = _left_id_limit(orig, n)
+    rows = torch.full((max(1, ids),), -1, dtype=torch.int32, device=device)
+    if n:
+        rows[orig[:n].long()] = torch.arange(n, dtype=torch.int32, device=device)
+    return rows[:ids] if ids else rows[:0]
+
+
+def _pairs(entry: str, tables: tuple, left, right, device, i, j) -> np.ndarray:
+    """A pairs query through the C entry ``entry``: ``tables`` in the entry's argument order, ``left`` / ``right`` the two
+    tables among them whose rows the caller ids name."""
+    i, j = check_pair_ids(i, j)
+    dev = _require_gpu(device)
+    fn = getattr(_lib.load(), entry)
+    n = len(i)
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    fits = lambda a: np.where((a >= 0) & (a < (1 << 31)), a, -1).astype(np.int32)  # (no such id: -1.0 either way)
+    host = np.zeros((n, 2), dtype=np.float64)
+    ij = host.view(np.int32).reshape(n, 4)
+    ij[:, 2], ij[:, 3] = fits(i), fits(j)
+    records = torch.from_numpy(host).to(dev)
+    lmap, rmap = _row_map(left.orig, left.n, dev), _row_map(right.orig, right.n, dev)
+    structs = [t.struct() for t in tables]
+    ptr = lambda t: t.data_ptr() if t.numel() else 0
+    _lib.check(fn(*structs, ptr(lmap), int(lmap.numel()), ptr(rmap), int(rmap.numel()), records.data_ptr(), n,
+                  torch.cuda.current_stream(dev).cuda_stream), entry)
+    return records[:, 0].cpu().numpy()
+
+
+def indel_raw_pairs(left: StrTable, right: StrTable, i, j) -> np.ndarray:
+    """The ``fuzzy_match`` score of every listed pair: ``i`` / ``j`` are integer arrays of equal length holding caller ids
+    (the tables' ``orig`` values).  Returns float64 scores in the caller's order -- ``lookup_pairs(indel_raw_grid(left,
+    right, -inf), i, j)`` bit for bit, ``-1.0`` for an id the table does not hold -- in O(P), by ``nsm_indel_raw_pairs``."""
+    i, j = check_pair_ids(i, j)
+    return _pairs("nsm_indel_raw_pairs", (left, right), left, right, left.codes.device, i, j)
+
+
+def jaccard_raw_pairs(left: SetTable, right: SetTable, i, j) -> np.ndarray:
+    """``intersection_vs_union`` counterpart of ``indel_raw_pairs``; a pair of two empty sets gets ``-1.0`` (the plugin
+    raises ``ZeroDivisionError`` for it)."""
+    i, j = check_pair_ids(i, j)
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    return _pairs("nsm_jaccard_raw_pairs", (left, right), left, right, left.ids.device, i, j)
+
+
+def indel_levels_pairs(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, i, j) -> np.ndarray:
+    """The ``compare_terms`` x ``fuzzy_match`` score of every listed pair of items, as ``indel_levels_grid`` computes it --
+    without category predicate or blacklist.  ``-1.0`` also for a pair with an item without levels.  Tables must be encoded
+    with ``partition=False``."""
+    i, j = check_pair_ids(i, j)
+    return _pairs("nsm_indel_levels_pairs", (left, left_strings, right, right_strings), left, right, left.first.device, i, j)
+
+
+def jaccard_levels_pairs(left: SetTable, right: SetTable, i, j) -> np.ndarray:
+    """``intersection_vs_union`` counterpart of ``indel_levels_pairs`` (tables from ``SetTable.from_levels`` /
+    ``from_nested_arrays`` with ``partition=False``); ``-1.0`` also for a pair that compares two empty levels."""
+    i, j = check_pair_ids(i, j)
+    if left.nlev is None or right.nlev is None:
+        raise ValueError("levels pairs need tables built with SetTable.from_levels")
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    return _pairs("nsm_jaccard_levels_pairs", (left, right), left, right, left.ids.device, i, j)
+
+
 # ------------------------------------------------------------------------------- levels grids
 def jaccard_levels_grid(
     left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True,

@@ -455,6 +455,80 @@ class ComparableData:
                           np.arange(pre.n_r)))
         return grid.merge_profiles(parts, t, pre.n_l, pre.n_r)
 
+    def score_pairs(self, other, pairs, compare_column: str = None, score_func: str = None,
+                    identifier_column_left: Optional[str] = None, identifier_column_right: Optional[str] = None,
+                    left_name: str = None, right_name: str = None, **kwargs) -> Comparable:
+        """What do THESE pairs score?  ``pairs``: a sequence of (left identifier, right identifier), or a ``Mapping`` (a
+        validated mapping, a whitelist, a blacklist), read with ``flatten_mapping(left_name, right_name, mapping)``.
+        Returns a ``Comparable`` with ``compare``'s columns and one row per listed pair, in list order (a plain
+        ``RangeIndex``); ``MatchScore`` is ``compare_terms`` of the two items, NaN where an identifier is not in the compared
+        frame (the frame after ``dropna`` on the compare column; of several rows with one identifier the first counts).
+
+        Takes ``compare``'s keyword arguments and runs its per-item prelude (dropna, the level builder).  No whitelist
+        removal, blacklist, category filter or threshold is applied -- those arguments are ignored: the whitelist's own
+        pairs are what a user scores here.  Two level-less items score 0 as in ``compare_terms``; the FIRST listed pair for
+        which ``compare_terms`` would raise raises here too (``IndexError``: level-less against levels,
+        ``ZeroDivisionError``: an empty-vs-empty level), before any device work.  One launch of ``nsm_*_levels_pairs`` for
+        the whole list, O(P); pairs with a wide or irregular item go through the general grids, one call per distinct left
+        item of such pairs (slow, rare).  On a sharded run every rank scores the whole list itself: no collective."""
+        if isinstance(pairs, (Mapping, dict)) or (hasattr(pairs, "dict") and not isinstance(pairs, (list, tuple))):
+            if not left_name or not right_name:
+                raise ValueError("score_pairs: a Mapping needs left_name and right_name (the cohorts whose identifiers it lists)")
+            pairs = flatten_mapping(left_name, right_name, _as_mapping(pairs))
+        if isinstance(pairs, (str, bytes)):
+            raise ValueError("score_pairs: pairs must be a sequence of (left identifier, right identifier)")
+        pairs = list(pairs)
+        for pair in pairs:
+            if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
+                raise ValueError(f"score_pairs: {pair!r} is not a (left identifier, right identifier) pair")
+        pre = self._compare_prelude(other, None, None, score_func, compare_column, kwargs.get("category_column", "Category"),
+                                    left_name or "left", right_name or "right", False, identifier_column_left,
+                                    identifier_column_right, listed=True)
+        first_row = lambda ids: {v: k for k, v in reversed(list(enumerate(ids)))}
+        pos_l, pos_r = first_row(pre.id_l), first_row(pre.id_r)
+        pi = np.array([pos_l.get(a, -1) for a, _ in pairs], dtype=np.int64)
+        pj = np.array([pos_r.get(b, -1) for _, b in pairs], dtype=np.int64)
+        known = (pi >= 0) & (pj >= 0)
+        score = np.full(len(pairs), np.nan, dtype=np.float64)
+        # ---- the reference's per-pair exceptions, in list order; level-less pairs score 0
+        is_sets = pre.plugin.kind == "sets"
+        empty = {}
+        if is_sets:
+            reach = lambda levels: _empty_levels([lv if isinstance(lv, list) else lv.split() for lv in levels])
+            empty = {("l", k): reach(pre.levels_l[k]) for k in set(pi[known].tolist())}
+            empty.update({("r", k): reach(pre.levels_r[k]) for k in set(pj[known].tolist())})
+        todo = []
+        for p in np.flatnonzero(known):
+            a, b = pre.levels_l[pi[p]], pre.levels_r[pj[p]]
+            if len(a) == 0 and len(b) == 0:
+                score[p] = 0.0
+            elif len(a) == 0 or len(b) == 0:
+                raise IndexError("list index out of range")
+            elif is_sets and empty[("l", int(pi[p]))] and empty[("r", int(pj[p]))] and \
+                    _divides_by_zero(a, empty[("l", int(pi[p]))], b, empty[("r", int(pj[p]))]):
+                raise ZeroDivisionError("division by zero")
+            else:
+                todo.append(p)
+        if todo:
+            todo = np.array(todo, dtype=np.int64)
+            score[todo] = _levels_pairs(pre.plugin, pre.levels_l, pre.levels_r, pi[todo], pj[todo])
+        # ---- output frame: compare's columns, one row per listed pair
+        lf = pre.lf.assign(**{COMP_COLUMN: pre.levels_l, QUESTION_OUTPUT: pre.argument_l})
+        rf = pre.rf.assign(**{COMP_COLUMN: pre.levels_r, QUESTION_OUTPUT: pre.argument_r})
+        out = {}
+        sides = ((lf, pre.lp, pi, identifier_column_left or IDENTIFIER, [a for a, _ in pairs]),
+                 (rf, pre.rp, pj, identifier_column_right or IDENTIFIER, [b for _, b in pairs]))
+        for frame, prefix, rows, id_col, given in sides:
+            for col in frame.columns:
+                if col in COLUMN_NAMES:
+                    cells = np.empty(len(rows), dtype=object)
+                    values = frame[col].to_numpy()
+                    for k, r in enumerate(rows):
+                        cells[k] = values[r] if r >= 0 else (given[k] if col == id_col else None)
+                    out[prefix + col] = cells
+        out[MATCH_SCORE] = score
+        return Comparable(data=pd.DataFrame(out), left_name=pre.lp, right_name=pre.rp)
+
     def _hash_compare_args(self, other, whitelist, blacklist, compare_column, cache_threshold, kwargs, top_k=None) -> str:
         other_csv = other.to_csv() if hasattr(other, "to_csv") else pd.DataFrame(other).to_csv(index=False)
         parts = [
@@ -471,11 +545,13 @@ class ComparableData:
 
     def _compare_prelude(self, right, existing_mappings_whitelist, existing_mappings_blacklist, score_func, compare_column,
                          category_column, left_name, right_name, filter_categories, identifier_column_left,
-                         identifier_column_right, per_item: Optional[str] = None) -> SimpleNamespace:
+                         identifier_column_right, per_item: Optional[str] = None, listed: bool = False) -> SimpleNamespace:
         """Everything of :133-222 that comes before the scores, shared by ``gen_comparable`` and ``compare_profile``:
         whitelist, levels, blacklist as position pairs, categories, the reference's per-pair exceptions in pair order, the
         zero-level pairs that score 0, and the items the device grid takes.  ``per_item``: the name of a query whose
-        category predicate must run on the device (``NotImplementedError`` beyond 64 labels)."""
+        category predicate must run on the device (``NotImplementedError`` beyond 64 labels).  ``listed``
+        (``score_pairs``): the per-item part only -- dropna, levels, identifiers; the caller names its pairs itself, so no
+        whitelist removal, blacklist, category filter or scan of the whole grid for the reference's exceptions."""
         plugin = getattr(score_functions, score_func)  # AttributeError for an unknown name (:150)
         whitelist = _as_mapping(existing_mappings_whitelist)
         blacklist = _as_mapping(existing_mappings_blacklist)
@@ -488,8 +564,9 @@ class ComparableData:
             "comparing number of items %i left, %i right, potential %s comparisons",
             len(left), len(right), "{:,}".format(len(left) * len(right)),
         )
-        remove_existing_mappings(left, right, left_name, right_name, whitelist)
-        logger.info("after removing existing whitelisted mappings: %i left, %i right", len(left), len(right))
+        if not listed:
+            remove_existing_mappings(left, right, left_name, right_name, whitelist)
+            logger.info("after removing existing whitelisted mappings: %i left, %i right", len(left), len(right))
 
         lf, rf = left.map_for_comparable(), right.map_for_comparable()
         lp, rp = left_name.title(), right_name.title()
@@ -503,6 +580,9 @@ class ComparableData:
         # ---- blacklist as position pairs
         id_l = list(lf[identifier_column_left or IDENTIFIER])
         id_r = list(rf[identifier_column_right or IDENTIFIER])
+        if listed:
+            return SimpleNamespace(plugin=plugin, lf=lf, rf=rf, lp=lp, rp=rp, n_l=n_l, n_r=n_r, levels_l=levels_l,
+                                   levels_r=levels_r, argument_l=argument_l, argument_r=argument_r, id_l=id_l, id_r=id_r)
         banned = _banned_positions(flatten_mapping(left_name, right_name, blacklist), id_l, id_r)
         logger.info("remaining %s entries after removing blacklisted ones", "{:,}".format(n_l * n_r - len(banned)))
 
@@ -910,6 +990,58 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
     general = lambda li, ri: wide.indel_any_grid(sub(ops_l, li), sub(ops_r, ri), threshold, cut(cat_l, li), cut(cat_r, ri),
                                                  cat_mode, device=dev)
     return split_grid(split, fast, general)
+
+
+# =============================================================================== listed pairs
+_NO_LEVELS: list = []  # stands in for the items no listed pair names
+
+
+def _levels_pairs(plugin, levels_l, levels_r, pi: np.ndarray, pj: np.ndarray) -> np.ndarray:
+    """``compare_terms`` x ``plugin`` of the listed pairs ``(levels_l[pi[p]], levels_r[pj[p]])`` -- every item with at
+    least one level, no pair the reference raises for -- on the current device: tables of the listed items only, one
+    ``nsm_*_levels_pairs`` launch.  Pairs with an item the fast layouts cannot hold (``wide.py``) go through
+    ``_levels_grid``'s general kernels instead, one 1 x partners grid per distinct left item of such pairs."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise _lib.NsmLibraryError("the match loop runs on an MI355X (HIP device); there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    from .. import wide
+
+    pi, pj = np.asarray(pi, dtype=np.int64), np.asarray(pj, dtype=np.int64)
+    used = lambda items, idx: [items[k] if k in idx else _NO_LEVELS for k in range(len(items))]  # (unlisted items: not looked at)
+    set_l, set_r = set(pi.tolist()), set(pj.tolist())
+    if plugin.kind == "sets":
+        as_set_levels = lambda it: [lv if isinstance(lv, list) else lv.split() for lv in it]
+        sl, sr = [as_set_levels(it) for it in used(levels_l, set_l)], [as_set_levels(it) for it in used(levels_r, set_r)]
+
+        def fast(li, ri, qi, qj):
+            vocab = tables.Vocabulary()
+            a, b = [sl[k] for k in li], [sr[k] for k in ri]
+            width = tables.pick_width(max((len(set(it[-1])) for it in a if it), default=1),
+                                      max((len(set(it[-1])) for it in b if it), default=1))
+            lt = tables.SetTable.from_levels(a, "left", dev, vocab, width=width, partition=False, index=False)
+            rt = tables.SetTable.from_levels(b, "right", dev, vocab, width=width, partition=False, index=False)
+            return grid.jaccard_levels_pairs(lt, rt, qi, qj)
+
+        general = lambda li, ri: wide.jaccard_any_grid([sl[k] for k in li], [sr[k] for k in ri], float("-inf"), device=dev)
+        split = wide.wide_set_items(sl, sr)
+        try:
+            return wide.split_pairs(split, pi, pj, fast, general)
+        except tables.IrregularLevels:  # levels that are not suffix-nested: only those items leave the fast path
+            split = wide.wide_set_items(sl, sr, nesting=True)
+            if split is None:
+                raise
+            return wide.split_pairs(split, pi, pj, fast, general)
+    prep = lambda items: ComparableData._memoised("fuzzy", items, lambda it: [score_functions.fuzzy_operand(lv) for lv in it])
+    ops_l, ops_r = prep(used(levels_l, set_l)), prep(used(levels_r, set_r))
+
+    def fast(li, ri, qi, qj):
+        a, b, c, d = tables.encode_level_strings([ops_l[k] for k in li], [ops_r[k] for k in ri], dev, partition=False)
+        return grid.indel_levels_pairs(a, b, c, d, qi, qj)
+
+    general = lambda li, ri: wide.indel_any_grid([ops_l[k] for k in li], [ops_r[k] for k in ri], float("-inf"), device=dev)
+    return wide.split_pairs(wide.wide_string_items(ops_l, ops_r), pi, pj, fast, general)
 
 
 # =============================================================================== per-item top-k

@@ -98,6 +98,42 @@ def split_profile(split, n_left: int, n_right: int, thresholds, fast: Callable, 
     return grid.merge_profiles(parts, thresholds, n_left, n_right)
 
 
+def check_pair_positions(pairs, n_left: int, n_right: int):
+    """``pairs`` of a pairs query -- a sequence of ``(i, j)`` positions or a P x 2 integer array -- as two int64 arrays.
+    Anything else is a ``ValueError``, a position outside the item lists an ``IndexError``; both before any device work."""
+    arr = np.asarray(pairs)
+    if arr.size == 0 and arr.ndim <= 2:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    if arr.ndim != 2 or arr.shape[1] != 2 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("pairs must be a sequence of (i, j) integer positions or a P x 2 integer array")
+    i, j = arr[:, 0].astype(np.int64), arr[:, 1].astype(np.int64)
+    if (i < 0).any() or (i >= n_left).any() or (j < 0).any() or (j >= n_right).any():
+        raise IndexError(f"pair position outside the {n_left} left / {n_right} right items")
+    return i, j
+
+
+def split_pairs(split, i: np.ndarray, j: np.ndarray, fast: Callable, general: Callable) -> np.ndarray:
+    """The scores of the listed pairs ``(i[p], j[p])`` when ``split`` ((wide_l, wide_r) or None) takes some items off the
+    fast path.  ``fast(left_idx, right_idx, pi, pj)`` scores the pairs ``(left_idx[pi[p]], right_idx[pj[p]])`` through a
+    pairs entry, tables built from those items alone; ``general(left_idx, right_idx)`` is the general grid of ``split_grid``,
+    called at -inf.  A pair with a wide item goes through the general grids: per distinct left item of such pairs ONE grid
+    over its listed partners, picked with ``grid.lookup_pairs``.  That route is slow (a launch and a sync per left item)
+    and meant for the few items that need it."""
+    out = np.full(len(i), grid.NO_SCORE, dtype=np.float64)
+    if len(i) == 0:
+        return out
+    slow = np.zeros(len(i), dtype=bool) if split is None else (split[0][i] | split[1][j])
+    if not slow.all():
+        li, pi = np.unique(i[~slow], return_inverse=True)
+        ri, pj = np.unique(j[~slow], return_inverse=True)
+        out[~slow] = fast(li, ri, pi.reshape(-1), pj.reshape(-1))
+    for a in np.unique(i[slow]):
+        sel = np.flatnonzero(slow & (i == a))
+        partners, pj = np.unique(j[sel], return_inverse=True)
+        out[sel] = grid.lookup_pairs(general(np.array([a]), partners), np.zeros(len(sel), np.int64), pj.reshape(-1))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ strings
 def wide_string_items(items_l: Sequence[Sequence[str]], items_r: Sequence[Sequence[str]]):
     """Which items must leave the fast fuzzy path: a level string longer than 512 code units, or a code unit outside the
