@@ -6,10 +6,17 @@
 // v_sad_u8.  On configs[2] it passes 1 % of the pairs -- far too many for a wave-wide second look (some lane of a row's 64
 // passes in 20 % of the rows), so the survivors are handled PER PAIR:
 //
-//   scan    per batch of R = 8 left rows (their 128 bytes of coarse histograms arrive with two s_load_dwordx16) and T = 2
-//           right tiles: 4 v_sad_u8 per pair, the sign of the seeded sum shifted into a per-lane bit mask (v_alignbit);
-//   stack   lanes whose mask is not empty push (batch, lane, mask) on the wave's LDS stack -- one ballot and one ds_write per
-//           BATCH, nothing per pair;
+//   scan    per push of 16 left rows (two groups of R = 8; a group's 128 bytes of coarse histograms arrive with two
+//           s_load_dwordx16, the second group re-uses the first one's 32 SGPRs) and T = 2 right tiles: ONE accumulator
+//           register per left row carries both tiles -- 4 v_sad_u8 add tile 0's L1 into the low half, 4 v_sad_hi_u8 tile 1's
+//           into the high half -- and the verdict is a CARRY, not a sign: row position r seeds each half with
+//           2^(8 + r) - 1 - limit, so bit 8 + r of the half comes out set exactly when L1 > limit (L1 <= 128 and limit >= -1
+//           keep the seed in [0, 2^15] and the sum below 2^16: nothing leaves tile 0's half).  One v_bitop3_b32 per row
+//           (with a wave-uniform mask) folds bits 8 + r and 24 + r into the group's word, one v_perm_b32 per push puts the
+//           first group's verdicts in the odd bytes and the second group's in the even ones, one v_not makes them passes;
+//   stack   lanes whose mask is not empty push (first row, lane, mask) on the wave's LDS stack -- one ballot and one
+//           ds_write per PUSH of 32 pairs, nothing per pair.  The last 1..15 rows of a length class are scanned one at a
+//           time at row position 0 and pushed once;
 //   drain   whenever the stack holds more than 128 entries, 64 at a time (64 of 64 lanes busy): lane = one entry, ONE of
 //           its pairs (an entry with more pairs goes back on the stack) -- the 32-bucket L1 of the pair (the left histogram
 //           gathered from global memory, the right one read from the tile's copy in LDS, 8 v_sad_u8: 1 % of the pairs), then,
@@ -18,9 +25,11 @@
 //
 // Every test that drops a pair is an upper bound of the LCS: the hits are the one-stage kernel's, the exhaustive kernel's and
 // the oracle's.  Where the time goes on configs[2] (200k x 200k, threshold 0.8, same box, variant builds NSM_C3C_X_*):
-// scan 3.11 ms (VALU-bound: 64 v_sad_u8 + 16 v_alignbit + one push per batch), pop / re-push 0.11, the 32-bucket test of
-// 4e8 pairs 0.39, 4.1e5 LCS 0.16 -- 3.76 ms against the one-stage kernel's 5.11 (two tiles per wave; 6.54 with one tile and
-// the wave-wide LCS).
+// scan 2.71 ms (VALU-bound, every op of it half-rate: 128 v_sad_u8 / v_sad_hi_u8 + 14 v_bitop3 + 1 v_perm + one push of 8
+// ops per 16 rows ~ 151 issues of 4.3-4.5 cycles, x 1.02e7 pushes / 1024 SIMDs = 2.75 ms at 2.4 GHz), pop / re-push 0.10,
+// the 32-bucket test of 4e8 pairs 0.41, 4.1e5 LCS 0.11 -- 3.32 ms.  Before (a sign per pair shifted into the mask with
+// v_alignbit, one push per 8 rows: 176 issues per 16 rows): scan 3.11, kernel 3.76; the one-stage kernel: 5.11 (two tiles
+// per wave; 6.54 with one tile and the wave-wide LCS).
 #pragma once
 
 namespace nsm {
@@ -32,8 +41,10 @@ namespace nsm {
 #define NSM_C3C_ROWS 8
 #endif
 constexpr int kC3cStack = 192;  // entries per wave; drained when fewer than 64 slots are left
-// a stack entry: low word = the batch's pass mask (R rows x T tiles <= 32 bits), high word = (first row - chunk start) << 13 |
-// la << 6 | lane  (a chunk has at most 2^15 rows: nsm_indel_raw_grid)
+constexpr int kC3cGroups = 2;   // groups of R left rows per push
+// a stack entry: low word = the pass mask of 2 groups x R rows x T tiles = 32 pairs, high word = (first row - chunk start)
+// << 13 | la << 6 | lane  (a chunk has at most 2^15 rows: nsm_indel_raw_grid).  Bit p of the mask: byte = p >> 3,
+// tile = byte >> 1, group = 1 - (byte & 1), row = 8 group + (p & 7)
 
 // dynamic LDS: [wave][kC3cStack] u64 stack | [wave][T][8][64] u32 right histograms | [wave][T][64] u8 right lengths
 //              | lcsmin bytes
@@ -51,7 +62,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const uint8_t* __restrict__ rcodes, const int32_t* __restrict__ rlen, const int32_t* __restrict__ rorig,
     const uint32_t* __restrict__ rhist, const uint32_t* __restrict__ rh16, nsm_hit* __restrict__ hits,
     unsigned long long* __restrict__ count, const IndelRawParams p) {
-  static_assert((T == 1 || T == 2 || T == 4) && (R == 4 || R == 8) && R * T <= 32, "R rows x T right tiles per batch: one mask bit each");
+  // T = 2: one accumulator register per left row carries both tiles (its two 16-bit halves); R = 8: a row's verdicts sit at
+  // bits 8 + r and 24 + r, so a group of 8 rows fills bytes 1 and 3; kC3cGroups groups share one 32-bit mask and one push
+  static_assert(T == 2 && R == 8 && kC3cGroups == 2 && kC3cGroups * R * T == 32, "two groups of 8 rows x 2 tiles: one mask bit each");
+  static_assert(kC3cStack >= 3 * kWave, "a push needs 64 free slots; the drain runs on full passes");
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_mem[];
   unsigned long long* s_stack = s_mem;
   uint32_t* s_rh = reinterpret_cast<uint32_t*>(s_stack + kWavesPerBlock * kC3cStack);
@@ -113,8 +127,9 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const int ib = i0 + static_cast<int>(ehi >> 13);
     const int pos = active ? 31 - __clz(bits) : 0;  // (an entry on the stack has a bit set)
     bits &= ~(1u << pos);
-    const int k = R * T - 1 - pos;  // pair k of the batch: row k / T, tile k % T
-    const int r = k / T, t = k - r * T;
+    const int byte = pos >> 3;  // (the entry format above: the first group of a push sits in the odd bytes)
+    const int t = byte >> 1;
+    const int r = R * (1 - (byte & 1)) + (pos & 7);
     const int row = active ? ib + r : i0;
     // the 32-bucket filter of the pair
     const uint4* lp = reinterpret_cast<const uint4*>(lhist + static_cast<size_t>(row) * 8);
@@ -178,65 +193,90 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const int b = min(i1, lstart[c + 1]);
     if (a >= b) continue;
     const int la = 64 - c;
-    uint32_t seed[T];
+    // per tile: the pair can only hit if L1 <= limit = la + lb - 2 need (-1: it cannot fit).  Row position r of a group seeds
+    // its 16-bit half of the SAD chain with 2^(8 + r) - 1 - limit >= 0 (L1 <= 128): bit 8 + r of the half comes out set <=>
+    // L1 > limit, and since seed + L1 < 2^16 nothing carries from tile 0's half into tile 1's
+    uint32_t seed[R];
     bool some = false;
+    {
+      uint32_t below = 0;  // (-1 - limit) of both tiles, one per half
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
-      const int need = valid[t] ? need_of(la, lbj[t]) : static_cast<int>(kNever);
-      const bool fits = min(la, lbj[t]) >= need;  // exact length filter: LCS <= min(la, lb)
-      some = some || fits;
-      // the pair can only hit if L1 <= la + lb - 2 need; the SAD chain is seeded with -(limit + 1): negative <=> passes
-      const int limit = fits ? la + lbj[t] - 2 * need : -1;
-      seed[t] = static_cast<uint32_t>(-(limit + 1));
+      for (int t = 0; t < T; ++t) {
+        const int need = valid[t] ? need_of(la, lbj[t]) : static_cast<int>(kNever);
+        const bool fits = min(la, lbj[t]) >= need;  // exact length filter: LCS <= min(la, lb)
+        some = some || fits;
+        const int limit = fits ? la + lbj[t] - 2 * need : -1;
+        below |= (static_cast<uint32_t>(-1 - limit) & 0xffffu) << (16 * t);
+      }
+      // (2^(8 + r) + (-1 - limit)) per half: the sum of the halves never borrows, -1 - limit >= -129 > -2^8
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const uint32_t lo = ((0x100u << r) + (below & 0xffffu)) & 0xffffu;
+        const uint32_t hi = ((0x100u << r) + (below >> 16)) & 0xffffu;
+        seed[r] = hi << 16 | lo;
+      }
     }
     if (!__any(some)) continue;
 
     const uint32_t* __restrict__ hp = lh16 + static_cast<size_t>(a) * 4;
     const uint32_t lane_field = (static_cast<uint32_t>(la) << 6) | static_cast<uint32_t>(lane);
-    // the 4 R histogram dwords of a batch of `nrows` rows at hp_ (rows past the class re-read its last row; their bits are
-    // dropped below)
-    auto load_batch = [&](uint32_t (&h)[4 * R], const uint32_t* __restrict__ hp_, int nrows) {
-      if (nrows >= R) {
+    // one full group, its 128 bytes of histograms in 32 SGPRs: bits 8 + r / 24 + r of the result = pair (row r, tile 0 / 1)
+    // FAILED the coarse test (the other bits: junk)
+    auto scan_group = [&](const uint32_t* __restrict__ hp_) -> uint32_t {
+      uint32_t h[4 * R];
 #pragma unroll
-        for (int q = 0; q < 4 * R; ++q) h[q] = hp_[q];
-      } else {
+      for (int q = 0; q < 4 * R; ++q) h[q] = hp_[q];
+      uint32_t acc = 0;
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const uint32_t* __restrict__ hr_ = hp_ + 4 * min(r, nrows - 1);
+      for (int r = 0; r < R; ++r) {
+        uint32_t x = seed[r];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) h[4 * r + q] = hr_[q];
+        for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_sad_u8(h[4 * r + q], hc[0][q], x);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_sad_hi_u8(h[4 * r + q], hc[1][q], x);
+        // acc = (x & m) | (acc & ~m), m = 0x01000100 << r wave-uniform: one v_bitop3_b32 per row
+        acc = r == 0 ? x : __builtin_amdgcn_bitop3_b32(x, 0x01000100u << r, acc, 0xE2);
+      }
+      return acc;
+    };
+    // lanes with a pair that passed push (first row, lane, mask): one ballot and one ds_write per push
+    auto push = [&](uint32_t acc, int i) {
+      const bool nz = acc != 0u;
+      const unsigned long long m = __ballot(nz);
+      if (m != 0ull) {
+        if (nz) {
+          const int slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), static_cast<uint32_t>(q_cnt)));
+          stack[slot] = (static_cast<unsigned long long>((static_cast<uint32_t>(i - i0) << 13) | lane_field) << 32) | acc;
         }
+        q_cnt += __popcll(m);
       }
     };
-    for (int i = a; i < b;) {
-      for (; i < b && q_cnt <= kC3cStack - kWave; i += R, hp += 4 * R) {
-        const int nrows = min(R, b - i);
-        uint32_t h[4 * R];
-        load_batch(h, hp, nrows);
-        // acc: bit (R T - 1 - k) set = pair k = (row i + r, tile t), k = r T + t, passed the coarse test
-        uint32_t acc = 0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-#pragma unroll
-          for (int t = 0; t < T; ++t) {
-            uint32_t l1 = seed[t];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) l1 = __builtin_amdgcn_sad_u8(h[4 * r + q], hc[t][q], l1);
-            acc = __builtin_amdgcn_alignbit(acc, l1, 31);  // acc = acc << 1 | sign(l1)
-          }
-        }
-        if (nrows < R) acc &= ~((1u << ((R - nrows) * T)) - 1u);
-        const bool nz = acc != 0u;
-        const unsigned long long m = __ballot(nz);
-        if (m != 0ull) {  // one ds_write per batch: (first row, lane, mask)
-          if (nz) {
-            const int slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), static_cast<uint32_t>(q_cnt)));
-            stack[slot] = (static_cast<unsigned long long>((static_cast<uint32_t>(i - i0) << 13) | lane_field) << 32) | acc;
-          }
-          q_cnt += __popcll(m);
-        }
+    constexpr int kPush = kC3cGroups * R;  // left rows per push
+    const int b_full = a + (b - a) / kPush * kPush;
+    for (int i = a; i < b_full;) {
+      for (; i < b_full && q_cnt <= kC3cStack - kWave; i += kPush, hp += 4 * kPush) {
+        const uint32_t fail_a = scan_group(hp);
+        const uint32_t fail_b = scan_group(hp + 4 * R);
+        // the first group's verdicts stay in the odd bytes, the second group's move into the even ones: one v_perm_b32
+        push(~__builtin_amdgcn_perm(fail_a, fail_b, 0x07030501u), i);
       }
       while (q_cnt >= kWave) drain_pass();  // full passes only: the rest waits for more
+    }
+    if (b_full < b) {
+      // the class's last 1..15 rows, one at a time at row position 0 (verdicts at bits 8 and 24), each moved to its place
+      while (q_cnt > kC3cStack - kWave) drain_pass();
+      uint32_t acc = 0;
+#pragma unroll 1
+      for (int r = 0; r < b - b_full; ++r, hp += 4) {
+        uint32_t x = seed[0];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_sad_u8(hp[q], hc[0][q], x);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_sad_hi_u8(hp[q], hc[1][q], x);
+        acc |= ((~x >> 8) & 0x00010001u) << ((r < R ? 8 : 0) + (r & (R - 1)));
+      }
+      push(acc, b_full);
+      while (q_cnt >= kWave) drain_pass();
     }
   }
   while (q_cnt > 0) drain_pass();

@@ -69,6 +69,12 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, uint32_t s0, uint32_t s1
         if (KIND == 50) asm volatile("v_mov_b32_dpp %0, %1 row_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
         if (KIND == 51) asm volatile("v_readlane_b32 s20, %0, 3" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
         if (KIND == 52) asm volatile("ds_read_b64 %0, %1" : "=v"(pk[q&3]) : "v"(w[q] & 0xff8));
+        if (KIND == 53) asm volatile("v_sad_hi_u8 %0, %0, %1, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 54) asm volatile("v_sad_hi_u8 %0, %2, %1, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 55) asm volatile("v_sad_u8 %0, %2, %1, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 56) asm volatile("v_bitop3_b32 %0, %1, %3, %0 bitop3:0xe2" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 57) asm volatile("v_bitop3_b32 %0, %1, %2, %0 bitop3:0xe2" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 58) asm volatile("v_bfi_b32 %0, %2, %1, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
       }
     }
   }
@@ -153,5 +159,11 @@ int main() {
   run<50>("v_mov_b32 dpp row_shr", 1);
   run<51>("v_readlane (salu dst)", 1);
   run<52>("ds_read_b64 (same addr)", 1);
+  run<53>("v_sad_hi_u8", 1);
+  run<54>("v_sad_hi_u8 sgpr", 1);
+  run<55>("v_sad_u8 sgpr", 1);
+  run<56>("v_bitop3_b32", 1);
+  run<57>("v_bitop3_b32 sgpr", 1);
+  run<58>("v_bfi_b32 sgpr", 1);
   return 0;
 }
