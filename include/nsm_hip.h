@@ -151,9 +151,10 @@ typedef struct nsm_set_table {
  *                                   with (c & 31) == b; optional (NULL: no histogram prune)
  *   hist16 device uint8 [n][16]     (ABI 5) the same histogram over 16 buckets: hist16[r][b] = min(255, hist[r][b] +
  *                                   hist[r][b + 16]); optional.  With it on BOTH sides the RAW grid of 64-unit strings
- *                                   filters in two stages: 16 buckets for every pair (half the arithmetic and half the
- *                                   bytes of the 32-bucket test, which can only pass more pairs), 32 buckets for the
- *                                   pairs that pass (csrc/indel_raw_coarse.hpp); the hits are the same either way.
+ *                                   filters in two stages: a cheaper bound for every pair (since the matrix-pipe scan it is
+ *                                   built from the 32-bucket hist column; hist16 still selects the kernel), the exact
+ *                                   32-bucket test for the pairs that pass (csrc/indel_raw_coarse.hpp); the hits are the
+ *                                   same either way.
  *                                   16-byte aligned (a row is read as one 128-bit word)
  */
 typedef struct nsm_str_table {

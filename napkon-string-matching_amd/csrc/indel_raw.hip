@@ -441,24 +441,29 @@ extern "C" int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table
       set_error("nsm_indel_raw_grid: hist16 must be 16-byte aligned (rows are read as one 128-bit word)");
       return NSM_E_BADARG;
     }
-    // both tables carry the 16-bucket histograms: the two-stage filter (indel_raw_coarse.hpp)
-    constexpr int T = NSM_C3C_TILES;
-    const int n_tiles = ((right->n + kWave - 1) / kWave + T - 1) / T;
-    p.rows_per_chunk = pick_rows_per_chunk(left->n, n_tiles);
+    if ((reinterpret_cast<uintptr_t>(left->hist) | reinterpret_cast<uintptr_t>(right->hist)) & 15u) {
+      set_error("nsm_indel_raw_grid: hist must be 16-byte aligned (rows are read as 128-bit words)");
+      return NSM_E_BADARG;
+    }
+    // both tables carry the 16-bucket histograms: the two-stage filter (indel_raw_coarse.hpp; its first stage is built from
+    // the 32-bucket column)
+    const int n_tiles = (right->n + kC3cRights - 1) / kC3cRights;
+    // a multiple of the block size (blocks start at a length class's first row in the chunk, so this aligns nothing: it only
+    // keeps a chunk from ending on a few rows of a class that the next chunk then scans as a partial block of its own)
+    p.rows_per_chunk = (pick_rows_per_chunk(left->n, n_tiles) + kC3cBlock - 1) / kC3cBlock * kC3cBlock;
     dim3 grid((n_tiles + kWavesPerBlock - 1) / kWavesPerBlock, (left->n + p.rows_per_chunk - 1) / p.rows_per_chunk);
     if (grid.y > 65535) {
-      p.rows_per_chunk = (left->n + 65534) / 65535;
+      p.rows_per_chunk = ((left->n + 65534) / 65535 + kC3cBlock - 1) / kC3cBlock * kC3cBlock;
       grid.y = (left->n + p.rows_per_chunk - 1) / p.rows_per_chunk;
     }
     if (p.rows_per_chunk > (1 << 15)) {  // (a stack entry keeps its row relative to the chunk in 15 bits)
       set_error("nsm_indel_raw_grid: %d left rows per chunk", p.rows_per_chunk);
       return NSM_E_UNSUPPORTED;
     }
-    hipLaunchKernelGGL((indel_raw_coarse_kernel<T, NSM_C3C_ROWS>), grid, dim3(kBlock), c3c_lds_bytes(T),
+    hipLaunchKernelGGL((indel_raw_coarse_kernel<NSM_C3C_NT, NSM_C3C_CAP>), grid, dim3(kBlock), c3c_lds_bytes(),
                        static_cast<hipStream_t>(stream), left->codes, left->len, left->len_start, left->orig,
-                       reinterpret_cast<const uint32_t*>(left->hist), reinterpret_cast<const uint32_t*>(left->hist16), right->codes,
-                       right->len, right->orig, reinterpret_cast<const uint32_t*>(right->hist),
-                       reinterpret_cast<const uint32_t*>(right->hist16), hits, hit_count, p);
+                       reinterpret_cast<const uint32_t*>(left->hist), right->codes, right->len, right->orig,
+                       reinterpret_cast<const uint32_t*>(right->hist), hits, hit_count, p);
     return hip_status(hipGetLastError(), "indel_raw_coarse_kernel launch");
   }
   // wavefronts along the right side: one per T tiles of 64 strings

@@ -164,8 +164,8 @@ def indel_raw_grid(
     two_stage: bool = True,
 ) -> Hits:
     """``fuzzy_match`` (QRatio/100 = Indel ratio after default_process) on one string per item.
-    ``two_stage=False``: the 32-bucket histogram test for every pair even when both tables carry the 16-bucket
-    column (A/B runs, tests; same hits)."""
+    ``two_stage=False``: the 32-bucket histogram test for every pair even when both tables carry the ``hist16``
+    column that selects the two-stage kernel (A/B runs, tests; same hits)."""
     lib = _lib.load()
     ls, rs = left.struct(), right.struct()
     flags = (_lib.FLAG_PRUNE if prune else 0) | (0 if two_stage else _lib.FLAG_ONE_STAGE)

@@ -679,8 +679,9 @@ class StrTable:
     has_empty: bool
     hist: Optional[torch.Tensor] = None
     len_start: Optional[torch.Tensor] = None
-    # 16-bucket histogram (bucket b + bucket b + 16 of ``hist``): the first stage of the RAW grid's filter on 64-unit
-    # strings (include/nsm_hip.h, ABI 5); only sorted 64-unit tables carry it
+    # 16-bucket histogram (bucket b + bucket b + 16 of ``hist``): with it on both sides the RAW grid of 64-unit strings
+    # runs its two-stage kernel (include/nsm_hip.h, ABI 5).  The kernel's first stage is built from ``hist`` now; the
+    # column only selects the kernel.  Only sorted 64-unit tables carry it
     hist16: Optional[torch.Tensor] = None
 
     @classmethod
