@@ -404,6 +404,49 @@ int nsm_jaccard_levels_profile(const nsm_set_table* left, const nsm_set_table* r
                                const int32_t* banned_j, uint64_t* pairs, double* left_best, double* right_best,
                                uint64_t* stats, void* stream);
 
+/* Floor grids (ABI 5, additive; csrc/floors_raw.hip, floors_levels.hip, floor_gate.hpp): a threshold grid whose threshold
+ * is per item.  Take the hit list of the matching grid (nsm_*_raw_grid / nsm_*_levels_grid; levels: after the category
+ * predicate, without the banned pairs) -- the same pairs and the same doubles, bit for bit.  A record (score, i, j) is
+ * emitted iff
+ *     score >= threshold  &&  (left_floor == NULL || score >= left_floor[i])  &&  (right_floor == NULL || score >= right_floor[j])
+ * with exact IEEE comparisons, no margin: a NaN floor admits nothing for its item, -inf admits everything, and with both
+ * arrays NULL the records are exactly the threshold grid's.  With floor = best - margin from the outputs of a profile call
+ * at [threshold] this is the best-match query: every item's best match with everything as good or nearly as good
+ * (left_floor alone), or only the pairs that are best from both sides (both floors: reciprocal best hits).
+ *   left_floor, right_floor  device doubles or NULL, indexed by CALLER id (left->orig / right->orig), one entry per id up to
+ *              the largest: the left_best / right_best arrays of nsm_*_profile can be handed over as they are
+ *   hits, capacity, hit_count  as for the threshold grids: records are appended behind the *hit_count already there, in ANY
+ *              order (nsm_sort_hits orders them), and the counter keeps counting past `capacity` -- grow and call again.  The
+ *              output size depends on the data (a cohort of identical items has left->n * right->n best records), so there is
+ *              no bound known in advance.  Null hit_count, or null hits with capacity > 0: NSM_E_BADARG
+ *   operands, category_mode, banned_start, banned_j, stats, flags  as for the matching nsm_*_top_k entry, with its table
+ *              checks; items must be ONE row each.  NSM_FLAG_PRUNE skips a pair only when an upper bound of its score is
+ *              strictly below max(threshold, left_floor[i]) -- final from the first pair on, so the sweep prunes at least as
+ *              hard as a profile sweep at `threshold`; without it every pair is scored.  The records are the same either way.
+ *              Levels mode applies the category predicate, then the floors, and consults the blacklist only for a pair about to
+ *              be emitted
+ * Checks, all before the first HIP call, in this order: a null table, hit_count, or hits with capacity > 0: NSM_E_BADARG; a
+ * negative n: NSM_E_BADARG; then a side without rows returns 0 without a launch (its columns are not looked at, as in the
+ * threshold grids); then the table checks of the matching nsm_*_top_k entry.  No device memory is allocated and one kernel
+ * goes on `stream`: the calls can be captured. */
+int nsm_indel_raw_floor_grid(const nsm_str_table* left, const nsm_str_table* right, double threshold,
+                             const double* left_floor /*device or NULL*/, const double* right_floor /*device or NULL*/,
+                             uint32_t flags, nsm_hit* hits, uint64_t capacity,
+                             unsigned long long* hit_count /*device, caller zeroes*/, uint64_t* stats /*device [4] or NULL*/,
+                             void* stream);
+int nsm_jaccard_raw_floor_grid(const nsm_set_table* left, const nsm_set_table* right, double threshold,
+                               const double* left_floor, const double* right_floor, uint32_t flags, nsm_hit* hits,
+                               uint64_t capacity, unsigned long long* hit_count, uint64_t* stats, void* stream);
+int nsm_indel_levels_floor_grid(const nsm_level_items* left, const nsm_str_table* left_strings,
+                                const nsm_level_items* right, const nsm_str_table* right_strings, double threshold,
+                                const double* left_floor, const double* right_floor, int32_t category_mode, uint32_t flags,
+                                const int32_t* banned_start, const int32_t* banned_j, nsm_hit* hits, uint64_t capacity,
+                                unsigned long long* hit_count, uint64_t* stats, void* stream);
+int nsm_jaccard_levels_floor_grid(const nsm_set_table* left, const nsm_set_table* right, double threshold,
+                                  const double* left_floor, const double* right_floor, int32_t category_mode, uint32_t flags,
+                                  const int32_t* banned_start, const int32_t* banned_j, nsm_hit* hits, uint64_t capacity,
+                                  unsigned long long* hit_count, uint64_t* stats, void* stream);
+
 /* Listed pairs (ABI 5, additive; csrc/pairs.hip): the score of every record of a caller's list, written in place --
  * rapidfuzz's process.cpdist beside extract (nsm_*_top_k) and the threshold grids.  It stands in for one `score_func(a, b)`
  * / `compare_terms(a, b)` call per listed pair (compare/score_functions.py:6-27, types/comparable_data.py:248-265): the

@@ -124,6 +124,10 @@ EXPORTS = (
     "nsm_jaccard_raw_pairs",
     "nsm_indel_levels_pairs",
     "nsm_jaccard_levels_pairs",
+    "nsm_indel_raw_floor_grid",
+    "nsm_jaccard_raw_floor_grid",
+    "nsm_indel_levels_floor_grid",
+    "nsm_jaccard_levels_floor_grid",
 )
 
 _lib = None
@@ -196,6 +200,16 @@ def load() -> ctypes.CDLL:
     lib.nsm_jaccard_raw_pairs.argtypes = [P(NsmSetTable), P(NsmSetTable)] + pairs_tail
     lib.nsm_indel_levels_pairs.argtypes = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable)] + pairs_tail
     lib.nsm_jaccard_levels_pairs.argtypes = [P(NsmSetTable), P(NsmSetTable)] + pairs_tail
+    # threshold, left_floor, right_floor, flags, hits, capacity, hit_count, stats, stream
+    floor_tail = [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, c_u64, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p]
+    lib.nsm_indel_raw_floor_grid.argtypes = [P(NsmStrTable), P(NsmStrTable)] + floor_tail
+    lib.nsm_jaccard_raw_floor_grid.argtypes = [P(NsmSetTable), P(NsmSetTable)] + floor_tail
+    # threshold, left_floor, right_floor, category_mode, flags, banned_start, banned_j, hits, capacity, hit_count, stats, stream
+    levels_floor_tail = [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p,
+                         ctypes.c_void_p, ctypes.c_void_p, c_u64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.nsm_indel_levels_floor_grid.argtypes = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable)] + levels_floor_tail
+    lib.nsm_jaccard_levels_floor_grid.argtypes = [P(NsmSetTable), P(NsmSetTable)] + levels_floor_tail
     # hits, scratch, capacity, hit_count, n_hint, id_limit, stream
     lib.nsm_sort_hits.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_u64, ctypes.c_void_p, c_u64, ctypes.c_uint32,
                                   ctypes.c_void_p]

@@ -21,6 +21,10 @@ Same names, call convention and error behaviour as the reference's
 * ``plugin.profile(left_items, right_items, thresholds)`` answers what a whole ladder of thresholds would do -- hit counts
   per threshold and every item's best score -- without the hits (``grid.ThresholdProfile``).
 
+* ``plugin.best(left_items, right_items, margin, threshold, mutual)`` keeps every left item's best match together with
+  everything within ``margin`` of it -- all its ties at ``margin=0``, which no fixed ``k`` returns -- and with
+  ``mutual=True`` only the pairs that are best from both sides (reciprocal best hits).
+
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
 """
@@ -101,6 +105,24 @@ def _padded_ids(rows, vocab, width: int) -> np.ndarray:
         uniq = list(dict.fromkeys(vocab.id(tok) for tok in row))
         ids[k, : len(uniq)] = uniq
     return ids
+
+
+def _best(profile, split, n_left: int, n_right: int, margin: float, threshold: float, mutual: bool, fast, general) -> grid.Hits:
+    """Best matches of a plugin grid in two passes.  Pass 1: ``profile([threshold])``, the plugin's own profile routing --
+    it merges the wide parts, so the bests are global.  Pass 2: the grid cut as ``wide.split_grid`` cuts it (``split``:
+    (wide_l, wide_r) or None); ``fast(li, ri, left_floor, right_floor)`` is the floor grid of a sub-grid with the floors
+    gathered to its sub-tables, ``general(li, ri)`` the general kernel's hits at ``threshold``, gated on the host."""
+    from .. import wide
+
+    if not n_left or not n_right:
+        return wide.merge([])
+    lf, rf = grid.floors_of_profile(profile([threshold]), margin, mutual)
+    take = lambda floor, idx: None if floor is None else floor[np.asarray(idx, dtype=np.int64)]
+    fast_part = lambda li, ri: fast(li, ri, take(lf, li), take(rf, ri))
+    general_part = lambda li, ri: grid.filter_by_floors(general(li, ri), take(lf, li), take(rf, ri))
+    if split is None:
+        return fast_part(range(n_left), range(n_right))
+    return wide.split_grid(split[0], split[1], fast_part, general_part)
 
 
 class _IntersectionVsUnion:
@@ -241,6 +263,35 @@ class _IntersectionVsUnion:
         return wide.split_profile(wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]), len(l_rows), len(r_rows),
                                   t, fast, general)
 
+    def best(self, left_items: Sequence[Operand], right_items: Sequence[Operand], margin: float = 0.0, threshold: float = 0.0,
+             mutual: bool = False, device=None, prune: bool = True) -> grid.Hits:
+        """``grid.best_of_hits(raw_grid(left_items, right_items, threshold), margin, mutual)`` without the grid's hits:
+        every left item's best match with everything within ``margin`` of it (``margin=0``: all its ties); ``mutual``: only
+        the pairs also within ``margin`` of the right item's best.  Wide items are routed as ``profile`` routes them."""
+        from .. import wide
+
+        margin = grid.check_margin(margin)
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_rows = [list(set_operand(v)) for v in left_items]
+        r_rows = [list(set_operand(v)) for v in right_items]
+        if any(not r for r in l_rows) and any(not r for r in r_rows):
+            raise ZeroDivisionError("division by zero")  # (:13)
+
+        def fast(li, ri, lf, rf):
+            vocab = tables.Vocabulary()
+            ls, rs = [l_rows[k_] for k_ in li], [r_rows[k_] for k_ in ri]
+            width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
+            lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
+            rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
+            return grid.jaccard_raw_floor_grid(lt, rt, threshold, lf, rf, prune=prune)
+
+        general = lambda li, ri: wide.jaccard_any_grid([[l_rows[k_]] for k_ in li], [[r_rows[k_]] for k_ in ri], threshold,
+                                                       raw=True, device=dev)
+        return _best(lambda t: self.profile(left_items, right_items, t, device=dev, prune=prune),
+                     wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]), len(l_rows), len(r_rows), margin,
+                     threshold, mutual, fast, general)
+
 
 class _FuzzyMatch:
     __name__ = "fuzzy_match"
@@ -349,6 +400,29 @@ class _FuzzyMatch:
             t, len(li), len(ri))
         return wide.split_profile(wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]), len(l_ops), len(r_ops),
                                   t, fast, general)
+
+    def best(self, left_items: Sequence[Operand], right_items: Sequence[Operand], margin: float = 0.0, threshold: float = 0.0,
+             mutual: bool = False, device=None, prune: bool = True) -> grid.Hits:
+        """``grid.best_of_hits(raw_grid(left_items, right_items, threshold), margin, mutual)`` without the grid's hits --
+        at threshold 0.0 that grid is N M records: every left item's best match with everything within ``margin`` of it
+        (``margin=0``: all its ties, which ``top_k(k=1)`` cuts in ``j`` order); ``mutual``: only the pairs also within
+        ``margin`` of the right item's best (reciprocal best hits).  Wide items are routed as ``profile`` routes them."""
+        from .. import wide
+
+        margin = grid.check_margin(margin)
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+
+        def fast(li, ri, lf, rf):
+            lt, rt = tables.encode_strings([l_ops[k_] for k_ in li], [r_ops[k_] for k_ in ri], dev)
+            return grid.indel_raw_floor_grid(lt, rt, threshold, lf, rf, prune=prune)
+
+        general = lambda li, ri: wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], threshold, raw=True,
+                                                     device=dev)
+        return _best(lambda t: self.profile(left_items, right_items, t, device=dev, prune=prune),
+                     wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]), len(l_ops), len(r_ops), margin,
+                     threshold, mutual, fast, general)
 
 
 intersection_vs_union = _IntersectionVsUnion()

@@ -517,6 +517,217 @@ def jaccard_levels_profile(left: SetTable, right: SetTable, thresholds, category
                            banned, stats)
 
 
+# ------------------------------------------------------------------------------- floor grids and best matches
+def check_margin(margin) -> float:
+    """``margin`` of a best-match query: a finite number ``>= 0`` (not a bool), else ``ValueError`` -- before any device
+    work."""
+    if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)):
+        raise ValueError(f"margin must be a finite number >= 0, got {margin!r}")
+    m = float(margin)
+    if not np.isfinite(m) or m < 0.0:
+        raise ValueError(f"margin must be a finite number >= 0, got {margin!r}")
+    return m
+
+
+def _best_scores(hits: Hits, n_left: Optional[int], n_right: Optional[int]):
+    """(left_best, right_best) of a hit list: every item's largest score, ``-inf`` for an item without a hit."""
+    nl = max(int(n_left or 0), int(hits.i.max()) + 1 if len(hits) else 0)
+    nr = max(int(n_right or 0), int(hits.j.max()) + 1 if len(hits) else 0)
+    lb, rb = np.full(nl, -np.inf), np.full(nr, -np.inf)
+    np.maximum.at(lb, hits.i, hits.score)
+    np.maximum.at(rb, hits.j, hits.score)
+    return lb, rb
+
+
+def _canonical(score: np.ndarray, i: np.ndarray, j: np.ndarray) -> Hits:
+    order = np.lexsort((j, i, -score))
+    return Hits(score[order], i[order], j[order])
+
+
+def filter_by_floors(hits: Hits, left_floor=None, right_floor=None) -> Hits:
+    """The records of ``hits`` with ``score >= left_floor[i]`` and ``score >= right_floor[j]`` (each array float64 by
+    caller id, or None for no floor on that side), in canonical order: the definition of a floor grid in terms of the
+    threshold grid's hits, and the host-side gate for hits that come from the general kernels.  The comparisons are exact;
+    a NaN floor admits nothing."""
+    keep = np.ones(len(hits), dtype=bool)
+    if left_floor is not None:
+        keep &= hits.score >= np.asarray(left_floor, dtype=np.float64)[hits.i]
+    if right_floor is not None:
+        keep &= hits.score >= np.asarray(right_floor, dtype=np.float64)[hits.j]
+    return _canonical(hits.score[keep], hits.i[keep], hits.j[keep])
+
+
+def best_of_hits(hits: Hits, margin: float = 0.0, mutual: bool = False, n_left: Optional[int] = None,
+                 n_right: Optional[int] = None) -> Hits:
+    """The definition of a best-match query on a threshold grid's hit list: the records with ``score >= lb[i] - margin``,
+    ``lb[i]`` the left item's largest score in ``hits``; with ``mutual`` also ``score >= rb[j] - margin`` for the right
+    item's.  One float64 subtraction, exact comparisons.  ``margin=0`` is every item's best match with all its ties, a
+    margin at least as large as the largest score gives ``hits`` back.  Canonical order."""
+    m = check_margin(margin)
+    lb, rb = _best_scores(hits, n_left, n_right)
+    return filter_by_floors(hits, lb - m, rb - m if mutual else None)
+
+
+def _floor_column(floor, ids: int, device, what: str) -> Optional[torch.Tensor]:
+    """A floor array as the float64 device column the C entries read: one entry per caller id, reaching at least to the
+    table's largest (``ids`` = that id + 1) -- the kernels index it with the table's ``orig`` values."""
+    if floor is None:
+        return None
+    if isinstance(floor, torch.Tensor):
+        if floor.dim() != 1 or floor.dtype != torch.float64:
+            raise ValueError(f"{what}: floors must be a one-dimensional float64 tensor")
+        col = floor.to(device).contiguous()
+    else:
+        arr = np.ascontiguousarray(floor, dtype=np.float64)
+        if arr.ndim != 1:
+            raise ValueError(f"{what}: floors must be a one-dimensional float64 array")
+        col = torch.from_numpy(arr).to(device)
+    if int(col.shape[0]) < ids:
+        raise ValueError(f"{what}: {int(col.shape[0])} floors for caller ids up to {ids - 1}")
+    return col
+
+
+def _floor_grid(entry: str, structs: list, middle: tuple, left, right, device, threshold: float, left_floor, right_floor,
+                stats: Optional[list], capacity: Optional[int]) -> Hits:
+    """A floor grid through the C entry ``entry``: ``structs`` the tables in the entry's argument order, ``middle`` what it
+    takes between the floors and the hit buffer, ``left`` / ``right`` the two tables whose caller ids the floors go by."""
+    dev = _require_gpu(device)
+    fn = getattr(_lib.load(), entry)
+    ids_l, ids_r = _left_id_limit(left.orig, left.n), _left_id_limit(right.orig, right.n)
+    lf = _floor_column(left_floor, ids_l, dev, entry + ": left_floor")
+    rf = _floor_column(right_floor, ids_r, dev, entry + ": right_floor")
+    st = torch.zeros(4, dtype=torch.int64, device=dev)
+    ptr = lambda t: 0 if t is None or t.numel() == 0 else t.data_ptr()
+
+    def launch(buf: HitBuffer, stream: int) -> int:
+        st.zero_()  # (a retry at a larger capacity sweeps again)
+        return fn(*structs, float(threshold), ptr(lf), ptr(rf), *middle, buf.records.data_ptr(), buf.capacity,
+                  buf.count.data_ptr(), st.data_ptr(), stream)
+
+    # (every reported id is below the larger limit: the sort's key width; an empty side reports nothing)
+    hits = run_grid(launch, dev, capacity, entry, id_limit=max(ids_l, ids_r) if ids_l and ids_r else 0)
+    if stats is not None:
+        stats[:] = [int(v) for v in st.tolist()]
+    return hits
+
+
+def indel_raw_floor_grid(left: StrTable, right: StrTable, threshold: float, left_floor=None, right_floor=None,
+                         prune: bool = True, stats: Optional[list] = None, capacity: Optional[int] = None) -> Hits:
+    """``filter_by_floors(indel_raw_grid(left, right, threshold), left_floor, right_floor)`` in one sweep of
+    ``nsm_indel_raw_floor_grid`` (the top-k kernel with a gate in place of its lists): a threshold grid whose threshold is
+    per item.  Floors: numpy float64 arrays or float64 tensors indexed by caller id, or None.  ``stats`` as for
+    ``indel_raw_top_k``."""
+    flags = _lib.FLAG_PRUNE if prune else 0
+    return _floor_grid("nsm_indel_raw_floor_grid", [left.struct(), right.struct()], (flags,), left, right, left.codes.device,
+                       threshold, left_floor, right_floor, stats, capacity)
+
+
+def jaccard_raw_floor_grid(left: SetTable, right: SetTable, threshold: float, left_floor=None, right_floor=None,
+                           prune: bool = True, stats: Optional[list] = None, capacity: Optional[int] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_raw_floor_grid``; preconditions as for ``jaccard_raw_top_k``."""
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    if left.has_empty and right.has_empty:
+        raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
+    flags = _lib.FLAG_PRUNE if prune else 0
+    return _floor_grid("nsm_jaccard_raw_floor_grid", [left.struct(), right.struct()], (flags,), left, right, left.ids.device,
+                       threshold, left_floor, right_floor, stats, capacity)
+
+
+def _levels_floor_grid(entry: str, tables: tuple, left, right, device, threshold: float, left_floor, right_floor,
+                       category_mode: int, prune: bool, banned, stats: Optional[list], capacity: Optional[int]) -> Hits:
+    if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
+        category_mode = left.category_mode
+    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), device)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    middle = (int(category_mode), _lib.FLAG_PRUNE if prune else 0, ptr(bs), ptr(bj))
+    return _floor_grid(entry, [t.struct() for t in tables], middle, left, right, device, threshold, left_floor, right_floor,
+                       stats, capacity)
+
+
+def indel_levels_floor_grid(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable,
+                            threshold: float, left_floor=None, right_floor=None, category_mode: int = _lib.CAT_NONE,
+                            prune: bool = True, banned=None, stats: Optional[list] = None,
+                            capacity: Optional[int] = None) -> Hits:
+    """``filter_by_floors`` of ``indel_levels_grid(...)`` without the ``banned`` pairs, in one sweep of
+    ``nsm_indel_levels_floor_grid`` (``indel_levels_top_k``'s arguments and preconditions: tables encoded with
+    ``partition=False``)."""
+    return _levels_floor_grid("nsm_indel_levels_floor_grid", (left, left_strings, right, right_strings), left, right,
+                              left.first.device, threshold, left_floor, right_floor, category_mode, prune, banned, stats, capacity)
+
+
+def jaccard_levels_floor_grid(left: SetTable, right: SetTable, threshold: float, left_floor=None, right_floor=None,
+                              category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
+                              stats: Optional[list] = None, capacity: Optional[int] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_levels_floor_grid`` (``jaccard_levels_top_k``'s preconditions)."""
+    if left.nlev is None or right.nlev is None:
+        raise ValueError("levels floor grid needs tables built with SetTable.from_levels")
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    return _levels_floor_grid("nsm_jaccard_levels_floor_grid", (left, right), left, right, left.ids.device, threshold,
+                              left_floor, right_floor, category_mode, prune, banned, stats, capacity)
+
+
+def floors_of_profile(prof: ThresholdProfile, margin: float, mutual: bool):
+    """(left_floor, right_floor) of a best-match query from the profile at its threshold: ``best - margin``, one float64
+    subtraction per item; no right floor unless ``mutual``.  An item without a hit (best -1.0) has nothing to admit."""
+    m = check_margin(margin)
+    return prof.left_best - m, (prof.right_best - m if mutual else None)
+
+
+def _best(profile: Callable, floor_grid: Callable, margin: float, threshold: float, mutual: bool, stats: Optional[list]) -> Hits:
+    """Best matches in two sweeps: ``profile([threshold], stats)`` for every item's best score, then
+    ``floor_grid(left_floor, right_floor, stats)`` with ``floor = best - margin``.  ``stats`` receives both sweeps'
+    counters: [the profile's four, the floor grid's four]."""
+    m = check_margin(margin)
+    t = check_thresholds([threshold])
+    st1, st2 = [], []
+    lf, rf = floors_of_profile(profile(t, st1), m, mutual)
+    hits = floor_grid(lf, rf, st2)
+    if stats is not None:
+        stats[:] = [st1, st2]
+    return hits
+
+
+def indel_raw_best(left: StrTable, right: StrTable, margin: float = 0.0, threshold: float = 0.0, mutual: bool = False,
+                   prune: bool = True, stats: Optional[list] = None) -> Hits:
+    """``best_of_hits(indel_raw_grid(left, right, threshold), margin, mutual)`` without the grid's hits: every left item's
+    best match with everything within ``margin`` of it (``margin=0``: all its ties), with ``mutual`` only the pairs that
+    are also within ``margin`` of the right item's best.  A profile sweep at ``[threshold]``, then a floor grid."""
+    return _best(lambda t, st: indel_raw_profile(left, right, t, prune=prune, stats=st),
+                 lambda lf, rf, st: indel_raw_floor_grid(left, right, threshold, lf, rf, prune=prune, stats=st),
+                 margin, threshold, mutual, stats)
+
+
+def jaccard_raw_best(left: SetTable, right: SetTable, margin: float = 0.0, threshold: float = 0.0, mutual: bool = False,
+                     prune: bool = True, stats: Optional[list] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_raw_best``; preconditions as for ``jaccard_raw_top_k``."""
+    return _best(lambda t, st: jaccard_raw_profile(left, right, t, prune=prune, stats=st),
+                 lambda lf, rf, st: jaccard_raw_floor_grid(left, right, threshold, lf, rf, prune=prune, stats=st),
+                 margin, threshold, mutual, stats)
+
+
+def indel_levels_best(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable,
+                      margin: float = 0.0, threshold: float = 0.0, mutual: bool = False, category_mode: int = _lib.CAT_NONE,
+                      prune: bool = True, banned=None, stats: Optional[list] = None) -> Hits:
+    """Best matches of ``indel_levels_grid(...)`` without the ``banned`` pairs (``indel_levels_top_k``'s preconditions)."""
+    tabs = (left, left_strings, right, right_strings)
+    return _best(lambda t, st: indel_levels_profile(*tabs, t, category_mode=category_mode, prune=prune, banned=banned, stats=st),
+                 lambda lf, rf, st: indel_levels_floor_grid(*tabs, threshold, lf, rf, category_mode=category_mode, prune=prune,
+                                                            banned=banned, stats=st),
+                 margin, threshold, mutual, stats)
+
+
+def jaccard_levels_best(left: SetTable, right: SetTable, margin: float = 0.0, threshold: float = 0.0, mutual: bool = False,
+                        category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
+                        stats: Optional[list] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_levels_best`` (``jaccard_levels_top_k``'s preconditions)."""
+    return _best(lambda t, st: jaccard_levels_profile(left, right, t, category_mode=category_mode, prune=prune, banned=banned, stats=st),
+                 lambda lf, rf, st: jaccard_levels_floor_grid(left, right, threshold, lf, rf, category_mode=category_mode,
+                                                              prune=prune, banned=banned, stats=st),
+                 margin, threshold, mutual, stats)
+
+
 # ------------------------------------------------------------------------------- listed pairs
 NO_SCORE = -1.0  # what a listed pair without a score gets (the profiles' "none")
 

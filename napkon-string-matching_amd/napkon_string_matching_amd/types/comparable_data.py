@@ -348,6 +348,8 @@ class ComparableData:
         identifier_column_right: Optional[str] = None,
         *args,
         top_k: Optional[int] = None,
+        best_margin: Optional[float] = None,
+        mutual_best: bool = False,
         **kwargs,
     ) -> Comparable:
         """:69-128.  Scores at ``cache_threshold or score_threshold``, keeps ``>= score_threshold``,
@@ -357,6 +359,15 @@ class ComparableData:
         ascending) -- the frame ``compare()`` returns without it, restricted to those pair labels (rapidfuzz's
         ``process.extract(limit=)`` over ``compare_terms``).  Each item's pairs are cut in score order, so cutting at
         ``cache_threshold`` and then filtering at ``score_threshold`` keeps the meaning of both.
+
+        ``best_margin`` (a finite number >= 0): keep only the pairs within ``best_margin`` of their left item's best score --
+        the frame ``compare()`` returns without it (after ``dropna``, whitelist removal, blacklist and categories; zero-level
+        pairs, which score 0, count as rows like any other), restricted to ``score >= best[left item] - best_margin``.  0.0
+        is every item's best match with all its ties, which no ``top_k`` returns.  ``mutual_best=True``: a pair must also be
+        within ``best_margin`` of its RIGHT item's best (reciprocal best hits).  The bests are taken at ``cache_threshold``
+        and the rows filtered at ``score_threshold`` afterwards, which keeps the meaning: an item whose best is below
+        ``score_threshold`` has no rows either way, and one whose best is above it has the same best at both thresholds.
+        Restrictions as for ``top_k`` (at most 64 category labels; one rank); not together with ``top_k``.
 
         Compare cache: the reference keys ``compared__score_{md5}.json`` by a hash
         that embeds object addresses (``str(kwargs.items())`` of ``Mapping`` objects, :61-67), so it
@@ -368,12 +379,13 @@ class ComparableData:
         """
         if top_k is not None:
             top_k = grid.check_k(top_k)
+        best_margin = _check_best_args(best_margin, mutual_best, top_k)
         first = cache_threshold if cache_threshold else score_threshold
         cache_file = None
         if cached and cache_dir is not None:
             cache_file = Path(cache_dir) / CACHE_FILE_PATTERN.format(
                 self._hash_compare_args(other, existing_mappings_whitelist, existing_mappings_blacklist,
-                                        compare_column, first, kwargs, top_k))
+                                        compare_column, first, kwargs, top_k, best_margin, mutual_best))
         # hit or miss is decided ONCE for all ranks of a sharded run (rank 0 looks, everybody follows): with a
         # rank-local exists() the ranks can disagree -- a cache_dir that is not shared between nodes, or a repeated
         # compare() where one rank looks before rank 0's rename has landed -- and the ranks that miss would then
@@ -397,6 +409,8 @@ class ComparableData:
                 identifier_column_left=identifier_column_left,
                 identifier_column_right=identifier_column_right,
                 top_k=top_k,
+                best_margin=best_margin,
+                mutual_best=mutual_best,
                 **kwargs,
             )
             if cache_file is not None:
@@ -434,26 +448,13 @@ class ComparableData:
         t = grid.check_thresholds(thresholds)
         if distributed.world()[1] > 1:
             raise NotImplementedError("compare_profile on more than one rank (sharded profiles are not implemented)")
-        for name in ("score_threshold", "cached", "cache_threshold", "cache_dir", "top_k"):
+        for name in ("score_threshold", "cached", "cache_threshold", "cache_dir", "top_k", "best_margin", "mutual_best"):
             kwargs.pop(name, None)
         pre = self._compare_prelude(
             other, existing_mappings_whitelist, existing_mappings_blacklist, kwargs.get("score_func"), compare_column,
             kwargs.get("category_column", "Category"), kwargs.get("left_name"), kwargs.get("right_name"),
             kwargs.get("filter_categories", False), identifier_column_left, identifier_column_right, per_item="a threshold profile")
-        parts = []
-        if pre.keep_l.size and pre.keep_r.size:
-            on_device = pre.cats is not None
-            parts.append((_levels_grid(
-                pre.plugin, [pre.levels_l[k] for k in pre.keep_l], [pre.levels_r[k] for k in pre.keep_r], float(t[0]),
-                pre.cats.left_mask[pre.keep_l] if on_device else None, pre.cats.right_mask[pre.keep_r] if on_device else None,
-                pre.cats.mode if on_device else _lib.CAT_NONE, banned=_local_banned(pre.banned, pre.keep_l, pre.keep_r),
-                profile=t), pre.keep_l, pre.keep_r))
-        if pre.extra_hits:  # zero-level x zero-level pairs score 0
-            ei = np.array([p[0] for p in pre.extra_hits], dtype=np.int32)
-            ej = np.array([p[1] for p in pre.extra_hits], dtype=np.int32)
-            parts.append((grid.profile_of_hits(grid.Hits(np.zeros(len(ei)), ei, ej), t, pre.n_l, pre.n_r), np.arange(pre.n_l),
-                          np.arange(pre.n_r)))
-        return grid.merge_profiles(parts, t, pre.n_l, pre.n_r)
+        return _prelude_profile(pre, t)
 
     def score_pairs(self, other, pairs, compare_column: str = None, score_func: str = None,
                     identifier_column_left: Optional[str] = None, identifier_column_right: Optional[str] = None,
@@ -529,7 +530,8 @@ class ComparableData:
         out[MATCH_SCORE] = score
         return Comparable(data=pd.DataFrame(out), left_name=pre.lp, right_name=pre.rp)
 
-    def _hash_compare_args(self, other, whitelist, blacklist, compare_column, cache_threshold, kwargs, top_k=None) -> str:
+    def _hash_compare_args(self, other, whitelist, blacklist, compare_column, cache_threshold, kwargs, top_k=None,
+                           best_margin=None, mutual_best=False) -> str:
         other_csv = other.to_csv() if hasattr(other, "to_csv") else pd.DataFrame(other).to_csv(index=False)
         parts = [
             self.to_csv(), other_csv,
@@ -541,6 +543,10 @@ class ComparableData:
         ]
         if top_k is not None:  # (absent from the key otherwise: the keys of plain calls stay what they were)
             parts.append(f"top_k={int(top_k)}")
+        if best_margin is not None:
+            parts.append(f"best_margin={float(best_margin)!r}")
+            if mutual_best:
+                parts.append("mutual_best=True")
         return md5("\x1f".join(parts).encode("utf-8"), usedforsecurity=False).hexdigest()
 
     def _compare_prelude(self, right, existing_mappings_whitelist, existing_mappings_blacklist, score_func, compare_column,
@@ -637,15 +643,23 @@ class ComparableData:
         identifier_column_right: Optional[str] = None,
         *args,
         top_k: Optional[int] = None,
+        best_margin: Optional[float] = None,
+        mutual_best: bool = False,
         **kwargs,
     ) -> Comparable:
         """:133-246 (steps 1-12 of SURVEY.md 3.2), the per-pair part on the GPU.  ``top_k``: per left item only the
-        first ``top_k`` pairs (score descending, right item ascending) of what would be returned (``compare``)."""
+        first ``top_k`` pairs (score descending, right item ascending) of what would be returned (``compare``).
+        ``best_margin`` / ``mutual_best``: only the pairs within ``best_margin`` of their left (and right) item's best score
+        among what would be returned (``compare``): a profile sweep for the bests, then a floor grid."""
         if top_k is not None:
             top_k = grid.check_k(top_k)
+        best_margin = _check_best_args(best_margin, mutual_best, top_k)
+        if best_margin is not None and distributed.world()[1] > 1:
+            raise NotImplementedError("best_margin on more than one rank (sharded best matches are not implemented)")
         pre = self._compare_prelude(right, existing_mappings_whitelist, existing_mappings_blacklist, score_func, compare_column,
                                     category_column, left_name, right_name, filter_categories, identifier_column_left,
-                                    identifier_column_right, per_item=None if top_k is None else "top_k")
+                                    identifier_column_right,
+                                    per_item="top_k" if top_k is not None else "best_margin" if best_margin is not None else None)
         plugin, lf, rf, lp, rp, n_l, n_r = pre.plugin, pre.lf, pre.rf, pre.lp, pre.rp, pre.n_l, pre.n_r
         levels_l, levels_r, argument_l, argument_r = pre.levels_l, pre.levels_r, pre.argument_l, pre.argument_r
         banned, cats, nlev_l, nlev_r, extra_hits, keep_l, keep_r = (pre.banned, pre.cats, pre.nlev_l, pre.nlev_r, pre.extra_hits,
@@ -661,7 +675,26 @@ class ComparableData:
         logger.info("calculate score")
         host_filter = bool(banned) or (cats is not None and not cats.on_device)
         pending = None
-        if keep_l.size and keep_r.size and top_k is not None:
+        floors = None
+        if best_margin is not None:
+            # pass 1: every item's best score over the frame a plain call returns (zero-level pairs included); pass 2 below
+            # emits what reaches floor = best - margin.  Categories and blacklist run in the kernel in both passes
+            floors = grid.floors_of_profile(_prelude_profile(pre, grid.check_thresholds([score_threshold])), best_margin,
+                                            mutual_best)
+        if keep_l.size and keep_r.size and floors is not None:
+            on_device = cats is not None
+            hits = _levels_grid(
+                plugin,
+                [levels_l[k] for k in keep_l],
+                [levels_r[k] for k in keep_r],
+                score_threshold,
+                cats.left_mask[keep_l] if on_device else None,
+                cats.right_mask[keep_r] if on_device else None,
+                cats.mode if on_device else _lib.CAT_NONE,
+                banned=_local_banned(banned, keep_l, keep_r),
+                floors=(floors[0][keep_l], None if floors[1] is None else floors[1][keep_r]),
+            )
+        elif keep_l.size and keep_r.size and top_k is not None:
             # per-item lists on the device: categories and blacklist go to the kernel, which keeps each item's best
             on_device = cats is not None
             hits = _levels_grid(
@@ -712,6 +745,9 @@ class ComparableData:
             if extra:
                 ei = np.array([p[0] for p in extra_hits], dtype=np.int64)
                 ej = np.array([p[1] for p in extra_hits], dtype=np.int64)
+                if floors is not None:  # (a zero-level pair is a row like any other: it passes the same gate)
+                    gated = grid.filter_by_floors(grid.Hits(np.zeros(len(ei)), ei, ej), floors[0], floors[1])
+                    ei, ej = gated.i, gated.j
                 hi, hj, hs = np.concatenate([hi, ei]), np.concatenate([hj, ej]), np.concatenate([hs, np.zeros(len(ei))])
 
             if top_k is not None:
@@ -719,7 +755,7 @@ class ComparableData:
                 sel = grid.select_top_k(grid.Hits(hs, hi, hj), top_k)
                 hi, hj, hs = sel.i, sel.j, sel.score
             # ---- per hit: blacklist (and categories when they could not go to the device)
-            elif len(hs) and host_filter:
+            elif floors is None and len(hs) and host_filter:
                 ok = np.fromiter(
                     (
                         (int(a), int(b)) not in banned and (cats is None or cats.on_device or cats.match(int(a), int(b)))
@@ -773,6 +809,38 @@ def _resolve_plugin(score_func):
     raise NotImplementedError(
         "only this package's score functions (intersection_vs_union, fuzzy_match) have a device implementation"
     )
+
+
+def _check_best_args(best_margin, mutual_best, top_k):
+    """``best_margin`` / ``mutual_best`` of ``compare``: the margin as a float (None: no best filter), else ``ValueError`` --
+    before any device work."""
+    if best_margin is None:
+        if mutual_best:
+            raise ValueError("mutual_best needs best_margin (0.0: exact best matches)")
+        return None
+    if top_k is not None:
+        raise ValueError("best_margin and top_k cannot be combined")
+    return grid.check_margin(best_margin)
+
+
+def _prelude_profile(pre, t) -> grid.ThresholdProfile:
+    """The threshold profile of the frame ``compare`` returns for the prelude ``pre`` (``_compare_prelude``), by position
+    in the compared frames: the device grid's over the items with levels, merged with the zero-level x zero-level pairs,
+    which score 0.  Categories and blacklist run in the kernel."""
+    parts = []
+    if pre.keep_l.size and pre.keep_r.size:
+        on_device = pre.cats is not None
+        parts.append((_levels_grid(
+            pre.plugin, [pre.levels_l[k] for k in pre.keep_l], [pre.levels_r[k] for k in pre.keep_r], float(t[0]),
+            pre.cats.left_mask[pre.keep_l] if on_device else None, pre.cats.right_mask[pre.keep_r] if on_device else None,
+            pre.cats.mode if on_device else _lib.CAT_NONE, banned=_local_banned(pre.banned, pre.keep_l, pre.keep_r),
+            profile=t), pre.keep_l, pre.keep_r))
+    if pre.extra_hits:  # zero-level x zero-level pairs score 0
+        ei = np.array([p[0] for p in pre.extra_hits], dtype=np.int32)
+        ej = np.array([p[1] for p in pre.extra_hits], dtype=np.int32)
+        parts.append((grid.profile_of_hits(grid.Hits(np.zeros(len(ei)), ei, ej), t, pre.n_l, pre.n_r), np.arange(pre.n_l),
+                      np.arange(pre.n_r)))
+    return grid.merge_profiles(parts, t, pre.n_l, pre.n_r)
 
 
 def _banned_positions(pairs, id_l: Sequence, id_r: Sequence) -> set:
@@ -855,12 +923,13 @@ def _may_be_wide_sets(*sides) -> bool:
 
 
 def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, defer=False, top_k=None,
-                         banned=None, profile=None):
+                         banned=None, profile=None, floors=None):
     """The suffix-nested fast layout of both sides + ``nsm_jaccard_levels_grid``; raises ``tables.IrregularLevels`` when an
     item does not fit it.  ``top_k``: ``nsm_jaccard_levels_top_k`` instead, without the ``banned`` pairs (tables without a
     category partition and without an inverted index).  ``profile`` (a ladder of thresholds): ``nsm_jaccard_levels_profile``
-    on the same tables."""
-    per_item = top_k is not None or profile is not None
+    on the same tables.  ``floors`` ((left, right) arrays by position, the right one or None):
+    ``nsm_jaccard_levels_floor_grid`` on the same tables."""
+    per_item = top_k is not None or profile is not None or floors is not None
     part = False if per_item else tables.partition_allowed(cat_mode, cat_l, cat_r)
     index = False if per_item else None
     memo = ComparableData._item_memo
@@ -892,6 +961,8 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
         raise NotImplementedError("vocabulary of 2^25 or more distinct tokens")
     if profile is not None:
         return grid.jaccard_levels_profile(lt, rt, profile, category_mode=cat_mode, banned=banned)
+    if floors is not None:
+        return grid.jaccard_levels_floor_grid(lt, rt, threshold, floors[0], floors[1], category_mode=cat_mode, banned=banned)
     if top_k is not None:
         return grid.jaccard_levels_top_k(lt, rt, top_k, threshold, category_mode=cat_mode, banned=banned)
     # the library picks the inverted-index kernel from the threshold alone (it cannot see the vocabulary); the host
@@ -902,7 +973,7 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
 
 
 def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_lib.CAT_NONE, defer: bool = False, top_k=None,
-                 banned=None, profile=None):
+                 banned=None, profile=None, floors=None):
     """Encode both sides' levels for ``plugin`` and run the levels grid on the current device.  ``defer``: when the
     whole grid goes through ONE fast kernel call, return its hits still on the device (``grid.PendingHits``: the sharded
     ``gen_comparable`` exchanges them without a host detour); grids that are split (wide / irregular items) return
@@ -916,7 +987,12 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
 
     ``profile`` (a validated ladder, ``threshold`` its first entry): the grid's ``grid.ThresholdProfile`` without the
     ``banned`` pairs instead of its hits, routed like a top-k query -- ``nsm_*_levels_profile`` for the items the fast
-    kernels take, ``grid.profile_of_hits`` of the general kernels' hits for the rest, merged."""
+    kernels take, ``grid.profile_of_hits`` of the general kernels' hits for the rest, merged.
+
+    ``floors`` ((left floors, right floors or None), float64 by position in these lists): only the records of that grid
+    without the ``banned`` pairs that reach both their items' floors (``grid.filter_by_floors``), routed like a top-k
+    query -- ``nsm_*_levels_floor_grid`` with the floors gathered to the sub-tables for the items the fast kernels take, the
+    general kernels' hits gated on the host for the rest."""
     import torch
 
     if not torch.cuda.is_available():
@@ -927,9 +1003,13 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
     # (idx None: the whole side)
     sub = lambda seq, idx: seq if idx is None else [seq[k] for k in idx]
     cut = lambda cat, idx: cat if cat is None or idx is None else np.asarray(cat)[np.asarray(idx, dtype=np.int64)]
+    cut_floors = lambda li, ri: None if floors is None else (cut(floors[0], li), cut(floors[1], ri))
 
     def split_grid(split, fast, general):
         """The parts of a split grid, merged; a top-k query cuts the general parts and the merged result per item."""
+        if floors is not None:
+            gate = lambda li, ri: grid.filter_by_floors(_drop_banned(general(li, ri), banned, li, ri), *cut_floors(li, ri))
+            return wide.split_grid(split[0], split[1], fast, gate)
         if profile is not None:
             tally = lambda li, ri: grid.profile_of_hits(_drop_banned(general(li, ri), banned, li, ri), profile, len(li), len(ri))
             return wide.split_profile(split, len(levels_l), len(levels_r), profile, fast, tally)
@@ -945,7 +1025,7 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
             # path (wide.py: general kernel, every step's level sets scored on their own); the rest is scored as always
             fast = lambda li, ri: _levels_grid(plugin, sub(levels_l, li), sub(levels_r, ri), threshold, cut(cat_l, li),
                                                cut(cat_r, ri), cat_mode, top_k=top_k, banned=_restrict_banned(banned, li, ri),
-                                               profile=profile)
+                                               profile=profile, floors=cut_floors(li, ri))
             general = lambda li, ri: wide.jaccard_any_grid(
                 [as_set_levels(levels_l[k]) for k in li], [as_set_levels(levels_r[k]) for k in ri], threshold, cut(cat_l, li),
                 cut(cat_r, ri), cat_mode, device=dev)
@@ -957,7 +1037,7 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
             return split_route(split)
         try:
             return _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev,
-                                        defer and top_k is None, top_k, banned, profile)
+                                        defer and top_k is None and floors is None, top_k, banned, profile, floors)
         except tables.IrregularLevels:
             # the reference scores whatever its tokenizer yields per level (:283-299): find the items the nested layout
             # cannot hold and route only them
@@ -975,6 +1055,11 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
             a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
                                                      partition=False)
             return grid.indel_levels_profile(a, b, c, d, profile, category_mode=cat_mode, banned=_restrict_banned(banned, li, ri))
+        if floors is not None:
+            a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
+                                                     partition=False)
+            return grid.indel_levels_floor_grid(a, b, c, d, threshold, *cut_floors(li, ri), category_mode=cat_mode,
+                                                banned=_restrict_banned(banned, li, ri))
         if top_k is None:
             a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode)
             return grid.indel_levels_grid(a, b, c, d, threshold, category_mode=cat_mode, defer=defer)
