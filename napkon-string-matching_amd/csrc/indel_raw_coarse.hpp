@@ -20,20 +20,30 @@
 //           choice on both operands, so the order of k inside the instruction does not matter) are built once from the
 //           right fine histograms.  Left rows come in blocks of 32 of one length class: lane l loads 16 bytes of row l & 31,
 //           makes its CAP A fragments with byte-parallel arithmetic ([c >= k] = ((c + 0x80 - k) & 0x80) >> 7 per byte,
-//           counts <= 64) and per tile CAP MFMAs are chained on one accumulator.  The 16 results of a lane (rows
+//           counts <= 64) and per tile CAP MFMAs are chained on an accumulator.  The 16 results of a lane (rows
 //           (i & 3) + 8 (i >> 2) + 4 (l >> 5) of the block, column l & 31 of the tile) are folded with v_max3_i32 and compared
-//           with the lane's need once; only where some lane passes are the 16 compared one by one.  The last block of a class
-//           in a chunk repeats its last row, and the bits of the rows that do not exist are masked off;
+//           with the lane's need once; only where some lane passes is the 16-bit mask made, a full-rate v_sub_u32 and a
+//           v_alignbit_b32 per result (the sign of need - 1 - D, shifted in from below).  The last block of a class in a chunk
+//           repeats its last row, and the bits of the rows that do not exist are masked off;
+//   order   TWO accumulators, tile t in acc[t & 1] (NSM_C3C_PIPE, NT even): the chain of tile t + 1 -- after a block's last
+//           tile that of tile 0 of the class's next block, whose A fragments are made just before -- is issued before the
+//           branch and the push of tile t, its MFMAs with the v_max3_i32 of tile t's fold between them (a chained MFMA waits
+//           for the one before it, and a wave issues in order), so the matrix pipe works under the wave's own epilogue and
+//           not only under those of the SIMD's other waves.  The pipeline is filled at the start of a length class and is empty at its end,
+//           and it is emptied in front of a drain (no accumulator lives across one); NSM_C3C_PIPE=0 is the order of before,
+//           chain, fold, chain, fold on one accumulator;
 //   stack   lanes whose 16-bit mask is not empty push (block's first row, la, tile, lane, mask) on the wave's LDS stack: one
 //           ballot and one ds_write per tile of 1024 pairs;
-//   drain   whenever fewer than NT x 64 slots are free, 64 entries at a time (64 of 64 lanes busy): lane = one entry, ONE of
+//   drain   whenever more than 128 entries are on the stack, checked every NT tiles (in front of a block's last tile, whose
+//           entries are still pushed before the drain runs, and at the start of a class), 64 entries at a time (64 of 64
+//           lanes busy): lane = one entry, ONE of
 //           its pairs (an entry with more pairs goes back on the stack) -- the exact 32-bucket L1 of the pair (the left
 //           histogram gathered from global memory, the right one read from the wave's copy in LDS, 8 v_sad_u8), then, for
 //           those that remain, the bit-parallel LCS of the pair on the SCALAR unit (raw_lcs_pair).  Entries carry their
 //           row and its length, so the stack outlives the length classes and is emptied once, at the end.
 //
 // Every test that drops a pair is an upper bound of the LCS: the hits are the one-stage kernel's, the exhaustive kernel's and
-// the oracle's.  Measurements: profiles/c3_mfma_ab.txt and DESIGN 4.3.
+// the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt and DESIGN 4.3.
 #pragma once
 
 namespace nsm {
@@ -44,12 +54,18 @@ namespace nsm {
 #ifndef NSM_C3C_NT
 #define NSM_C3C_NT 4  // right tiles of 32 strings per wave
 #endif
+#ifndef NSM_C3C_PIPE
+#define NSM_C3C_PIPE (NSM_C3C_NT % 2 == 0)  // 1: two accumulators, a tile's MFMAs are issued around the fold of the tile before
+#endif
 #ifndef NSM_C3C_BRANCHFREE
 #define NSM_C3C_BRANCHFREE 0  // 1: every tile builds its 16-bit masks, no fold and no branch
 #endif
 constexpr int kC3cBlock = 32;                  // left rows per block = right strings per tile: the M and N of the MFMA
 constexpr int kC3cRights = NSM_C3C_NT * kC3cBlock;  // right strings per wave
-constexpr int kC3cStack = (NSM_C3C_NT + 2) * kWave;  // entries per wave; drained when fewer than NT x 64 slots are left
+// entries per wave; drained when more than kC3cDrainAt are on it.  NT x 64 pushes between two drain checks, and the pipelined scan
+// pushes one more tile's before the drain it has decided on runs (the pipeline is emptied first)
+constexpr int kC3cStack = (NSM_C3C_NT + 2 + (NSM_C3C_PIPE ? 1 : 0)) * kWave;
+constexpr int kC3cDrainAt = 2 * kWave;
 // a stack entry: low word = the pass mask of 16 left rows (bit i: row (i & 3) + 8 (i >> 2) + 4 (lane >> 5) of the block) against
 // right string tile * 32 + (lane & 31) of the wave, high word = (block's first row - chunk start) << 15 | la << 8 | tile << 6 | lane
 // (a chunk has at most 2^15 rows: nsm_indel_raw_grid)
@@ -83,10 +99,11 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const int32_t* __restrict__ rlen, const int32_t* __restrict__ rorig, const uint32_t* __restrict__ rhist,
     nsm_hit* __restrict__ hits, unsigned long long* __restrict__ count, const IndelRawParams p) {
   constexpr int kRights = NT * kC3cBlock;
-  // the stack's invariant: a block starts with at most kC3cStack - NT x 64 entries (above that the drain runs first, down to
-  // fewer than 64) and pushes at most NT x 64, so no slot past kC3cStack is written; the drain's trigger level must itself be
-  // at least 64, so that it only ever runs full passes
-  static_assert(kC3cStack - NT * kWave >= kWave, "the drain is triggered above kC3cStack - NT x 64 entries and runs full passes");
+  // the stack's invariant: a drain check leaves at most kC3cDrainAt entries (above that the drain runs, down to fewer than 64;
+  // in the pipelined scan after one more tile's pushes) and at most NT x 64 are pushed before the next check, so no slot past
+  // kC3cStack is written; the drain's trigger level must itself be at least 64, so that it only ever runs full passes
+  static_assert(kC3cDrainAt >= kWave && kC3cDrainAt + (NT + (NSM_C3C_PIPE ? 1 : 0)) * kWave <= kC3cStack,
+                "the drain is triggered above kC3cDrainAt entries and runs full passes");
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_mem[];
   unsigned long long* s_stack = s_mem;
   uint32_t* s_rh = reinterpret_cast<uint32_t*>(s_stack + kWavesPerBlock * kC3cStack);
@@ -122,14 +139,12 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   }
   // the B fragments: lane = right string col of tile t, buckets 16 half .. + 15; rows that do not exist are zero
   bool valid[NT];
-  int lbj[NT];
   c3c_v4i bfrag[NT][CAP];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int j = j0 + t * kC3cBlock + col;
     valid[t] = j < p.n_right;
     const int jcl = valid[t] ? j : p.n_right - 1;
-    lbj[t] = valid[t] ? rlen[jcl] : 0;
     uint4 f = reinterpret_cast<const uint4*>(rhist + static_cast<size_t>(jcl) * 8)[half];
     if (!valid[t]) f = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
@@ -234,79 +249,149 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     if (a >= b) continue;
     const int la = 64 - c;
     // per tile: the lane's right string can only hit a row of this class if D >= need (kNever: it cannot fit)
-    int need[NT];
+    int nm1[NT];  // need - 1: "D > nm1" is the fold's test, and the sign of nm1 - D is a pair's pass bit
     bool some = false;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int nd = valid[t] ? need_of(la, lbj[t]) : static_cast<int>(kNever);
-      const bool fits = min(la, lbj[t]) >= nd;  // exact length filter: LCS <= min(la, lb)
+      const int lb = rl_lds[t * kC3cBlock + col];  // (from the wave's copy: no register holds it across the classes)
+      const int nd = valid[t] ? need_of(la, lb) : static_cast<int>(kNever);
+      const bool fits = min(la, lb) >= nd;  // exact length filter: LCS <= min(la, lb)
       some = some || fits;
-      need[t] = fits ? nd : static_cast<int>(kNever);
+      nm1[t] = (fits ? nd : static_cast<int>(kNever)) - 1;
     }
     if (!__any(some)) continue;
 
-    const uint32_t entry_hi = (static_cast<uint32_t>(la) << 8) | static_cast<uint32_t>(lane);
     // the lane's 16 bytes of row i + col (the class's last row again past its end)
     auto load_rows = [&](int i) -> uint4 {
       return reinterpret_cast<const uint4*>(lhist + static_cast<size_t>(min(i + col, b - 1)) * 8)[half];
     };
+    // the A fragments of a block: CAP - 1 indicator slots and the excess
+    c3c_v4i afrag[CAP];
+    auto make_afrag = [&](const uint4& w) {
+      uint32_t ex[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int s = 0; s < CAP - 1; ++s) {
+        const uint32_t g0 = c3c_ge(w.x, s + 1), g1 = c3c_ge(w.y, s + 1), g2 = c3c_ge(w.z, s + 1), g3 = c3c_ge(w.w, s + 1);
+        afrag[s].x = static_cast<int>(g0); afrag[s].y = static_cast<int>(g1);
+        afrag[s].z = static_cast<int>(g2); afrag[s].w = static_cast<int>(g3);
+        ex[0] -= g0; ex[1] -= g1; ex[2] -= g2; ex[3] -= g3;  // (bytewise: an indicator never exceeds its count)
+      }
+      afrag[CAP - 1].x = static_cast<int>(ex[0]); afrag[CAP - 1].y = static_cast<int>(ex[1]);
+      afrag[CAP - 1].z = static_cast<int>(ex[2]); afrag[CAP - 1].w = static_cast<int>(ex[3]);
+    };
+    // the CAP chained MFMAs of the current block against tile t
+    auto chain = [&](int t) -> c3c_v16i {
+      c3c_v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int s = 0; s < CAP; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[s], bfrag[t][s], acc, 0, 0, 0);
+      return acc;
+    };
+    // fold, compare and push of tile t of the block at row i (exist: the lane's 16 rows of that block that exist)
+    auto fold = [&](const c3c_v16i& acc) -> int {
+      int top = max(max(acc[0], acc[1]), acc[2]);
+#pragma unroll
+      for (int k = 3; k < 15; k += 2) top = max(max(top, acc[k]), acc[k + 1]);
+      return max(top, acc[15]);
+    };
+    auto finish = [&](int top, const c3c_v16i& acc, int t, int i, uint32_t exist) {
+#if !NSM_C3C_BRANCHFREE
+      if (!__any(top > nm1[t])) return;
+#endif
+      // bit k = [acc[k] >= need]: the sign of need - 1 - acc[k], shifted in from below (k = 15 first)
+      uint32_t mask = 0;
+#pragma unroll
+      for (int k = 15; k >= 0; --k) mask = __builtin_amdgcn_alignbit(mask, static_cast<uint32_t>(nm1[t] - acc[k]), 31);
+      mask &= exist;
+      // lanes with a pair that passed push: one ballot and one ds_write per tile
+      const bool nz = mask != 0u;
+      const unsigned long long m = __ballot(nz);
+      if (m != 0ull) {
+        if (nz) {
+          const int slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), static_cast<uint32_t>(q_cnt)));
+          // (the wave-uniform part first: one v_or at the push instead of a register per tile)
+          const uint32_t hi = (static_cast<uint32_t>(i - i0) << 15) | (static_cast<uint32_t>(la) << 8) | (static_cast<uint32_t>(t) << 6);
+          uint32_t el = static_cast<uint32_t>(lane);
+          asm volatile("" : "+v"(el));  // (opaque: or-ed in here, not kept in a register per tile and class)
+          stack[slot] = (static_cast<unsigned long long>(hi | el) << 32) | mask;
+        }
+        q_cnt += __popcll(m);
+      }
+    };
+    // the lane's 16 rows of the block at row i that exist (all of them but in a class's last block)
+    auto exist_of = [&](int i) -> uint32_t {
+      const int n_rows = b - i;
+      const uint32_t rows = n_rows < kC3cBlock ? (1u << n_rows) - 1u : 0xffffffffu;  // (wave-uniform) bit r: row i + r exists
+      const uint32_t x = rows >> (4 * half);  // bit k of the result = bit (k & 3) + 8 (k >> 2) of x
+      return (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);
+    };
     uint4 w_next = load_rows(a);
+#if NSM_C3C_PIPE
+    // software pipeline over the tiles and the blocks of the class: acc[t & 1] holds tile t, and the chain of the tile after
+    // (tile 0 of the next block after a block's last, with that block's A fragments) is issued around the fold and before
+    // the branch and the push of tile t, so that the matrix pipe works under the wave's own epilogue.  Filled here, empty
+    // again at the end of the class.
+    static_assert(NT % 2 == 0, "tile 0 of the next block takes the accumulator of tile NT: NT must be even (or NSM_C3C_PIPE=0)");
+    c3c_v16i acc[2];
+    if (q_cnt > kC3cDrainAt)  // (a class of one block has no other check in front of its first NT - 1 tiles)
+      while (q_cnt >= kWave) drain_pass();
+    make_afrag(w_next);
+    if (a + kC3cBlock < b) w_next = load_rows(a + kC3cBlock);
+    acc[0] = chain(0);
+    for (int i = a; i < b; i += kC3cBlock) {
+      const uint32_t exist = exist_of(i);
+      const bool more = i + kC3cBlock < b;
+      // the drain check sits in front of a block's LAST tile: at most NT tiles, NT x 64 entries, between two checks.  Where
+      // the drain has to run, the pipeline is emptied first (one more tile's entries: kC3cStack's extra 64 slots), so that
+      // no accumulator and no A fragment lives across the drain.
+      bool flush = false;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        if (t + 1 < NT) {
+          acc[(t + 1) & 1] = chain(t + 1);
+        } else {
+          flush = q_cnt > kC3cDrainAt;
+          if (more && !flush) {
+            make_afrag(w_next);
+            if (i + 2 * kC3cBlock < b) w_next = load_rows(i + 2 * kC3cBlock);
+            acc[0] = chain(0);
+          }
+        }
+        // the fold of tile t goes BETWEEN the MFMAs of the chain (MFMA, 4 VALU, MFMA, 4 VALU, MFMA): a wave issues in order and
+        // a chained MFMA waits for the one before it, so a fold behind the whole chain would start 64 cycles later.  The
+        // branch ends the scheduling region: the chain cannot sink below it
+        const int top = fold(acc[t & 1]);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        finish(top, acc[t & 1], t, i, exist);
+      }
+      if (flush) {
+        while (q_cnt >= kWave) drain_pass();  // full passes only: the rest waits for more
+        if (more) {
+          make_afrag(w_next);
+          if (i + 2 * kC3cBlock < b) w_next = load_rows(i + 2 * kC3cBlock);
+          acc[0] = chain(0);
+        }
+      }
+    }
+#else
     for (int i = a; i < b; i += kC3cBlock) {
       const uint4 w = w_next;
       if (i + kC3cBlock < b) w_next = load_rows(i + kC3cBlock);
       // a block pushes up to NT x 64 entries
-      if (q_cnt > kC3cStack - NT * kWave)
+      if (q_cnt > kC3cDrainAt)
         while (q_cnt >= kWave) drain_pass();  // full passes only: the rest waits for more
-      // the A fragments: CAP - 1 indicator slots and the excess
-      c3c_v4i afrag[CAP];
-      {
-        uint32_t ex[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int s = 0; s < CAP - 1; ++s) {
-          const uint32_t g0 = c3c_ge(w.x, s + 1), g1 = c3c_ge(w.y, s + 1), g2 = c3c_ge(w.z, s + 1), g3 = c3c_ge(w.w, s + 1);
-          afrag[s].x = static_cast<int>(g0); afrag[s].y = static_cast<int>(g1);
-          afrag[s].z = static_cast<int>(g2); afrag[s].w = static_cast<int>(g3);
-          ex[0] -= g0; ex[1] -= g1; ex[2] -= g2; ex[3] -= g3;  // (bytewise: an indicator never exceeds its count)
-        }
-        afrag[CAP - 1].x = static_cast<int>(ex[0]); afrag[CAP - 1].y = static_cast<int>(ex[1]);
-        afrag[CAP - 1].z = static_cast<int>(ex[2]); afrag[CAP - 1].w = static_cast<int>(ex[3]);
-      }
-      // the lane's 16 rows of the block that exist (all of them but in a class's last block)
-      const int n_rows = b - i;
-      uint32_t exist = 0xffffu;
-      if (n_rows < kC3cBlock) {
-        exist = 0u;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) exist |= ((k & 3) + 8 * (k >> 2) + 4 * half < n_rows ? 1u : 0u) << k;
-      }
+      make_afrag(w);
+      const uint32_t exist = exist_of(i);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        c3c_v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < CAP; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[s], bfrag[t][s], acc, 0, 0, 0);
-#if !NSM_C3C_BRANCHFREE
-        int top = max(max(acc[0], acc[1]), acc[2]);
-#pragma unroll
-        for (int k = 3; k < 15; k += 2) top = max(max(top, acc[k]), acc[k + 1]);
-        top = max(top, acc[15]);
-        if (!__any(top >= need[t])) continue;
-#endif
-        uint32_t mask = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) mask |= (acc[k] >= need[t] ? 1u : 0u) << k;
-        mask &= exist;
-        // lanes with a pair that passed push: one ballot and one ds_write per tile
-        const bool nz = mask != 0u;
-        const unsigned long long m = __ballot(nz);
-        if (m != 0ull) {
-          if (nz) {
-            const int slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), static_cast<uint32_t>(q_cnt)));
-            stack[slot] = (static_cast<unsigned long long>((static_cast<uint32_t>(i - i0) << 15) | (static_cast<uint32_t>(t) << 6) | entry_hi) << 32) | mask;
-          }
-          q_cnt += __popcll(m);
-        }
+        const c3c_v16i acc = chain(t);
+        finish(fold(acc), acc, t, i, exist);
       }
     }
+#endif
   }
   while (q_cnt > 0) drain_pass();
 }
