@@ -240,8 +240,9 @@ int nsm_jaccard_raw_grid(const nsm_set_table* left, const nsm_set_table* right, 
  * threshold grid above with a per-row rank cut.  It stands in for the reference's `score_func` over every pair
  * (compare/score_functions.py:6-27) when only the best few candidates of an item are wanted, as in the 1 x M use of
  * terminology/mesh.py:207-220 (rapidfuzz's process.extract(query, choices, scorer, limit, score_cutoff) for fuzzy_match).
- *   out        device, room for left->n * k records; the selected records are written in ANY order (nsm_sort_hits
- *              orders them); the output is bounded in advance: no capacity, no retry
+ *   out        device, room for left->n * k records, k as clamped below (left->n * min(k, right->n)); the selected
+ *              records are written in ANY order (nsm_sort_hits orders them); the output is bounded in advance: no
+ *              capacity, no retry
  *   out_count  device, caller zeroes; receives the number of records
  *   stats      device uint64[4] or NULL; per call (added to): [0] pairs in the right classes (len_start / size_start)
  *              that were visited, [1] pairs that passed the length / size bound, [2] pairs that passed the histogram /
@@ -593,7 +594,10 @@ int nsm_jaccard_any_grid(const nsm_any_sets* left, const nsm_any_sets* right, do
 
 /* In-place canonical ordering of the first min(*hit_count, capacity) hits:
  * score descending, then i, then j ascending.  `scratch` is a device buffer of the same capacity (may be NULL when at most
- * 8192 records can be live).
+ * 8192 records can be live).  With n_hint, and as long as the promise holds (at most n_hint records are live), the sort
+ * touches at most n_hint records of `scratch` and of `hits`: a scratch of n_hint records is enough and the records of `hits`
+ * from n_hint on stay as they are.  What the records of `hits` between the live ones and n_hint (n_hint == 0: `capacity`)
+ * hold afterwards is unspecified.  With more live records than promised, records of `hits` beyond n_hint may be moved too.
  *   n_hint    0, or the caller's promise that at most n_hint records are live (a host that has read the counter knows):
  *             the launch geometry then follows n_hint instead of capacity -- one launch up to 8192 records whatever the
  *             buffer's size.  With more live records than promised the order is unspecified (no record is lost).

@@ -12,7 +12,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
-import test_gpu_threshold_probes as probe_tables
+from support import probe_tables
 from support import best_matches as bm
 from support import threshold_probes as tp
 
@@ -42,12 +42,12 @@ def _calls(g, dev):
 
     cap = g.pairs  # (room for every pair: no retry)
     if g.raw:
-        lt, rt = probe_tables._raw_indel_tables(g, dev) if g.kind == "indel" else probe_tables._raw_jaccard_tables(g, dev)
+        lt, rt = probe_tables.raw_indel_tables(g, dev) if g.kind == "indel" else probe_tables.raw_jaccard_tables(g, dev)
         fg, best = (grid.indel_raw_floor_grid, grid.indel_raw_best) if g.kind == "indel" else \
             (grid.jaccard_raw_floor_grid, grid.jaccard_raw_best)
         return (lambda thr, lf, rf, prune, banned=None, stats=None: fg(lt, rt, thr, lf, rf, prune=prune, stats=stats, capacity=cap),
                 lambda m, thr, mutual, prune, banned=None, stats=None: best(lt, rt, m, thr, mutual, prune=prune, stats=stats))
-    tabs = probe_tables._levels_indel_tables(g, dev, False) if g.kind == "indel" else probe_tables._levels_jaccard_tables(g, dev, False)
+    tabs = probe_tables.levels_indel_tables(g, dev, False) if g.kind == "indel" else probe_tables.levels_jaccard_tables(g, dev, False)
     fg, best = (grid.indel_levels_floor_grid, grid.indel_levels_best) if g.kind == "indel" else \
         (grid.jaccard_levels_floor_grid, grid.jaccard_levels_best)
     return (lambda thr, lf, rf, prune, banned=None, stats=None: fg(*tabs, thr, lf, rf, category_mode=g.mode, prune=prune,
@@ -305,11 +305,11 @@ def _entry_calls(dev):
                         ("levels_jaccard-cat2_lanes", "nsm_jaccard_levels_floor_grid")):
         g = tp.grid(name)
         if g.raw:
-            tabs = probe_tables._raw_indel_tables(g, dev) if g.kind == "indel" else probe_tables._raw_jaccard_tables(g, dev)
+            tabs = probe_tables.raw_indel_tables(g, dev) if g.kind == "indel" else probe_tables.raw_jaccard_tables(g, dev)
             middle = (_lib.FLAG_PRUNE,)
         else:
-            tabs = probe_tables._levels_indel_tables(g, dev, False) if g.kind == "indel" else \
-                probe_tables._levels_jaccard_tables(g, dev, False)
+            tabs = probe_tables.levels_indel_tables(g, dev, False) if g.kind == "indel" else \
+                probe_tables.levels_jaccard_tables(g, dev, False)
             middle = (g.mode, _lib.FLAG_PRUNE, 0, 0)
         fn = getattr(lib, entry)
         out[entry] = (lambda thr, lf, rf, hits, cap, cnt, fn=fn, tabs=tabs, middle=middle: fn(

@@ -12,7 +12,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
-import test_gpu_threshold_probes as probe_tables
+from support import probe_tables
 from support import threshold_probes as tp
 
 pytestmark = pytest.mark.gpu
@@ -57,15 +57,15 @@ def _profile_call(g, dev):
     from napkon_string_matching_amd import grid
 
     if g.raw and g.kind == "indel":
-        lt, rt = probe_tables._raw_indel_tables(g, dev)
+        lt, rt = probe_tables.raw_indel_tables(g, dev)
         return lambda t, prune: grid.indel_raw_profile(lt, rt, t, prune=prune)
     if g.raw:
-        lt, rt = probe_tables._raw_jaccard_tables(g, dev)
+        lt, rt = probe_tables.raw_jaccard_tables(g, dev)
         return lambda t, prune: grid.jaccard_raw_profile(lt, rt, t, prune=prune)
     if g.kind == "indel":
-        tabs = probe_tables._levels_indel_tables(g, dev, False)
+        tabs = probe_tables.levels_indel_tables(g, dev, False)
         return lambda t, prune, banned=None: grid.indel_levels_profile(*tabs, t, category_mode=g.mode, prune=prune, banned=banned)
-    lt, rt = probe_tables._levels_jaccard_tables(g, dev, False)
+    lt, rt = probe_tables.levels_jaccard_tables(g, dev, False)
     return lambda t, prune, banned=None: grid.jaccard_levels_profile(lt, rt, t, category_mode=g.mode, prune=prune, banned=banned)
 
 
@@ -271,8 +271,8 @@ def test_c_entries_refuse_bad_arguments(dev):
     BADARG = 10001
     lt, rt = tables.encode_strings(["abc", "abd"], ["abc", "xyz", ""], dev)
     g = tp.grid("levels_jaccard")
-    jl, jr = probe_tables._levels_jaccard_tables(g, dev, False)
-    il = probe_tables._levels_indel_tables(tp.grid("levels_indel_one_word"), dev, False)
+    jl, jr = probe_tables.levels_jaccard_tables(g, dev, False)
+    il = probe_tables.levels_indel_tables(tp.grid("levels_indel_one_word"), dev, False)
     pairs = torch.full((64,), 7, dtype=torch.int64, device=dev)
     lb = torch.full((128,), 5.0, dtype=torch.float64, device=dev)
     rb = torch.full((256,), 5.0, dtype=torch.float64, device=dev)
@@ -329,8 +329,8 @@ def test_c_entries_with_an_empty_table(dev):
     stream = torch.cuda.current_stream(dev).cuda_stream
     t = (ctypes.c_double * 3)(0.0, 0.5, 1.0)
     st, jt = tables.encode_strings(["abc", "abd"], ["abc", "xyz", ""], dev)
-    jl, jr = probe_tables._levels_jaccard_tables(tp.grid("levels_jaccard"), dev, False)
-    il, ils, ir, irs = probe_tables._levels_indel_tables(tp.grid("levels_indel_one_word"), dev, False)
+    jl, jr = probe_tables.levels_jaccard_tables(tp.grid("levels_jaccard"), dev, False)
+    il, ils, ir, irs = probe_tables.levels_indel_tables(tp.grid("levels_indel_one_word"), dev, False)
 
     def entries(empty_left):
         """(name, call(pairs, left_best, right_best, stats), rows left, rows right) with one side's row count set to 0."""

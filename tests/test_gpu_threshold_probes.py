@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from support import threshold_probes as tp
+from support import probe_tables
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +32,6 @@ def dev():
     import torch
 
     return torch.device("cuda:0")
-
-
-def _first_difference(got, want):
-    extra, missing = sorted(set(got) - set(want))[:4], sorted(set(want) - set(got))[:4]
-    return f"got {len(got)} hits, oracle {len(want)}; only in got {extra}; lost (only in oracle) {missing}"
 
 
 _AT = {}
@@ -59,7 +55,7 @@ def _check(g, route, run):
     for thr in tp.thresholds_around(scores):
         want = tp.expectation(all_hits, thr)
         got = seen[thr] = run(thr)
-        assert got == want, f"{g.name} / {route} at threshold {thr!r}: {_first_difference(got, want)}"
+        assert got == want, f"{g.name} / {route} at threshold {thr!r}: {probe_tables.first_difference(got, want)}"
     at = _pairs_at(g)
     for s in scores:  # (implied by the equalities above; spelled out, since it is what these thresholds are for)
         here, below, above = ({(i, j) for _, i, j in seen[t]} for t in (s, math.nextafter(s, 0.0), math.nextafter(s, 2.0)))
@@ -81,74 +77,7 @@ def _check_top_k(g, route, run, groups=None):
         for thr in sorted(set(thresholds) | set(tp.thresholds_around([] if tie is None else [tie]))):
             want = ranks.cut(thr, k)
             got = run(k, thr)
-            assert got == want, f"{g.name} / {route} k={k} at threshold {thr!r}: {_first_difference(got, want)}"
-
-
-# ------------------------------------------------------------------------------------------------------------ tables
-_TABLES = {}
-
-
-def _cached(key, make):
-    if key not in _TABLES:
-        _TABLES[key] = make()
-    return _TABLES[key]
-
-
-def _raw_indel_tables(g, dev):
-    from napkon_string_matching_amd import tables
-
-    def make():
-        lt, rt = tables.encode_strings([tp.text(r) for r in g.left], [tp.text(r) for r in g.right], dev)
-        assert lt.stride == rt.stride == g.size and (g.size != 64 or (lt.hist16 is not None and rt.hist16 is not None))
-        return lt, rt
-
-    return _cached(g.name, make)
-
-
-def _raw_jaccard_tables(g, dev):
-    from napkon_string_matching_amd import tables
-
-    def make():
-        def padded(rows):
-            ids = np.full((len(rows), g.size), -1, dtype=np.int32)
-            for r, row in enumerate(rows):
-                ids[r, : len(row)] = row
-            return ids
-
-        lt = tables.SetTable.from_padded(padded(g.left), "left", dev, width=g.size)
-        rt = tables.SetTable.from_padded(padded(g.right), "right", dev, width=g.size)
-        assert rt.post is not None and lt.post is None and lt.width == rt.width == g.size
-        return lt, rt
-
-    return _cached(g.name, make)
-
-
-def _levels_indel_tables(g, dev, partition):
-    from napkon_string_matching_amd import tables
-
-    def make():
-        items = lambda side: [[tp.text(lv) for lv in it] for it in side]
-        li, ls, ri, rs = tables.encode_level_strings(items(g.left), items(g.right), dev, g.cat_l, g.cat_r, g.mode,
-                                                     partition=partition)
-        assert ls.stride == rs.stride == g.size and (li.seg is not None) == partition
-        return li, ls, ri, rs
-
-    return _cached((g.name, partition), make)
-
-
-def _levels_jaccard_tables(g, dev, partition):
-    from napkon_string_matching_amd import tables
-
-    def make():
-        vocabulary = tables.Vocabulary()
-        lt = tables.SetTable.from_levels(g.left, "left", dev, vocabulary, width=g.size, categories=g.cat_l, category_mode=g.mode,
-                                         partition=partition)
-        rt = tables.SetTable.from_levels(g.right, "right", dev, vocabulary, width=g.size, categories=g.cat_r,
-                                         category_mode=g.mode, partition=partition)
-        assert rt.post is not None and (lt.seg is not None) == partition
-        return lt, rt
-
-    return _cached((g.name, partition), make)
+            assert got == want, f"{g.name} / {route} k={k} at threshold {thr!r}: {probe_tables.first_difference(got, want)}"
 
 
 # --------------------------------------------------------------------------------------------------------- RAW Indel
@@ -164,7 +93,7 @@ def test_indel_raw_grid(dev, name, route):
     from napkon_string_matching_amd import grid
 
     g = tp.grid(name)
-    lt, rt = _raw_indel_tables(g, dev)
+    lt, rt = probe_tables.raw_indel_tables(g, dev)
     kw = RAW_INDEL_ROUTES[64 if g.size == 64 else 128][route]
     _check(g, route, lambda thr: grid.indel_raw_grid(lt, rt, thr, capacity=g.pairs + 1, **kw).as_tuples())
 
@@ -182,7 +111,7 @@ def test_jaccard_raw_grid(dev, name, route):
     from napkon_string_matching_amd import grid
 
     g = tp.grid(name)
-    lt, rt = _raw_jaccard_tables(g, dev)
+    lt, rt = probe_tables.raw_jaccard_tables(g, dev)
     kw = RAW_JACCARD_ROUTES[route]
     _check(g, route, lambda thr: grid.jaccard_raw_grid(lt, rt, thr, capacity=g.pairs + 1, **kw).as_tuples())
 
@@ -200,7 +129,7 @@ def test_jaccard_levels_grid(dev, name, route):
     from napkon_string_matching_amd import grid
 
     g = tp.grid(name)
-    lt, rt = _levels_jaccard_tables(g, dev, g.partition)
+    lt, rt = probe_tables.levels_jaccard_tables(g, dev, g.partition)
     kw = LEVELS_JACCARD_ROUTES[route]
     _check(g, route, lambda thr: grid.jaccard_levels_grid(lt, rt, thr, category_mode=g.mode, capacity=g.pairs + 1, **kw).as_tuples())
 
@@ -263,7 +192,7 @@ def test_indel_levels_grid_one_word(dev, name, route):
     from napkon_string_matching_amd import _lib
 
     g = tp.grid(name)
-    tabs = _levels_indel_tables(g, dev, g.partition)
+    tabs = probe_tables.levels_indel_tables(g, dev, g.partition)
     try:
         _check(g, route, lambda thr: ONE_WORD_ROUTES[route](tabs, g, thr))
     finally:
@@ -278,7 +207,7 @@ def test_indel_levels_grid_multi_word(dev, name, route):
     """The same bound in the shared-tile, park and wave-wide kernels at strides 128, 256 and 512; a tight family whose step-1
     strings fill the row (n1 = 2 * stride, 1024 at stride 512: the largest float rounding of ``needf``)."""
     g = tp.grid(name)
-    tabs = _levels_indel_tables(g, dev, g.partition)
+    tabs = probe_tables.levels_indel_tables(g, dev, g.partition)
     _check(g, route, lambda thr: MULTI_WORD_ROUTES[route](tabs, g, thr))
 
 
@@ -294,7 +223,7 @@ def test_indel_raw_top_k(dev, name, route, grouped):
     from napkon_string_matching_amd import grid
 
     g = tp.grid(name)
-    lt, rt = _raw_indel_tables(g, dev)
+    lt, rt = probe_tables.raw_indel_tables(g, dev)
     groups = tp.groups_of(g) if grouped else None
     _check_top_k(g, f"top_k-{route}-{'grouped' if grouped else 'plain'}",
                  lambda k, thr: grid.indel_raw_top_k(lt, rt, k, thr, prune=PRUNE[route], groups=groups).as_tuples(), groups)
@@ -308,7 +237,7 @@ def test_jaccard_raw_top_k(dev, name, route, grouped):
     from napkon_string_matching_amd import grid
 
     g = tp.grid(name)
-    lt, rt = _raw_jaccard_tables(g, dev)
+    lt, rt = probe_tables.raw_jaccard_tables(g, dev)
     groups = tp.groups_of(g) if grouped else None
     _check_top_k(g, f"top_k-{route}-{'grouped' if grouped else 'plain'}",
                  lambda k, thr: grid.jaccard_raw_top_k(lt, rt, k, thr, prune=PRUNE[route], groups=groups).as_tuples(), groups)
@@ -321,7 +250,7 @@ def test_indel_levels_top_k(dev, name, route):
     from napkon_string_matching_amd import grid
 
     g = tp.grid(name)
-    tabs = _levels_indel_tables(g, dev, False)
+    tabs = probe_tables.levels_indel_tables(g, dev, False)
     _check_top_k(g, f"top_k-{route}",
                  lambda k, thr: grid.indel_levels_top_k(*tabs, k, thr, category_mode=g.mode, prune=PRUNE[route]).as_tuples())
 
@@ -332,6 +261,6 @@ def test_jaccard_levels_top_k(dev, name, route):
     from napkon_string_matching_amd import grid
 
     g = tp.grid(name)
-    lt, rt = _levels_jaccard_tables(g, dev, False)
+    lt, rt = probe_tables.levels_jaccard_tables(g, dev, False)
     _check_top_k(g, f"top_k-{route}",
                  lambda k, thr: grid.jaccard_levels_top_k(lt, rt, k, thr, category_mode=g.mode, prune=PRUNE[route]).as_tuples())
