@@ -4,27 +4,37 @@
 // 32-bucket symbol histograms.  This kernel asks a cheaper question first, and asks it on the MATRIX pipe, which the
 // one-stage kernel leaves idle.  With a_b, r_b the counts of bucket b (symbol & 31) in the left and the right string,
 // LCS <= sum_b min(a_b, r_b), and a minimum is a dot product of thermometer codes: min(a, r) = sum_k [a >= k][r >= k].
-// Every bucket gets CAP code slots (K = 32 CAP):
+// The scan uses the bound D = sum_b D_b with D_b = min(a_b, r_b) where r_b < CAP and D_b = a_b where r_b >= CAP
+// (a_b >= min(a_b, r_b)), so D >= sum_b min(a_b, r_b) >= LCS and "D >= need" is a NECESSARY condition of a hit,
+// need = lcsmin[la + lb].  Every bucket gets CAP code slots (K = 32 CAP), of MIXED weight, so that all the arithmetic of the
+// code sits on the right side, which a wave builds once, and the left side, which every wave builds again for every
+// block, costs two instructions a word and slot:
 //
-//   left row,  slot s < CAP - 1:  [a_b >= s + 1]          right row, slot s < CAP - 1:  [r_b >= s + 1]
-//   left row,  last slot:         max(a_b - (CAP - 1), 0)  right row, last slot:         [r_b >= CAP]
+//   left row,  slot s < CAP - 1:  64 [a_b >= s + 1]   right row, slot s < CAP - 1:  [r_b >= s + 1] - [r_b >= CAP]   (0 or 1)
+//   left row,  last slot:         a_b                 right row, last slot:         64 [r_b >= CAP]
 //
-// (a stride-64 row keeps the last left slot <= 64: it fits i8).  Per bucket the dot product D collects min(a_b, r_b) where
-// r_b < CAP (the indicator slots give min(a_b, r_b, CAP - 1) = min(a_b, r_b), the last slot nothing) and a_b where
-// r_b >= CAP (min(a_b, CAP - 1) + max(a_b - (CAP - 1), 0)), so D >= sum_b min(a_b, r_b) >= LCS: "D >= need" is a NECESSARY
-// condition of a hit, need = lcsmin[la + lb].  The exact length filter min(la, lb) >= need stays in front of it as
-// need = kNever (D <= 64).  Integer arithmetic: nothing here rounds.
+// Where r_b < CAP the indicator slots give 64 sum_{k < CAP} [a_b >= k][r_b >= k] = 64 min(a_b, r_b, CAP - 1) = 64 min(a_b, r_b)
+// and the last slot nothing; where r_b >= CAP the right indicator slots are all zero and the last slot gives 64 a_b.  So
+// the dot product is D' = 64 D EXACTLY, and the test is D' >= 64 need, kept as D' > 64 need - 1.  Every operand byte is
+// 0 .. 64 (a stride-64 row has a_b <= 64): the i8 operands are never negative, D' <= 4096, and a pair that cannot fit has
+// need = kNever, 64 x 255 > 4096.  need = 0 passes everything.  The exact length filter min(la, lb) >= need stays in
+// front as need = kNever.  Integer arithmetic: nothing here rounds.  (64 [c >= k] of four counts in a word is
+// (w + (0x40 - k) 0x01010101) & 0x40404040: c + 0x40 - k is 56 .. 127, with bit 6 exactly where c >= k, and the last left
+// slot is the loaded word itself.  A code that scales by 128 with slack, left 0x80 = -128 against right 0xff = -1 and a last
+// right slot of 127, D' = 128 D - S, is as cheap on the left but dearer on the right, which shows in short chunks: DESIGN 4.3.)
 //
 //   scan    a wave owns NT right tiles of 32 strings; their CAP B fragments (v_mfma_i32_32x32x32_i8: lane = column
 //           l & 31, 16 of the 32 k of a step in lane half l >> 5 -- here buckets 16 (l >> 5) .. + 15 of code slot s, the SAME
 //           choice on both operands, so the order of k inside the instruction does not matter) are built once from the
-//           right fine histograms.  Left rows come in blocks of 32 of one length class: lane l loads 16 bytes of row l & 31,
-//           makes its CAP A fragments with byte-parallel arithmetic ([c >= k] = ((c + 0x80 - k) & 0x80) >> 7 per byte,
-//           counts <= 64) and per tile CAP MFMAs are chained on an accumulator.  The 16 results of a lane (rows
-//           (i & 3) + 8 (i >> 2) + 4 (l >> 5) of the block, column l & 31 of the tile) are folded with v_max3_i32 and compared
-//           with the lane's need once; only where some lane passes is the 16-bit mask made, a full-rate v_sub_u32 and a
-//           v_alignbit_b32 per result (the sign of need - 1 - D, shifted in from below).  The last block of a class in a chunk
-//           repeats its last row, and the bits of the rows that do not exist are masked off;
+//           right fine histograms.  Left rows come in blocks of 32 of one length class: lane l loads 16 bytes of row l & 31
+//           (a 32-bit offset from the chunk's first row), makes its CAP - 1 indicator fragments, and per tile CAP MFMAs are
+//           chained on an accumulator, the last with the loaded words as they are.  The words of consecutive blocks go to
+//           two register sets in turn (the block loop is unrolled by two), so no word is copied.  The 16 results of a lane
+//           (rows (i & 3) + 8 (i >> 2) + 4 (l >> 5) of the block, column l & 31 of the tile) are folded with v_max3_i32 and
+//           compared with the lane's 64 need - 1 once; only where some lane passes is the 16-bit mask made, a full-rate
+//           v_sub_u32 and a v_alignbit_b32 per result (the sign of 64 need - 1 - D', shifted in from below).  The last block
+//           of a class in a chunk repeats its last row where it is short of 32; only there, a wave-uniform condition, is
+//           the mask of the rows that exist made and applied, inside the mask path: full blocks need none;
 //   order   TWO accumulators, tile t in acc[t & 1] (NSM_C3C_PIPE, NT even): the chain of tile t + 1 -- after a block's last
 //           tile that of tile 0 of the class's next block, whose A fragments are made just before -- is issued before the
 //           branch and the push of tile t, its MFMAs with the v_max3_i32 of tile t's fold between them (a chained MFMA waits
@@ -43,7 +53,7 @@
 //           row and its length, so the stack outlives the length classes and is emptied once, at the end.
 //
 // Every test that drops a pair is an upper bound of the LCS: the hits are the one-stage kernel's, the exhaustive kernel's and
-// the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt and DESIGN 4.3.
+// the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt, profiles/c3_codes_ab.txt and DESIGN 4.3.
 #pragma once
 
 namespace nsm {
@@ -82,9 +92,9 @@ static inline size_t c3c_lds_bytes() {
 typedef int c3c_v4i __attribute__((ext_vector_type(4)));
 typedef int c3c_v16i __attribute__((ext_vector_type(16)));
 
-// [c >= k] of the four bytes of w (0 <= c <= 64, 1 <= k <= 64: c + 0x80 - k stays inside its byte)
-__device__ __forceinline__ uint32_t c3c_ge(uint32_t w, int k) {
-  return ((w + static_cast<uint32_t>(0x80 - k) * 0x01010101u) & 0x80808080u) >> 7;
+// 64 [c >= k] in each of the four bytes of w (0 <= c <= 64, 1 <= k <= 8: c + 0x40 - k is 56 .. 127, bit 6 where c >= k)
+__device__ __forceinline__ uint32_t c3c_ge64(uint32_t w, int k) {
+  return (w + static_cast<uint32_t>(0x40 - k) * 0x01010101u) & 0x40404040u;
 }
 
 #ifndef NSM_C3C_OCC
@@ -147,12 +157,14 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const int jcl = valid[t] ? j : p.n_right - 1;
     uint4 f = reinterpret_cast<const uint4*>(rhist + static_cast<size_t>(jcl) * 8)[half];
     if (!valid[t]) f = make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t fw[4] = {f.x, f.y, f.z, f.w};
 #pragma unroll
-    for (int s = 0; s < CAP; ++s) {
-      bfrag[t][s].x = static_cast<int>(c3c_ge(f.x, s + 1));
-      bfrag[t][s].y = static_cast<int>(c3c_ge(f.y, s + 1));
-      bfrag[t][s].z = static_cast<int>(c3c_ge(f.z, s + 1));
-      bfrag[t][s].w = static_cast<int>(c3c_ge(f.w, s + 1));
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t full = c3c_ge64(fw[q], CAP);  // the last slot: 64 [r >= CAP]
+#pragma unroll
+      for (int s = 0; s < CAP - 1; ++s)  // [r >= s + 1] - [r >= CAP] (the second implies the first: the xor is the difference)
+        bfrag[t][s][q] = static_cast<int>((c3c_ge64(fw[q], s + 1) ^ full) >> 6);
+      bfrag[t][CAP - 1][q] = static_cast<int>(full);
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -243,13 +255,16 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   // rows are sorted by length (descending): rows of length 64 - c are [lstart[c], lstart[c + 1])
   const int c_first = 64 - llen[i0];
   const int c_last = 64 - llen[i1 - 1];
+  // a left row's bytes as a 32-bit offset from the chunk's first row (a chunk has at most 2^15 rows of 32 bytes)
+  const char* chunk = reinterpret_cast<const char*>(lhist + static_cast<size_t>(i0) * 8);
+  const uint32_t lane_off = static_cast<uint32_t>(col * 32 + half * 16);
   for (int c = c_first; c <= c_last; ++c) {
     const int a = max(i0, lstart[c]);
     const int b = min(i1, lstart[c + 1]);
     if (a >= b) continue;
     const int la = 64 - c;
     // per tile: the lane's right string can only hit a row of this class if D >= need (kNever: it cannot fit)
-    int nm1[NT];  // need - 1: "D > nm1" is the fold's test, and the sign of nm1 - D is a pair's pass bit
+    int nm1[NT];  // 64 need - 1: "D' > nm1" is the fold's test, and the sign of nm1 - D' is a pair's pass bit
     bool some = false;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -257,51 +272,56 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       const int nd = valid[t] ? need_of(la, lb) : static_cast<int>(kNever);
       const bool fits = min(la, lb) >= nd;  // exact length filter: LCS <= min(la, lb)
       some = some || fits;
-      nm1[t] = (fits ? nd : static_cast<int>(kNever)) - 1;
+      nm1[t] = 64 * (fits ? nd : static_cast<int>(kNever)) - 1;
     }
     if (!__any(some)) continue;
 
     // the lane's 16 bytes of row i + col (the class's last row again past its end)
+    const uint32_t last_off = static_cast<uint32_t>(b - 1 - i0) * 32u + static_cast<uint32_t>(half * 16);
     auto load_rows = [&](int i) -> uint4 {
-      return reinterpret_cast<const uint4*>(lhist + static_cast<size_t>(min(i + col, b - 1)) * 8)[half];
+      const uint32_t off = min(static_cast<uint32_t>(i - i0) * 32u + lane_off, last_off);
+      return *reinterpret_cast<const uint4*>(chunk + off);
     };
-    // the A fragments of a block: CAP - 1 indicator slots and the excess
-    c3c_v4i afrag[CAP];
+    // the A fragments of a block: CAP - 1 indicator slots, two instructions a word; the last slot is the loaded word itself
+    c3c_v4i afrag[CAP - 1];
     auto make_afrag = [&](const uint4& w) {
-      uint32_t ex[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
       for (int s = 0; s < CAP - 1; ++s) {
-        const uint32_t g0 = c3c_ge(w.x, s + 1), g1 = c3c_ge(w.y, s + 1), g2 = c3c_ge(w.z, s + 1), g3 = c3c_ge(w.w, s + 1);
-        afrag[s].x = static_cast<int>(g0); afrag[s].y = static_cast<int>(g1);
-        afrag[s].z = static_cast<int>(g2); afrag[s].w = static_cast<int>(g3);
-        ex[0] -= g0; ex[1] -= g1; ex[2] -= g2; ex[3] -= g3;  // (bytewise: an indicator never exceeds its count)
+        afrag[s].x = static_cast<int>(c3c_ge64(w.x, s + 1)); afrag[s].y = static_cast<int>(c3c_ge64(w.y, s + 1));
+        afrag[s].z = static_cast<int>(c3c_ge64(w.z, s + 1)); afrag[s].w = static_cast<int>(c3c_ge64(w.w, s + 1));
       }
-      afrag[CAP - 1].x = static_cast<int>(ex[0]); afrag[CAP - 1].y = static_cast<int>(ex[1]);
-      afrag[CAP - 1].z = static_cast<int>(ex[2]); afrag[CAP - 1].w = static_cast<int>(ex[3]);
     };
-    // the CAP chained MFMAs of the current block against tile t
-    auto chain = [&](int t) -> c3c_v16i {
+    // the CAP chained MFMAs of the current block (its loaded words: w) against tile t
+    auto chain = [&](int t, const uint4& w) -> c3c_v16i {
       c3c_v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int s = 0; s < CAP; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[s], bfrag[t][s], acc, 0, 0, 0);
-      return acc;
+      for (int s = 0; s < CAP - 1; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[s], bfrag[t][s], acc, 0, 0, 0);
+      const c3c_v4i last = {static_cast<int>(w.x), static_cast<int>(w.y), static_cast<int>(w.z), static_cast<int>(w.w)};
+      return __builtin_amdgcn_mfma_i32_32x32x32_i8(last, bfrag[t][CAP - 1], acc, 0, 0, 0);
     };
-    // fold, compare and push of tile t of the block at row i (exist: the lane's 16 rows of that block that exist)
     auto fold = [&](const c3c_v16i& acc) -> int {
       int top = max(max(acc[0], acc[1]), acc[2]);
 #pragma unroll
       for (int k = 3; k < 15; k += 2) top = max(max(top, acc[k]), acc[k + 1]);
       return max(top, acc[15]);
     };
-    auto finish = [&](int top, const c3c_v16i& acc, int t, int i, uint32_t exist) {
+    // the lane's 16 rows that exist of a block of n_rows < 32 rows
+    auto exist_of = [&](int n_rows) -> uint32_t {
+      const uint32_t rows = (1u << n_rows) - 1u;  // (wave-uniform) bit r: the block's row r exists
+      const uint32_t x = rows >> (4 * half);  // bit k of the result = bit (k & 3) + 8 (k >> 2) of x
+      return (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);
+    };
+    // compare and push of tile t of the block at row i
+    auto finish = [&](int top, const c3c_v16i& acc, int t, int i) {
 #if !NSM_C3C_BRANCHFREE
       if (!__any(top > nm1[t])) return;
 #endif
-      // bit k = [acc[k] >= need]: the sign of need - 1 - acc[k], shifted in from below (k = 15 first)
+      // bit k = [acc[k] >= need]: the sign of nm1 - acc[k], shifted in from below (k = 15 first)
       uint32_t mask = 0;
 #pragma unroll
       for (int k = 15; k >= 0; --k) mask = __builtin_amdgcn_alignbit(mask, static_cast<uint32_t>(nm1[t] - acc[k]), 31);
-      mask &= exist;
+      // a block is short of rows only as a class's last (wave-uniform); the rows past the end repeat the last one
+      if (b - i < kC3cBlock) mask &= exist_of(b - i);
       // lanes with a pair that passed push: one ballot and one ds_write per tile
       const bool nz = mask != 0u;
       const unsigned long long m = __ballot(nz);
@@ -317,14 +337,6 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         q_cnt += __popcll(m);
       }
     };
-    // the lane's 16 rows of the block at row i that exist (all of them but in a class's last block)
-    auto exist_of = [&](int i) -> uint32_t {
-      const int n_rows = b - i;
-      const uint32_t rows = n_rows < kC3cBlock ? (1u << n_rows) - 1u : 0xffffffffu;  // (wave-uniform) bit r: row i + r exists
-      const uint32_t x = rows >> (4 * half);  // bit k of the result = bit (k & 3) + 8 (k >> 2) of x
-      return (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);
-    };
-    uint4 w_next = load_rows(a);
 #if NSM_C3C_PIPE
     // software pipeline over the tiles and the blocks of the class: acc[t & 1] holds tile t, and the chain of the tile after
     // (tile 0 of the next block after a block's last, with that block's A fragments) is issued around the fold and before
@@ -332,13 +344,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     // again at the end of the class.
     static_assert(NT % 2 == 0, "tile 0 of the next block takes the accumulator of tile NT: NT must be even (or NSM_C3C_PIPE=0)");
     c3c_v16i acc[2];
-    if (q_cnt > kC3cDrainAt)  // (a class of one block has no other check in front of its first NT - 1 tiles)
-      while (q_cnt >= kWave) drain_pass();
-    make_afrag(w_next);
-    if (a + kC3cBlock < b) w_next = load_rows(a + kC3cBlock);
-    acc[0] = chain(0);
-    for (int i = a; i < b; i += kC3cBlock) {
-      const uint32_t exist = exist_of(i);
+    // one block at row i.  wc: the block's loaded words, its last A slot, which the chains read until the block's last tile
+    // is issued; wn: those of the block after, loaded a block ahead.  The load of the block after that goes to wc, so the
+    // two register sets change places from block to block and no word is copied.
+    auto block = [&](int i, uint4& wc, uint4& wn) __attribute__((always_inline)) {
       const bool more = i + kC3cBlock < b;
       // the drain check sits in front of a block's LAST tile: at most NT tiles, NT x 64 entries, between two checks.  Where
       // the drain has to run, the pipeline is emptied first (one more tile's entries: kC3cStack's extra 64 slots), so that
@@ -347,13 +356,13 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         if (t + 1 < NT) {
-          acc[(t + 1) & 1] = chain(t + 1);
+          acc[(t + 1) & 1] = chain(t + 1, wc);
         } else {
           flush = q_cnt > kC3cDrainAt;
           if (more && !flush) {
-            make_afrag(w_next);
-            if (i + 2 * kC3cBlock < b) w_next = load_rows(i + 2 * kC3cBlock);
-            acc[0] = chain(0);
+            make_afrag(wn);
+            if (i + 2 * kC3cBlock < b) wc = load_rows(i + 2 * kC3cBlock);
+            acc[0] = chain(0, wn);
           }
         }
         // the fold of tile t goes BETWEEN the MFMAs of the chain (MFMA, 4 VALU, MFMA, 4 VALU, MFMA): a wave issues in order and
@@ -365,18 +374,32 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        finish(top, acc[t & 1], t, i, exist);
+        finish(top, acc[t & 1], t, i);
       }
       if (flush) {
         while (q_cnt >= kWave) drain_pass();  // full passes only: the rest waits for more
         if (more) {
-          make_afrag(w_next);
-          if (i + 2 * kC3cBlock < b) w_next = load_rows(i + 2 * kC3cBlock);
-          acc[0] = chain(0);
+          make_afrag(wn);
+          if (i + 2 * kC3cBlock < b) wc = load_rows(i + 2 * kC3cBlock);
+          acc[0] = chain(0, wn);
         }
       }
+    };
+    if (q_cnt > kC3cDrainAt)  // (a class of one block has no other check in front of its first NT - 1 tiles)
+      while (q_cnt >= kWave) drain_pass();
+    uint4 w0 = load_rows(a);
+    make_afrag(w0);
+    uint4 w1 = w0;  // (once per class, outside the block loop: a class of one block never loads the second set)
+    if (a + kC3cBlock < b) w1 = load_rows(a + kC3cBlock);
+    acc[0] = chain(0, w0);
+    for (int i = a;;) {
+      block(i, w0, w1);
+      if ((i += kC3cBlock) >= b) break;
+      block(i, w1, w0);
+      if ((i += kC3cBlock) >= b) break;
     }
 #else
+    uint4 w_next = load_rows(a);
     for (int i = a; i < b; i += kC3cBlock) {
       const uint4 w = w_next;
       if (i + kC3cBlock < b) w_next = load_rows(i + kC3cBlock);
@@ -384,11 +407,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       if (q_cnt > kC3cDrainAt)
         while (q_cnt >= kWave) drain_pass();  // full passes only: the rest waits for more
       make_afrag(w);
-      const uint32_t exist = exist_of(i);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const c3c_v16i acc = chain(t);
-        finish(fold(acc), acc, t, i, exist);
+        const c3c_v16i acc = chain(t, w);
+        finish(fold(acc), acc, t, i);
       }
     }
 #endif

@@ -75,6 +75,9 @@ __global__ __launch_bounds__(256) void k(uint32_t* out, uint32_t s0, uint32_t s1
         if (KIND == 56) asm volatile("v_bitop3_b32 %0, %1, %3, %0 bitop3:0xe2" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
         if (KIND == 57) asm volatile("v_bitop3_b32 %0, %1, %2, %0 bitop3:0xe2" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
         if (KIND == 58) asm volatile("v_bfi_b32 %0, %2, %1, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 59) asm volatile("v_add_u32 %0, 0x3f3f3f3f, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 60) asm volatile("v_and_b32 %0, 0x40404040, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
+        if (KIND == 61) asm volatile("v_lshrrev_b32 %0, 7, %0" : "+v"(v[q]) : "v"(w[q]), "s"(s0), "v"(w[(q + 1) & 7]), "v"(pk[q&3]), "v"(pw[q&3]) : "vcc", "s20");
       }
     }
   }
@@ -165,5 +168,8 @@ int main() {
   run<56>("v_bitop3_b32", 1);
   run<57>("v_bitop3_b32 sgpr", 1);
   run<58>("v_bfi_b32 sgpr", 1);
+  run<59>("v_add_u32 literal", 1);
+  run<60>("v_and_b32 literal", 1);
+  run<61>("v_lshrrev_b32 imm 7", 1);
   return 0;
 }
