@@ -74,24 +74,40 @@ __device__ __forceinline__ void raw_build_masks(unsigned long long* pm, int pm_s
   __builtin_amdgcn_wave_barrier();
 }
 
-// LCS of ONE pair (left row `row` of `la`, right row `j` of `lb` code units; all wave-uniform) on the SCALAR unit: lane k
-// holds code unit k of both strings (two 64-byte loads), v_readlane hands the right string's units to the scalar unit one
-// by one, and per unit c the match mask is a ballot -- M = lanes whose left unit equals c -- so the recurrence
+// LCS of ONE pair (left string of `la`, right string of `lb` code units; all wave-uniform) on the SCALAR unit: lane k holds
+// code unit k of both strings (two 64-byte loads, raw_lcs_pair below), v_readlane hands the TEXT's units to the scalar unit
+// one by one, and per unit c the match mask is a ballot -- M = lanes whose PATTERN unit equals c -- so the recurrence
 // V' = (V + (V & M)) | (V & ~M) runs on one 64-bit scalar: a v_readlane, a v_cmp and five SALU ops per code unit, no mask
 // table, no LDS, 50 VGPRs for the whole kernel.  (The wave-wide form scores 64 texts against one pattern; with one surviving
 // pair per pattern -- 4.1e5 of them per configs[2] grid -- 63 of its 64 lanes computed nothing: 0.9 of 4.2 ms, and its 32
 // address registers set the kernel's occupancy.)
-__device__ __forceinline__ int raw_lcs_pair(const uint8_t* __restrict__ lcodes, int row, int la, const uint8_t* __restrict__ rcodes,
-                                            int j, int lb, int lane) {
-  // lanes past the pattern hold a value no code unit equals, so the right string's padding (code = alphabet, like the left
-  // string's own) matches nothing and whole words can be processed without a per-unit length test
-  const uint32_t code = lcodes[static_cast<size_t>(row) * 64 + lane];
-  const uint32_t pat = lane < la ? code : 0x100u;
-  const uint32_t text = rcodes[static_cast<size_t>(j) * 64 + lane];
+//   roles   the LCS is symmetric: the LONGER string is the pattern (lanes past its length hold 0x100, which no code unit
+//           equals), the SHORTER one the text (lanes past its length hold 0x200, which equals nothing either: whole words of
+//           four units are processed without a per-unit length test, whatever either table pads its rows with).  The choice
+//           is wave-uniform per pair; with equal lengths the left string is the pattern;
+//   stop    `need` is the pair's integer threshold (wave-uniform).  A text unit adds at most one to the LCS, so after a
+//           word of four units that is not the text's last, every NSM_LCS_STOP_EVERY words, the chain ends where
+//           LCS so far + text units left < need -- as popcount(V) + units done > lt - need + 64, a s_bcnt1, an add, a
+//           compare and a branch.  A call that stops returns the count so far, which is then BELOW need: the callers only
+//           compare the result with need and score hits.  need = 0 (threshold <= 0, empty strings) never stops: the test
+//           would ask for more misses than units done.  99.5 % of the pairs that get here on configs[2] are no hits.
+//           (Measured, DESIGN 4.3 step 9: a test every word beats one every second word; a word's four compares written to
+//           four SGPR pairs in front of its four steps, instead of each through vcc, change nothing.)
+#ifndef NSM_LCS_STOP_EVERY
+#define NSM_LCS_STOP_EVERY 1  // words between two stop tests (0: the chain always runs to the text's end)
+#endif
+__device__ __forceinline__ int raw_lcs_units(uint32_t lcode, int la, uint32_t rcode, int lb, int need, int lane) {
+  const bool swap = la < lb;  // (wave-uniform)
+  const int lp = swap ? lb : la, lt = swap ? la : lb;
+  const uint32_t pat = lane < lp ? (swap ? rcode : lcode) : 0x100u;
+  const uint32_t text = lane < lt ? (swap ? lcode : rcode) : 0x200u;
+  const int lim = lt - need + 64;
   unsigned long long v = ~0ull;
+  // (16 words at most and wave-uniform exits: the loop unrolls fully, the lane of every v_readlane is a constant, and an exit
+  // is one s_cmp and one s_cbranch to the end)
+  if (lt > 0) {
 #pragma unroll
-  for (int w = 0; w < 16; ++w) {
-    if (4 * w < lb) {  // (wave-uniform; no `break`: the loop must unroll)
+    for (int w = 0; w < 16; ++w) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         const uint32_t c = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(text), 4 * w + b));
@@ -99,9 +115,18 @@ __device__ __forceinline__ int raw_lcs_pair(const uint8_t* __restrict__ lcodes, 
         const unsigned long long u = v & m;
         v = (v + u) | (v & ~m);
       }
+      if (4 * (w + 1) >= lt) break;  // (no test behind the text's last word)
+      if (NSM_LCS_STOP_EVERY > 0 && (w + 1) % (NSM_LCS_STOP_EVERY > 0 ? NSM_LCS_STOP_EVERY : 1) == 0 && __popcll(v) + 4 * (w + 1) > lim)
+        break;
     }
   }
   return __popcll(~v);
+}
+
+// ... of left row `row` and right row `j`
+__device__ __forceinline__ int raw_lcs_pair(const uint8_t* __restrict__ lcodes, int row, int la, const uint8_t* __restrict__ rcodes,
+                                            int j, int lb, int need, int lane) {
+  return raw_lcs_units(lcodes[static_cast<size_t>(row) * 64 + lane], la, rcodes[static_cast<size_t>(j) * 64 + lane], lb, need, lane);
 }
 
 #ifndef NSM_C3_OCC
@@ -280,7 +305,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3_OCC void indel_raw_kernel(
             const int j_s = __builtin_amdgcn_readlane(jc[t], leader);
             const int lb_s = __builtin_amdgcn_readlane(lbj[t], leader);
             const int need_s = __builtin_amdgcn_readlane(need[t], leader);
-            const int lcs = raw_lcs_pair(lcodes, i, la, rcodes, j_s, lb_s, lane);
+            const int lcs = raw_lcs_pair(lcodes, i, la, rcodes, j_s, lb_s, need_s, lane);
             if (lcs >= need_s && lane == 0) emit_hit(hits, p.cap, count, indel_score(la, lb_s, lcs), lorig[i], rorig[j_s]);
           }
         }

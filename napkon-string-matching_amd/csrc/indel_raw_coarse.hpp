@@ -49,11 +49,16 @@
 //           lanes busy): lane = one entry, ONE of
 //           its pairs (an entry with more pairs goes back on the stack) -- the exact 32-bucket L1 of the pair (the left
 //           histogram gathered from global memory, the right one read from the wave's copy in LDS, 8 v_sad_u8), then, for
-//           those that remain, the bit-parallel LCS of the pair on the SCALAR unit (raw_lcs_pair).  Entries carry their
-//           row and its length, so the stack outlives the length classes and is emptied once, at the end.
+//           those that remain, the bit-parallel LCS of the pair on the SCALAR unit (raw_lcs_units in indel_raw.hip), one
+//           pair after the other: the longer string of the pair is the pattern, the shorter one the text, and the chain
+//           stops after a word of four text units where LCS so far + text units left < need (99.5 % of these pairs are
+//           no hits); the two 64-byte rows of the NEXT surviving pair are requested before the current pair's chain runs
+//           (NSM_C3C_LCS_PREFETCH).  Entries carry their row and its length, so the stack outlives the length classes and
+//           is emptied once, at the end.
 //
 // Every test that drops a pair is an upper bound of the LCS: the hits are the one-stage kernel's, the exhaustive kernel's and
-// the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt, profiles/c3_codes_ab.txt and DESIGN 4.3.
+// the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt, profiles/c3_codes_ab.txt, profiles/c3_lcs_ab.txt
+// and DESIGN 4.3.
 #pragma once
 
 namespace nsm {
@@ -66,6 +71,9 @@ namespace nsm {
 #endif
 #ifndef NSM_C3C_PIPE
 #define NSM_C3C_PIPE (NSM_C3C_NT % 2 == 0)  // 1: two accumulators, a tile's MFMAs are issued around the fold of the tile before
+#endif
+#ifndef NSM_C3C_LCS_PREFETCH
+#define NSM_C3C_LCS_PREFETCH 1  // 1: the drain requests the next surviving pair's rows before the current pair's LCS chain
 #endif
 #ifndef NSM_C3C_BRANCHFREE
 #define NSM_C3C_BRANCHFREE 0  // 1: every tile builds its 16-bit masks, no fold and no branch
@@ -236,17 +244,33 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     pass = pass && p.n_left < 0;
 #endif
     const int jp = j0 + tl;
-    for (unsigned long long todo = __ballot(pass); todo; todo &= todo - 1ull) {
+    // Each pair is two 64-byte loads and the scalar chain of raw_lcs_units, which stops early for most pairs (the pair's need
+    // goes with it).  NSM_C3C_LCS_PREFETCH: the rows of the NEXT surviving pair are requested before the current pair's
+    // chain runs, whether that chain stops early or not.
+    unsigned long long todo = __ballot(pass);
+    auto row_units = [&](unsigned long long left_todo, uint32_t& lc, uint32_t& rc) {
+      const int leader = __builtin_ctzll(left_todo);
+      lc = lcodes[static_cast<size_t>(__builtin_amdgcn_readlane(row, leader)) * 64 + lane];
+      rc = rcodes[static_cast<size_t>(__builtin_amdgcn_readlane(jp, leader)) * 64 + lane];
+    };
+    uint32_t lc_next = 0, rc_next = 0;
+    if (NSM_C3C_LCS_PREFETCH && todo) row_units(todo, lc_next, rc_next);
+    while (todo) {
       const int leader = __builtin_ctzll(todo);
       const int row_s = __builtin_amdgcn_readlane(row, leader);
       const int j_s = __builtin_amdgcn_readlane(jp, leader);
       const int la_s = __builtin_amdgcn_readlane(la, leader);
       const int lb_s = __builtin_amdgcn_readlane(lb, leader);
-      const int lcs = raw_lcs_pair(lcodes, row_s, la_s, rcodes, j_s, lb_s, lane);
+      const int need_s = need_of(la_s, lb_s);
+      uint32_t lc = lc_next, rc = rc_next;
+      if (!NSM_C3C_LCS_PREFETCH) row_units(todo, lc, rc);
+      todo &= todo - 1ull;
+      if (NSM_C3C_LCS_PREFETCH && todo) row_units(todo, lc_next, rc_next);
+      const int lcs = raw_lcs_units(lc, la_s, rc, lb_s, need_s, lane);
 #ifdef NSM_C3C_X_COUNTLCS  // (experiments: one record per LCS call)
       if (lane == 0)
 #else
-      if (lcs >= need_of(la_s, lb_s) && lane == 0)
+      if (lcs >= need_s && lane == 0)
 #endif
         emit_hit(hits, p.cap, count, indel_score(la_s, lb_s, lcs), lorig[row_s], rorig[j_s]);
     }
