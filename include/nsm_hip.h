@@ -57,6 +57,8 @@ extern "C" {
 #define NSM_E_BADARG 10001   /* inconsistent sizes / unsupported width */
 #define NSM_E_UNSUPPORTED 10002
 
+#define NSM_LEVELS_ID_LIMIT (1 << 26) /* ids of a LEVELS set table are below it (nsm_set_table.ids says why) */
+
 /* One above-threshold pair.  16 bytes, the unit of the RCCL all-gather of hits. */
 typedef struct nsm_hit {
   double score; /* exactly the double the reference computes */
@@ -67,7 +69,17 @@ typedef struct nsm_hit {
 /* Token-id set table of one side, rows sorted by `cnt` DESCENDING (the encoder does this).
  *   ids   device int32 [n][width]  unique ids >= 0, unused slots padded (left: -1, right: -2).  RAW tables: ascending
  *                                  within the row (the builder sorts them; the global inverted index relies on it).
- *                                  Levels tables: first-appearance order, see plen
+ *                                  Levels tables: first-appearance order, see plen; every id is below
+ *                                  NSM_LEVELS_ID_LIMIT (2^26).  The levels Jaccard kernels (grid, top-k, profile, floor
+ *                                  grid; nsm_jaccard_levels_pairs compares whole ids) keep a left id as id << 6 and a
+ *                                  right id as (id << 6) | position in 32 bits and read min(left ^ right) < 64 as "found
+ *                                  at that position", so they compare ids modulo 2^26: two ids congruent modulo 2^26
+ *                                  would count as one token.  nsm_build_set_table
+ *                                  refuses such a row; a caller that fills the columns of a levels table by hand owns
+ *                                  this check (renumber the tokens densely, as a vocabulary does).  The two largest
+ *                                  allowed ids shift to the bit patterns of the padding (-1 << 6, -2 << 6) and are
+ *                                  still safe: padding sits at positions >= cnt, which no level counts.  RAW tables
+ *                                  compare whole ids and take any id >= 0
  *   cnt   device int32 [n]         number of ids in the row (RAW) / in the item's largest level
  *   sig   device uint64[n]         signature word: bits 0..57 = OR over the row's ids of
  *                                  1 << ((((id * 0x9E3779B1u) >> 16) & 0xffff) * 58 >> 16); bits 58..63 =
@@ -510,8 +522,8 @@ int nsm_release_all(void); /* the same for every stream of every device */
  *   They SORT (stable: ties stay in the caller's order), so the grids never see an unsorted table.
  *   They synchronise `stream` before returning (row count and validation verdict live on the device) and
  *   allocate their scratch stream-ordered (hipMallocAsync / hipFreeAsync): nothing is kept after the call.
- *   Data errors (row wider than the table, duplicate id in a LEVELS row, code unit >= alphabet,
- *   category bit 63 in use where "both empty" must become a category) return NSM_E_BADARG.
+ *   Data errors (row wider than the table, duplicate id in a LEVELS row, an id >= NSM_LEVELS_ID_LIMIT in a LEVELS row,
+ *   code unit >= alphabet, category bit 63 in use where "both empty" must become a category) return NSM_E_BADARG.
  */
 #define NSM_BUILD_PARTITION 1u /* levels tables: one row per (item, category), rows grouped by category */
 #define NSM_BUILD_VALIDATE 2u  /* (ABI v2 callers; no effect since v3: RAW rows always drop repeated ids -- they are sets --

@@ -32,6 +32,7 @@ enum BuildError : int {
   kErrBit63 = 4,         // category bit 63 in use: the empty items cannot become a category of their own
   kErrBadLevels = 5,     // nlev outside [1, max_levels] / plen not non-decreasing or above cnt
   kErrBadVocab = 6,      // an id >= the table's vocab (global inverted index)
+  kErrLevelsId = 7,      // an id >= NSM_LEVELS_ID_LIMIT in a levels row (the levels Jaccard kernels compare 26 bits)
 };
 
 struct Status {
@@ -198,6 +199,8 @@ __global__ void set_rows_kernel(const int32_t* __restrict__ ids_in, int n, int w
   for (int k = 0; k < width_in; ++k) {
     const int32_t v = src[k];
     if (v < 0) continue;
+    // the levels Jaccard kernels compare ids shifted left by 6 in 32 bits (include/nsm_hip.h: ids); RAW rows take any id
+    if (nlev_in && v >= NSM_LEVELS_ID_LIMIT) atomicMax(&st->err, static_cast<int>(kErrLevelsId));
     bool seen = false;
     for (int b = 0; b < min(cnt, width); ++b) seen = seen || dst[b] == v;
     if (seen) {
@@ -477,6 +480,8 @@ const char* error_text(int err) {
                            "(encode both sides without a partition)";
     case kErrBadLevels: return "nlev outside its range, or plen not a non-decreasing prefix-length row";
     case kErrBadVocab: return "an id is >= the table's vocab (the global inverted index addresses its offsets by id)";
+    case kErrLevelsId: return "a levels row holds an id >= 2^26 (NSM_LEVELS_ID_LIMIT): the levels Jaccard kernels compare ids "
+                              "modulo 2^26, renumber the tokens densely";
     default: return "unknown";
   }
 }

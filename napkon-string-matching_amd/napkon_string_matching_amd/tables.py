@@ -30,6 +30,8 @@ WIDTHS = (16, 32, 64)
 STRIDES = (64, 128, 256, 512)  # code units per string row: 1, 2, 4 or 8 words of the bit-parallel LCS
 MAX_LEVELS = 64
 MAX_INDEX_VOCAB = 1 << 23  # most index keys (ids; x 64 with a category partition) for which a right table gets its global inverted index by default (20 bytes of offsets per key)
+MAX_GLOBAL_INDEX_KEYS = 1 << 25  # most keys nsm_build_set_table builds a global inverted index for: every id is below it
+LEVELS_ID_LIMIT = 1 << 26  # NSM_LEVELS_ID_LIMIT: the levels Jaccard kernels compare ids modulo 2^26 (include/nsm_hip.h: ids)
 LEFT_PAD, RIGHT_PAD = -1, -2
 EMPTY_CATEGORY_BIT = 63  # stands for "no category at all" when empty-vs-empty counts as a match
 _GOLDEN = np.uint32(0x9E3779B1)
@@ -445,6 +447,15 @@ class SetTable:
                 category_mode=_lib.CAT_NONE, partition=False, index_vocab=0):
         if side not in ("left", "right"):
             raise ValueError("side must be 'left' or 'right'")
+        # (both checks before the branch to the device: the two paths refuse the same tables with the same words)
+        if nlev is not None and int(np.asarray(ids).max(initial=-1)) >= LEVELS_ID_LIMIT:
+            raise ValueError("a levels row holds an id >= 2^26 (NSM_LEVELS_ID_LIMIT): the levels Jaccard kernels compare ids "
+                             "modulo 2^26, renumber the tokens densely")
+        keys = index_vocab * (64 if (nlev is not None and cat is not None and category_mode != _lib.CAT_NONE and partition) else 1)
+        if keys > MAX_GLOBAL_INDEX_KEYS:
+            raise ValueError(f"the global inverted index addresses its offsets by id: every id must be below 2^25 (with a "
+                             f"category partition, below 2^19), this table needs {keys} keys; encode it with index=None or "
+                             "index=False")
         if nlev is not None:  # entries of plen past an item's last level repeat it (the clamped level index)
             plen = np.asarray(plen, dtype=np.uint8)
             clamp = np.minimum(np.arange(plen.shape[1])[None, :], np.maximum(np.asarray(nlev), 1)[:, None] - 1)
