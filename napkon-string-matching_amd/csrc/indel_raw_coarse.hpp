@@ -23,18 +23,24 @@
 // slot is the loaded word itself.  A code that scales by 128 with slack, left 0x80 = -128 against right 0xff = -1 and a last
 // right slot of 127, D' = 128 D - S, is as cheap on the left but dearer on the right, which shows in short chunks: DESIGN 4.3.)
 //
-//   scan    a wave owns NT right tiles of 32 strings; their CAP B fragments (v_mfma_i32_32x32x32_i8: lane = column
+//   waves   a wave owns NT right tiles of 32 strings and one chunk of left rows.  Where none of its right strings fits any
+//           length class of the chunk (46 % of the waves of configs[2]) it returns before it builds anything
+//           (NSM_C3C_EARLY_OUT): the left lengths that fit a right string are an interval around its own length, so the
+//           class nearest to it decides;
+//   scan    the CAP B fragments of the wave's tiles (v_mfma_i32_32x32x32_i8: lane = column
 //           l & 31, 16 of the 32 k of a step in lane half l >> 5 -- here buckets 16 (l >> 5) .. + 15 of code slot s, the SAME
-//           choice on both operands, so the order of k inside the instruction does not matter) are built once from the
-//           right fine histograms.  Left rows come in blocks of 32 of one length class: lane l loads 16 bytes of row l & 31
+//           choice on both operands, so the order of k inside the instruction does not matter) are built from the right fine
+//           histograms at the start, and again from the wave's LDS copy behind a drain between the tiles, which needs their
+//           48 registers.  Left rows come in blocks of 32 of one length class: lane l loads 16 bytes of row l & 31
 //           (a 32-bit offset from the chunk's first row), makes its CAP - 1 indicator fragments, and per tile CAP MFMAs are
 //           chained on an accumulator, the last with the loaded words as they are.  The words of consecutive blocks go to
 //           two register sets in turn (the block loop is unrolled by two), so no word is copied.  The 16 results of a lane
 //           (rows (i & 3) + 8 (i >> 2) + 4 (l >> 5) of the block, column l & 31 of the tile) are folded with v_max3_i32 and
-//           compared with the lane's 64 need - 1 once; only where some lane passes is the 16-bit mask made, a full-rate
-//           v_sub_u32 and a v_alignbit_b32 per result (the sign of 64 need - 1 - D', shifted in from below).  The last block
-//           of a class in a chunk repeats its last row where it is short of 32; only there, a wave-uniform condition, is
-//           the mask of the rows that exist made and applied, inside the mask path: full blocks need none;
+//           compared with the lane's 64 need - 1 once, and that is all the scan asks: WHICH of the 16 rows passed is left to
+//           the drain, so the accumulator is dead after its fold and a tile's epilogue is the fold, a compare and a ballot.
+//           (Until DESIGN 4.3 step 10 a tile with a passing lane -- one in four, with about one such lane -- built a 16-bit
+//           mask in all 64 lanes, 34 full-width instructions.)  The last block of a class in a chunk repeats its last row
+//           where it is short of 32; the repeated rows take part in the fold, and the drain leaves them out;
 //   order   TWO accumulators, tile t in acc[t & 1] (NSM_C3C_PIPE, NT even): the chain of tile t + 1 -- after a block's last
 //           tile that of tile 0 of the class's next block, whose A fragments are made just before -- is issued before the
 //           branch and the push of tile t, its MFMAs with the v_max3_i32 of tile t's fold between them (a chained MFMA waits
@@ -42,23 +48,33 @@
 //           not only under those of the SIMD's other waves.  The pipeline is filled at the start of a length class and is empty at its end,
 //           and it is emptied in front of a drain (no accumulator lives across one); NSM_C3C_PIPE=0 is the order of before,
 //           chain, fold, chain, fold on one accumulator;
-//   stack   lanes whose 16-bit mask is not empty push (block's first row, la, tile, lane, mask) on the wave's LDS stack: one
-//           ballot and one ds_write per tile of 1024 pairs;
+//   stack   lanes whose folded result passes push (block's first row, la, tile, lane, rows of the block that exist) on the
+//           wave's LDS stack, 8 bytes: one ballot per tile of 1024 pairs and one ds_write where it is not empty, at most 64
+//           entries a tile;
 //   drain   whenever more than 128 entries are on the stack, checked every NT tiles (in front of a block's last tile, whose
 //           entries are still pushed before the drain runs, and at the start of a class), 64 entries at a time (64 of 64
-//           lanes busy): lane = one entry, ONE of
-//           its pairs (an entry with more pairs goes back on the stack) -- the exact 32-bucket L1 of the pair (the left
-//           histogram gathered from global memory, the right one read from the wave's copy in LDS, 8 v_sad_u8), then, for
-//           those that remain, the bit-parallel LCS of the pair on the SCALAR unit (raw_lcs_units in indel_raw.hip), one
-//           pair after the other: the longer string of the pair is the pattern, the shorter one the text, and the chain
+//           lanes busy), an entry handled ONCE for all its rows (nothing goes back on the stack).  A pass has four quarters
+//           of 16 entries; in a quarter FOUR lanes have one entry, lane m of them its rows 8 g + 4 (lane >> 5) + m, g = 0 .. 3:
+//           the lane reads the right string's 32-bucket histogram and length from the wave's copy in LDS once and runs the
+//           exact test, min(la, lb) >= need and L1 <= la + lb - 2 need (8 v_sad_u8 a row, the chain started from the negated
+//           budget so that the verdict is its sign), on its four rows, their eight loads issued before the first chain.
+//           The four lanes of an entry read four consecutive rows, 128 contiguous bytes of the left histograms, with each
+//           load (with an entry per lane and 16 rows each, every lane of every load sat in a cache line of its own and the
+//           32-bucket test cost 0.28 ms of the launch instead of 0.04).  The exact test is stricter than the scan's bound
+//           (sum of min <= D), so the coarse result is not needed row by row; rows at or past the entry's row count read
+//           the block's last row and their verdict is dropped, so no pair shows twice.  The result is a 16-bit mask per
+//           lane (bit 4 quarter + g) of the pairs that go on to the bit-parallel LCS on the SCALAR unit (raw_lcs_units in
+//           indel_raw.hip), one pair after the other, lane by lane (the lowest lane of a ballot leads) and within a lane from
+//           its highest bit down, the pair's entry read again from the stack: the longer string of the pair is the pattern,
+//           the shorter one the text, and the chain
 //           stops after a word of four text units where LCS so far + text units left < need (99.5 % of these pairs are
 //           no hits); the two 64-byte rows of the NEXT surviving pair are requested before the current pair's chain runs
 //           (NSM_C3C_LCS_PREFETCH).  Entries carry their row and its length, so the stack outlives the length classes and
 //           is emptied once, at the end.
 //
 // Every test that drops a pair is an upper bound of the LCS: the hits are the one-stage kernel's, the exhaustive kernel's and
-// the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt, profiles/c3_codes_ab.txt, profiles/c3_lcs_ab.txt
-// and DESIGN 4.3.
+// the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt, profiles/c3_codes_ab.txt, profiles/c3_lcs_ab.txt,
+// profiles/c3_rows_ab.txt and DESIGN 4.3.
 #pragma once
 
 namespace nsm {
@@ -75,18 +91,19 @@ namespace nsm {
 #ifndef NSM_C3C_LCS_PREFETCH
 #define NSM_C3C_LCS_PREFETCH 1  // 1: the drain requests the next surviving pair's rows before the current pair's LCS chain
 #endif
-#ifndef NSM_C3C_BRANCHFREE
-#define NSM_C3C_BRANCHFREE 0  // 1: every tile builds its 16-bit masks, no fold and no branch
+#ifndef NSM_C3C_EARLY_OUT
+#define NSM_C3C_EARLY_OUT 1  // 1: a wave whose right strings fit no length class of its chunk returns before its set-up
 #endif
-constexpr int kC3cBlock = 32;                  // left rows per block = right strings per tile: the M and N of the MFMA
+constexpr int kC3cBlock = 32;                // left rows per block = right strings per tile: the M and N of the MFMA
 constexpr int kC3cRights = NSM_C3C_NT * kC3cBlock;  // right strings per wave
 // entries per wave; drained when more than kC3cDrainAt are on it.  NT x 64 pushes between two drain checks, and the pipelined scan
 // pushes one more tile's before the drain it has decided on runs (the pipeline is emptied first)
 constexpr int kC3cStack = (NSM_C3C_NT + 2 + (NSM_C3C_PIPE ? 1 : 0)) * kWave;
 constexpr int kC3cDrainAt = 2 * kWave;
-// a stack entry: low word = the pass mask of 16 left rows (bit i: row (i & 3) + 8 (i >> 2) + 4 (lane >> 5) of the block) against
-// right string tile * 32 + (lane & 31) of the wave, high word = (block's first row - chunk start) << 15 | la << 8 | tile << 6 | lane
-// (a chunk has at most 2^15 rows: nsm_indel_raw_grid)
+// a stack entry: one lane of the scan whose folded result passed, that is its 16 left rows (k & 3) + 8 (k >> 2) + 4 (lane >> 5)
+// of the block, k = 0 .. 15, against right string tile * 32 + (lane & 31) of the wave.  Low word = the number of rows of the block
+// that exist, 1 .. 32 (the drain tests those and no others), high word = (block's first row - chunk start) << 15 | la << 8 |
+// tile << 6 | lane (a chunk has at most 2^15 rows: nsm_indel_raw_grid)
 static_assert(NSM_C3C_NT >= 1 && NSM_C3C_NT <= 4, "an entry keeps its tile in 2 bits");
 // (CAP 2 is the smallest code with an excess slot beside an indicator; beyond 8 the B fragments alone take 128 registers)
 static_assert(NSM_C3C_CAP >= 2 && NSM_C3C_CAP <= 8, "code slots per bucket");
@@ -136,6 +153,29 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   const int half = lane >> 5;              // ... and its 16 buckets of the 32
   const int j0 = (blockIdx.x * kWavesPerBlock + wave) * kRights;
   if (j0 >= p.n_right) return;
+#if NSM_C3C_EARLY_OUT
+  // A wave whose right strings fit no length class of its chunk has nothing to scan: it leaves before it builds its LDS copy
+  // and its B fragments.  For a right string of lb > 0 units the left lengths that fit, min(la, lb) >= lcsmin[la + lb], are an
+  // interval around lb (a step of la towards lb adds one to min(la, lb) or takes one from la + lb, and lcsmin grows by at
+  // most one per unit of la + lb), so the class nearest to lb decides: the chunk's lengths are llen[i1 - 1] .. llen[i0].
+  // (Where empty strings score, zero_need == 0, an empty row fits everything: no wave leaves.)
+  if (p.zero_need != 0) {
+    const int ie = blockIdx.y * p.rows_per_chunk;
+    const int la_hi = llen[ie], la_lo = llen[min(p.n_left, ie + p.rows_per_chunk) - 1];
+    bool fits = false;
+#pragma unroll
+    for (int k = 0; k < (kRights + kWave - 1) / kWave; ++k) {
+      const int j = j0 + k * kWave + lane;
+      if (k * kWave + lane < kRights && j < p.n_right) {
+        const int lb = rlen[j];
+        const int la = min(max(lb, la_lo), la_hi);
+        const int nd = (la == 0 || lb == 0) ? p.zero_need : static_cast<int>(s_lcsmin[la + lb]);
+        fits = fits || min(la, lb) >= nd;
+      }
+    }
+    if (!__any(fits)) return;
+  }
+#endif
   unsigned long long* stack = s_stack + wave * kC3cStack;
   uint32_t* rh_lds = s_rh + wave * 8 * kRights;  // [q][right]
   uint8_t* rl_lds = s_rl + wave * kRights;
@@ -155,9 +195,19 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       rl_lds[rl] = static_cast<uint8_t>(j < p.n_right ? rlen[jcl] : 0);
     }
   }
-  // the B fragments: lane = right string col of tile t, buckets 16 half .. + 15; rows that do not exist are zero
+  // the B fragments: lane = right string col of tile t, buckets 16 half .. + 15; rows that do not exist are zero.  They are
+  // made from global memory here, beside the loads of the LDS copy, and AGAIN from that copy behind every drain between the
+  // tiles: the drain has the loads of eight rows per lane in flight, and 48 registers of fragments alive across it would not
+  // leave room for that at four waves per SIMD
   bool valid[NT];
   c3c_v4i bfrag[NT][CAP];
+  auto code_b = [&](int t, int q, uint32_t fw) {
+    const uint32_t full = c3c_ge64(fw, CAP);  // the last slot: 64 [r >= CAP]
+#pragma unroll
+    for (int s = 0; s < CAP - 1; ++s)  // [r >= s + 1] - [r >= CAP] (the second implies the first: the xor is the difference)
+      bfrag[t][s][q] = static_cast<int>((c3c_ge64(fw, s + 1) ^ full) >> 6);
+    bfrag[t][CAP - 1][q] = static_cast<int>(full);
+  };
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int j = j0 + t * kC3cBlock + col;
@@ -165,16 +215,16 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const int jcl = valid[t] ? j : p.n_right - 1;
     uint4 f = reinterpret_cast<const uint4*>(rhist + static_cast<size_t>(jcl) * 8)[half];
     if (!valid[t]) f = make_uint4(0u, 0u, 0u, 0u);
-    const uint32_t fw[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint32_t full = c3c_ge64(fw[q], CAP);  // the last slot: 64 [r >= CAP]
-#pragma unroll
-      for (int s = 0; s < CAP - 1; ++s)  // [r >= s + 1] - [r >= CAP] (the second implies the first: the xor is the difference)
-        bfrag[t][s][q] = static_cast<int>((c3c_ge64(fw[q], s + 1) ^ full) >> 6);
-      bfrag[t][CAP - 1][q] = static_cast<int>(full);
-    }
+    code_b(t, 0, f.x); code_b(t, 1, f.y); code_b(t, 2, f.z); code_b(t, 3, f.w);
   }
+  auto make_bfrag = [&]() {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const uint32_t* rp = rh_lds + (4 * half) * kRights + t * kC3cBlock + col;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) code_b(t, q, valid[t] ? rp[q * kRights] : 0u);
+    }
+  };
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const int i0 = blockIdx.y * p.rows_per_chunk;
@@ -183,104 +233,143 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
 
   auto need_of = [&](int la, int lb) -> int { return (la == 0 || lb == 0) ? p.zero_need : static_cast<int>(s_lcsmin[la + lb]); };
 
-  // pop up to 64 entries: lane = one entry, its first pair; entries with more pairs go back on the stack
+  // a left row's bytes as a 32-bit offset from the chunk's first row (a chunk has at most 2^15 rows of 32 bytes)
+  const char* chunk = reinterpret_cast<const char*>(lhist + static_cast<size_t>(i0) * 8);
+
+  // pop up to 64 entries and test their rows, a ROW per lane: in quarter s of the pass the four lanes 4 u .. 4 u + 3 have entry
+  // 16 s + u, lane 4 u + m its rows 8 g + 4 eh + m, g = 0 .. 3 (eh = the entry's lane half of the scan; the C layout of the
+  // 32x32 MFMA).  So the four lanes of an entry read 128 contiguous bytes of lhist with each load -- with an entry per lane
+  // (16 rows each) every lane of a load was in a cache line of its own, and the pass was bound by that: DESIGN 4.3 step 10.
   auto drain_pass = [&]() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const int n = min(q_cnt, kWave);
     const int base = q_cnt - n;
-    const bool active = lane < n;
+    q_cnt = base;  // (no entry goes back; nothing is pushed before the pass ends, so the slots [base, base + n) stay readable)
 #ifdef NSM_C3C_X_NODRAIN  // (timing experiments: the entries are dropped)
-    q_cnt = base;
     return;
 #endif
-    const unsigned long long e = stack[base + (active ? lane : 0)];
-    uint32_t bits = active ? static_cast<uint32_t>(e) : 0u;
-    const uint32_t ehi = static_cast<uint32_t>(e >> 32);
-    const int el = static_cast<int>(ehi & 63u);
-    const int t = static_cast<int>((ehi >> 6) & 3u);
-    const int la = static_cast<int>((ehi >> 8) & 127u);
-    const int ib = i0 + static_cast<int>(ehi >> 15);
-    const int pos = active ? 31 - __clz(bits) : 0;  // (an entry on the stack has a bit set)
-    bits &= ~(1u << pos);
-    const int r = (pos & 3) + 8 * (pos >> 2) + 4 * (el >> 5);  // (the C layout of the 32x32 MFMA)
-    const int tl = t * kC3cBlock + (el & 31);
-    const int row = active ? ib + r : i0;
-    // the 32-bucket filter of the pair
-    const uint4* lp = reinterpret_cast<const uint4*>(lhist + static_cast<size_t>(row) * 8);
-    const uint4 l0 = lp[0], l1v = lp[1];
-    const int lb = rl_lds[tl];
-    uint32_t rq[8];
-    {
-      const uint32_t* rp = rh_lds + tl;
+    const int m = lane & 3;
+    // bit 4 s + g of the lane's mask = [row 8 g + 4 eh + m of entry 16 s + (lane >> 2) goes on to the LCS]: the verdicts are
+    // shifted in from below, the highest quarter and g = 3 first.  The quarters are turns of a loop that is NOT unrolled, and a
+    // quarter without entries is left out (most waves only ever drain a short stack, at their end).  The eight loads of a
+    // lane's four rows need the entry alone, so they are issued first, and the right string is read while they are under way:
+    // a quarter pays one memory round trip, and 32 registers hold the rows, no more (two quarters in flight: 153 registers)
+    uint32_t mask = 0;
+#pragma nounroll
+    for (int s = (n - 1) >> 4; s >= 0; --s) {
+      const int e = 16 * s + (lane >> 2);
+      const bool active = e < n;
+      const unsigned long long ent = stack[base + (active ? e : 0)];
+      const int n_rows = active ? static_cast<int>(static_cast<uint32_t>(ent)) : 0;  // 1 .. 32 rows of the block exist
+      const uint32_t ehi = static_cast<uint32_t>(ent >> 32);
+      const uint32_t ib_rel = active ? ehi >> 15 : 0u;  // the block's first row, from the chunk's
+      // rows at or past the entry's row count read the block's last row, as the scan did, and their verdict is dropped:
+      // the repeated row must not be reported again
+      const int r0 = 4 * static_cast<int>((ehi >> 5) & 1u) + m;
+      const uint32_t last_r = static_cast<uint32_t>(max(n_rows, 1) - 1);
+      uint4 w0[4], w1[4];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) rq[q] = rp[q * kRights];
+      for (int g = 0; g < 4; ++g) {
+        const uint4* lp = reinterpret_cast<const uint4*>(chunk + (ib_rel + min(static_cast<uint32_t>(r0 + 8 * g), last_r)) * 32u);
+        w0[g] = lp[0];
+        w1[g] = lp[1];
+      }
+      // the right string: its 32-bucket histogram and its length from the wave's copy, once for the lane's four rows
+      const int la = static_cast<int>((ehi >> 8) & 127u);
+      const int tl = static_cast<int>((ehi >> 6) & 3u) * kC3cBlock + static_cast<int>(ehi & 31u);
+      const int lb = rl_lds[tl];
+      uint32_t rq[8];
+      {
+        const uint32_t* rp = rh_lds + tl;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) rq[q] = rp[q * kRights];
+      }
+      const int nd = need_of(la, lb);
+      // L1 <= la + lb - 2 need as the SIGN of L1 - (la + lb - 2 need) - 1: the v_sad_u8 chain starts from the negated budget
+      // (L1 <= 128, the budget is -1 .. 128; -1 where the lengths alone rule the pair out: then the chain starts from 0)
+      const int budget = (active && min(la, lb) >= nd) ? la + lb - 2 * nd : -1;
+      const uint32_t sad0 = ~static_cast<uint32_t>(budget);
+#pragma unroll
+      for (int g = 3; g >= 0; --g) {
+        uint32_t l1 = sad0;
+        l1 = __builtin_amdgcn_sad_u8(w0[g].x, rq[0], l1);
+        l1 = __builtin_amdgcn_sad_u8(w0[g].y, rq[1], l1);
+        l1 = __builtin_amdgcn_sad_u8(w0[g].z, rq[2], l1);
+        l1 = __builtin_amdgcn_sad_u8(w0[g].w, rq[3], l1);
+        l1 = __builtin_amdgcn_sad_u8(w1[g].x, rq[4], l1);
+        l1 = __builtin_amdgcn_sad_u8(w1[g].y, rq[5], l1);
+        l1 = __builtin_amdgcn_sad_u8(w1[g].z, rq[6], l1);
+        l1 = __builtin_amdgcn_sad_u8(w1[g].w, rq[7], l1);
+        if (r0 + 8 * g >= n_rows) l1 = 0u;
+        mask = __builtin_amdgcn_alignbit(mask, l1, 31);
+      }
     }
-    uint32_t l1 = 0;
-    l1 = __builtin_amdgcn_sad_u8(l0.x, rq[0], l1);
-    l1 = __builtin_amdgcn_sad_u8(l0.y, rq[1], l1);
-    l1 = __builtin_amdgcn_sad_u8(l0.z, rq[2], l1);
-    l1 = __builtin_amdgcn_sad_u8(l0.w, rq[3], l1);
-    l1 = __builtin_amdgcn_sad_u8(l1v.x, rq[4], l1);
-    l1 = __builtin_amdgcn_sad_u8(l1v.y, rq[5], l1);
-    l1 = __builtin_amdgcn_sad_u8(l1v.z, rq[6], l1);
-    l1 = __builtin_amdgcn_sad_u8(l1v.w, rq[7], l1);
-    const int nd = need_of(la, lb);
-    bool pass = active && min(la, lb) >= nd && static_cast<int>(l1) <= la + lb - 2 * nd;
-    // entries with pairs left go back (every lane has read its entry: the slots [base, base + n) are free)
-    __builtin_amdgcn_wave_barrier();
-    const bool more = bits != 0u;
-    const unsigned long long mm = __ballot(more);
-    if (more) {
-      const int slot = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mm >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mm), 0u));
-      stack[slot] = (static_cast<unsigned long long>(ehi) << 32) | bits;
-    }
-    q_cnt = base + __popcll(mm);
     // the pairs that remain, one after the other on the scalar unit
 #ifdef NSM_C3C_X_NOLCS  // (timing experiments)
-    pass = false;
+    mask = 0u;
 #endif
 #ifdef NSM_C3C_X_FINEONLY  // (timing experiments: the 32-bucket test runs, nobody passes -- not known at compile time)
-    pass = pass && p.n_left < 0;
+    mask = p.n_left < 0 ? mask : 0u;
 #endif
-    const int jp = j0 + tl;
     // Each pair is two 64-byte loads and the scalar chain of raw_lcs_units, which stops early for most pairs (the pair's need
-    // goes with it).  NSM_C3C_LCS_PREFETCH: the rows of the NEXT surviving pair are requested before the current pair's
-    // chain runs, whether that chain stops early or not.
-    unsigned long long todo = __ballot(pass);
-    auto row_units = [&](unsigned long long left_todo, uint32_t& lc, uint32_t& rc) {
-      const int leader = __builtin_ctzll(left_todo);
-      lc = lcodes[static_cast<size_t>(__builtin_amdgcn_readlane(row, leader)) * 64 + lane];
-      rc = rcodes[static_cast<size_t>(__builtin_amdgcn_readlane(jp, leader)) * 64 + lane];
+    // goes with it).  The pairs are walked lane by lane (the lowest lane of the ballot leads), a lane's from its highest bit
+    // down: `cur` holds the leader's bits that are left, on the scalar unit, and a pair's entry is read again from the stack
+    // (one address for the whole wave).  NSM_C3C_LCS_PREFETCH: the rows of the NEXT surviving pair are requested before the
+    // current pair's chain runs, whether that chain stops early or not.
+    unsigned long long todo = __ballot(mask != 0u);  // lanes whose pairs have not begun
+    uint32_t cur = 0u;
+    int leader = 0, row_s = 0, j_n = 0, la_n = 0, lb_n = 0;
+    auto next_pair = [&]() -> bool {  // (wave-uniform) the next pair: left row, right row and the two lengths
+      if (cur == 0u) {
+        if (todo == 0ull) return false;
+        leader = __builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        cur = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(mask), leader));
+      }
+      const int pos = 31 - __builtin_clz(cur);  // bit 4 s + g of lane 4 u + m
+      cur &= ~(1u << pos);
+      const uint32_t ehi = static_cast<uint32_t>(
+          __builtin_amdgcn_readfirstlane(static_cast<int>(stack[base + 16 * (pos >> 2) + (leader >> 2)] >> 32)));
+      const int tl = static_cast<int>((ehi >> 6) & 3u) * kC3cBlock + static_cast<int>(ehi & 31u);
+      row_s = i0 + static_cast<int>(ehi >> 15) + 8 * (pos & 3) + 4 * static_cast<int>((ehi >> 5) & 1u) + (leader & 3);
+      j_n = j0 + tl;
+      la_n = static_cast<int>((ehi >> 8) & 127u);
+      lb_n = __builtin_amdgcn_readfirstlane(static_cast<int>(rl_lds[tl]));
+      return true;
+    };
+    auto row_units = [&](uint32_t& lc, uint32_t& rc) {
+      lc = lcodes[static_cast<size_t>(row_s) * 64 + lane];
+      rc = rcodes[static_cast<size_t>(j_n) * 64 + lane];
     };
     uint32_t lc_next = 0, rc_next = 0;
-    if (NSM_C3C_LCS_PREFETCH && todo) row_units(todo, lc_next, rc_next);
-    while (todo) {
-      const int leader = __builtin_ctzll(todo);
-      const int row_s = __builtin_amdgcn_readlane(row, leader);
-      const int j_s = __builtin_amdgcn_readlane(jp, leader);
-      const int la_s = __builtin_amdgcn_readlane(la, leader);
-      const int lb_s = __builtin_amdgcn_readlane(lb, leader);
+    bool have = next_pair();
+    if (NSM_C3C_LCS_PREFETCH && have) row_units(lc_next, rc_next);
+    while (have) {
+      const int row_c = row_s, j_s = j_n, la_s = la_n, lb_s = lb_n;
       const int need_s = need_of(la_s, lb_s);
       uint32_t lc = lc_next, rc = rc_next;
-      if (!NSM_C3C_LCS_PREFETCH) row_units(todo, lc, rc);
-      todo &= todo - 1ull;
-      if (NSM_C3C_LCS_PREFETCH && todo) row_units(todo, lc_next, rc_next);
+      if (!NSM_C3C_LCS_PREFETCH) row_units(lc, rc);
+      have = next_pair();
+      if (NSM_C3C_LCS_PREFETCH && have) row_units(lc_next, rc_next);
       const int lcs = raw_lcs_units(lc, la_s, rc, lb_s, need_s, lane);
 #ifdef NSM_C3C_X_COUNTLCS  // (experiments: one record per LCS call)
       if (lane == 0)
 #else
       if (lcs >= need_s && lane == 0)
 #endif
-        emit_hit(hits, p.cap, count, indel_score(la_s, lb_s, lcs), lorig[row_s], rorig[j_s]);
+        emit_hit(hits, p.cap, count, indel_score(la_s, lb_s, lcs), lorig[row_c], rorig[j_s]);
     }
+  };
+  // the drain between the tiles of the scan: full passes only (the rest waits for more), then the B fragments again
+  auto drain_full = [&]() {
+    while (q_cnt >= kWave) drain_pass();
+    make_bfrag();
   };
 
   // rows are sorted by length (descending): rows of length 64 - c are [lstart[c], lstart[c + 1])
   const int c_first = 64 - llen[i0];
   const int c_last = 64 - llen[i1 - 1];
-  // a left row's bytes as a 32-bit offset from the chunk's first row (a chunk has at most 2^15 rows of 32 bytes)
-  const char* chunk = reinterpret_cast<const char*>(lhist + static_cast<size_t>(i0) * 8);
   const uint32_t lane_off = static_cast<uint32_t>(col * 32 + half * 16);
   for (int c = c_first; c <= c_last; ++c) {
     const int a = max(i0, lstart[c]);
@@ -329,37 +418,24 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       for (int k = 3; k < 15; k += 2) top = max(max(top, acc[k]), acc[k + 1]);
       return max(top, acc[15]);
     };
-    // the lane's 16 rows that exist of a block of n_rows < 32 rows
-    auto exist_of = [&](int n_rows) -> uint32_t {
-      const uint32_t rows = (1u << n_rows) - 1u;  // (wave-uniform) bit r: the block's row r exists
-      const uint32_t x = rows >> (4 * half);  // bit k of the result = bit (k & 3) + 8 (k >> 2) of x
-      return (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);
-    };
-    // compare and push of tile t of the block at row i
-    auto finish = [&](int top, const c3c_v16i& acc, int t, int i) {
-#if !NSM_C3C_BRANCHFREE
-      if (!__any(top > nm1[t])) return;
-#endif
-      // bit k = [acc[k] >= need]: the sign of nm1 - acc[k], shifted in from below (k = 15 first)
-      uint32_t mask = 0;
-#pragma unroll
-      for (int k = 15; k >= 0; --k) mask = __builtin_amdgcn_alignbit(mask, static_cast<uint32_t>(nm1[t] - acc[k]), 31);
-      // a block is short of rows only as a class's last (wave-uniform); the rows past the end repeat the last one
-      if (b - i < kC3cBlock) mask &= exist_of(b - i);
-      // lanes with a pair that passed push: one ballot and one ds_write per tile
-      const bool nz = mask != 0u;
-      const unsigned long long m = __ballot(nz);
-      if (m != 0ull) {
-        if (nz) {
-          const int slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), static_cast<uint32_t>(q_cnt)));
-          // (the wave-uniform part first: one v_or at the push instead of a register per tile)
-          const uint32_t hi = (static_cast<uint32_t>(i - i0) << 15) | (static_cast<uint32_t>(la) << 8) | (static_cast<uint32_t>(t) << 6);
-          uint32_t el = static_cast<uint32_t>(lane);
-          asm volatile("" : "+v"(el));  // (opaque: or-ed in here, not kept in a register per tile and class)
-          stack[slot] = (static_cast<unsigned long long>(hi | el) << 32) | mask;
-        }
-        q_cnt += __popcll(m);
+    // compare and push of tile t of the block at row i: the lanes whose folded result passes push one entry, at most 64 a
+    // tile as before (kC3cStack, kC3cDrainAt and their static_assert hold unchanged).  Which of a lane's 16 rows passed is
+    // not worked out here: the accumulator is dead after the fold, and the drain's exact test decides every row by itself
+    auto finish = [&](int top, int t, int i) {
+      const bool ps = top > nm1[t];
+      const unsigned long long m = __ballot(ps);
+      if (m == 0ull) return;
+      if (ps) {
+        const int slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), static_cast<uint32_t>(q_cnt)));
+        // (the wave-uniform part first: one v_or at the push instead of a register per tile)
+        const uint32_t hi = (static_cast<uint32_t>(i - i0) << 15) | (static_cast<uint32_t>(la) << 8) | (static_cast<uint32_t>(t) << 6);
+        uint32_t el = static_cast<uint32_t>(lane);
+        asm volatile("" : "+v"(el));  // (opaque: or-ed in here, not kept in a register per tile and class)
+        // the rows of the block that exist (wave-uniform): it is short only as the last of its class in the chunk
+        const uint32_t n_rows = static_cast<uint32_t>(min(kC3cBlock, b - i));
+        stack[slot] = (static_cast<unsigned long long>(hi | el) << 32) | n_rows;
       }
+      q_cnt += __popcll(m);
     };
 #if NSM_C3C_PIPE
     // software pipeline over the tiles and the blocks of the class: acc[t & 1] holds tile t, and the chain of the tile after
@@ -398,10 +474,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        finish(top, acc[t & 1], t, i);
+        finish(top, t, i);
       }
       if (flush) {
-        while (q_cnt >= kWave) drain_pass();  // full passes only: the rest waits for more
+        drain_full();
         if (more) {
           make_afrag(wn);
           if (i + 2 * kC3cBlock < b) wc = load_rows(i + 2 * kC3cBlock);
@@ -410,7 +486,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       }
     };
     if (q_cnt > kC3cDrainAt)  // (a class of one block has no other check in front of its first NT - 1 tiles)
-      while (q_cnt >= kWave) drain_pass();
+      drain_full();
     uint4 w0 = load_rows(a);
     make_afrag(w0);
     uint4 w1 = w0;  // (once per class, outside the block loop: a class of one block never loads the second set)
@@ -429,12 +505,12 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       if (i + kC3cBlock < b) w_next = load_rows(i + kC3cBlock);
       // a block pushes up to NT x 64 entries
       if (q_cnt > kC3cDrainAt)
-        while (q_cnt >= kWave) drain_pass();  // full passes only: the rest waits for more
+        drain_full();
       make_afrag(w);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const c3c_v16i acc = chain(t, w);
-        finish(fold(acc), acc, t, i);
+        finish(fold(acc), t, i);
       }
     }
 #endif
