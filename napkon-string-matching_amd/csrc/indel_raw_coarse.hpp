@@ -4,50 +4,83 @@
 // 32-bucket symbol histograms.  This kernel asks a cheaper question first, and asks it on the MATRIX pipe, which the
 // one-stage kernel leaves idle.  With a_b, r_b the counts of bucket b (symbol & 31) in the left and the right string,
 // LCS <= sum_b min(a_b, r_b), and a minimum is a dot product of thermometer codes: min(a, r) = sum_k [a >= k][r >= k].
-// The scan uses the bound D = sum_b D_b with D_b = min(a_b, r_b) where r_b < CAP and D_b = a_b where r_b >= CAP
-// (a_b >= min(a_b, r_b)), so D >= sum_b min(a_b, r_b) >= LCS and "D >= need" is a NECESSARY condition of a hit,
-// need = lcsmin[la + lb].  Every bucket gets CAP code slots (K = 32 CAP), of MIXED weight, so that all the arithmetic of the
-// code sits on the right side, which a wave builds once, and the left side, which every wave builds again for every
-// block, costs two instructions a word and slot:
+// The scan computes a bound D = sum_b D_b >= sum_b min(a_b, r_b) >= LCS, so "D >= need" is a NECESSARY condition of a hit,
+// need = lcsmin[la + lb].  The exact length filter min(la, lb) >= need stays in front as need = kNever, which no D reaches,
+// and need = 0 passes everything.
+//
+// The codes (NSM_C3C_FP4, the default): FOUR slots per bucket in FP4 (E2M1: 0, 0.5, 1, 1.5, 2, 3, 4, 6), K = 128, in TWO
+// v_mfma_f32_32x32x64_f8f6f4 per tile of 32 x 32 pairs, each of the cycles of ONE of the three v_mfma_i32_32x32x32_i8 that
+// the i8 codes below take (tools/mfma_fp4_probe: 16.9 ns against 16.0 in a chain, profiles/c3_fp4_ab.txt).  Indicators on
+// the left, the count on the right:
+//
+//   slot   left nibble          right nibble                                      MFMA, nibble of the count's byte
+//   1      2.0 [a_b >= 1]       0.5 [r_b >= 1]                                    first (unscaled form), low
+//   2      2.0 [a_b >= 2]       0.5 [r_b >= 2]                                    first, high
+//   3      2.0 [a_b >= 3]       0.5 [r_b >= 3]                                    second (B scale 2^k), low
+//   4      2.0 [a_b >= 4]       E / 2, E = ceil((r_b - 3) / 2^k) rounded UP to    second, high
+//                               the next of 0, 1, 2, 3, 4, 6, 8, 12
+//
+// D_b = [a>=1][r>=1] + [a>=2][r>=2] + 2^k ([a>=3][r>=3] + [a>=4] E).
+//
+//   scale   k is the right string's block scale exponent: the smallest with max_b r_b - 3 <= 12 x 2^k over ALL its 32
+//           buckets.  Both lanes of a string get the same E8M0 byte, so nothing depends on how the hardware maps lanes to
+//           scale blocks.  k = 0 where no count exceeds 15, which is every string of the benchmark; k <= 3.
+//   bound   for a <= 3: D_b = min(a, r, 2) + 2^k [a >= 3][r >= 3] >= min(a, r), with equality where k = 0;
+//           for a >= 4: D_b >= min(r, 3) + max(r - 3, 0) = r >= min(a, r).
+//   exact   every value is a multiple of 1/2 far below 2^24, so the f32 accumulation is exact; D <= 128 < kNever
+//           (test_no_bound_reaches_never), and the test is D > need - 1/2.  No value is negative, so the f32 bits order
+//           as integers do: the fold and the compare are the integer ones of the i8 scan, against the bits of need - 1/2
+//           (those of -1/2, need = 0, are a negative integer).
+//   layout  both operands of a slot put the same 16 buckets in lane half l >> 5 and the same slot in the same nibble, so
+//           the order of k inside the instruction does not matter.
+//   left    six instructions a loaded word for both MFMAs: (w + 0x3c3c3c3c) & 0x43434343 is, byte by byte, the count
+//           where it is below 4 and 0x40 or more where it is not.  As the selector of v_perm_b32 it reads a four-byte
+//           table for 0 .. 3 and gives 0xff from 13 on, which a mask turns into "both nibbles set".
+//           (NSM_C3C_FP4_PERM=0: two adds, two ands, a shift and an or a word and MFMA; slower)
+//   right   made once by the wave and again behind a drain.  k = 0: byte tables too, v_perm_b32 with the count's low
+//           three bits as the selector and the table of 0 .. 7 or of 8 .. 15 by its bit 3.  k > 0: byte by byte, the
+//           excess through a 13-nibble table in a 64-bit constant.
+//
+// tests/support/scan_fp4.py restates the codes; tests/test_cpu_indel_raw_scan_fp4.py checks every count.
+//
+// The i8 codes (NSM_C3C_FP4=0, the scan of before: DESIGN 4.3 steps 6 to 10): D_b = min(a_b, r_b) where r_b < CAP and a_b
+// where r_b >= CAP, CAP slots of MIXED weight per bucket (K = 32 CAP, CAP v_mfma_i32_32x32x32_i8 per tile):
 //
 //   left row,  slot s < CAP - 1:  64 [a_b >= s + 1]   right row, slot s < CAP - 1:  [r_b >= s + 1] - [r_b >= CAP]   (0 or 1)
 //   left row,  last slot:         a_b                 right row, last slot:         64 [r_b >= CAP]
 //
-// Where r_b < CAP the indicator slots give 64 sum_{k < CAP} [a_b >= k][r_b >= k] = 64 min(a_b, r_b, CAP - 1) = 64 min(a_b, r_b)
-// and the last slot nothing; where r_b >= CAP the right indicator slots are all zero and the last slot gives 64 a_b.  So
-// the dot product is D' = 64 D EXACTLY, and the test is D' >= 64 need, kept as D' > 64 need - 1.  Every operand byte is
-// 0 .. 64 (a stride-64 row has a_b <= 64): the i8 operands are never negative, D' <= 4096, and a pair that cannot fit has
-// need = kNever, 64 x 255 > 4096.  need = 0 passes everything.  The exact length filter min(la, lb) >= need stays in
-// front as need = kNever.  Integer arithmetic: nothing here rounds.  (64 [c >= k] of four counts in a word is
-// (w + (0x40 - k) 0x01010101) & 0x40404040: c + 0x40 - k is 56 .. 127, with bit 6 exactly where c >= k, and the last left
-// slot is the loaded word itself.  A code that scales by 128 with slack, left 0x80 = -128 against right 0xff = -1 and a last
-// right slot of 127, D' = 128 D - S, is as cheap on the left but dearer on the right, which shows in short chunks: DESIGN 4.3.)
+// The dot product is D' = 64 D exactly, tested as D' > 64 need - 1; every operand byte is 0 .. 64 (a stride-64 row has
+// a_b <= 64), D' <= 4096 < 64 kNever.  64 [c >= k] of four counts in a word is (w + (0x40 - k) 0x01010101) & 0x40404040, and
+// the last left slot is the loaded word itself.
 //
 //   waves   a wave owns NT right tiles of 32 strings and one chunk of left rows.  Where none of its right strings fits any
 //           length class of the chunk (46 % of the waves of configs[2]) it returns before it builds anything
 //           (NSM_C3C_EARLY_OUT): the left lengths that fit a right string are an interval around its own length, so the
 //           class nearest to it decides;
-//   scan    the CAP B fragments of the wave's tiles (v_mfma_i32_32x32x32_i8: lane = column
-//           l & 31, 16 of the 32 k of a step in lane half l >> 5 -- here buckets 16 (l >> 5) .. + 15 of code slot s, the SAME
-//           choice on both operands, so the order of k inside the instruction does not matter) are built from the right fine
-//           histograms at the start, and again from the wave's LDS copy behind a drain between the tiles, which needs their
-//           48 registers.  Left rows come in blocks of 32 of one length class: lane l loads 16 bytes of row l & 31
-//           (a 32-bit offset from the chunk's first row), makes its CAP - 1 indicator fragments, and per tile CAP MFMAs are
-//           chained on an accumulator, the last with the loaded words as they are.  The words of consecutive blocks go to
-//           two register sets in turn (the block loop is unrolled by two), so no word is copied.  The 16 results of a lane
-//           (rows (i & 3) + 8 (i >> 2) + 4 (l >> 5) of the block, column l & 31 of the tile) are folded with v_max3_i32 and
-//           compared with the lane's 64 need - 1 once, and that is all the scan asks: WHICH of the 16 rows passed is left to
-//           the drain, so the accumulator is dead after its fold and a tile's epilogue is the fold, a compare and a ballot.
-//           (Until DESIGN 4.3 step 10 a tile with a passing lane -- one in four, with about one such lane -- built a 16-bit
-//           mask in all 64 lanes, 34 full-width instructions.)  The last block of a class in a chunk repeats its last row
-//           where it is short of 32; the repeated rows take part in the fold, and the drain leaves them out;
+//   scan    the B fragments of the wave's tiles: lane = column l & 31, buckets 16 (l >> 5) .. + 15.  FP4: two fragments
+//           of four registers a tile and one register with the four tiles' scale bytes, picked with op_sel; a lane reads
+//           both halves of its string at the start, for the scale.  i8: CAP fragments a tile.  They are built from the
+//           right fine histograms at the start, and again from the wave's LDS copy behind a drain between the tiles,
+//           which needs their registers.
+//           Left rows come in blocks of 32 of one length class: lane l loads 16 bytes of row l & 31 (a 32-bit offset from
+//           the chunk's first row) and makes its A fragments: two with FP4; CAP - 1 with i8, where the last slot is the
+//           loaded words as they are.  Per tile the MFMAs are chained on an accumulator.  The words of consecutive blocks
+//           go to two register sets in turn (the block loop is unrolled by two), so no word is copied.
+//           The 16 results of a lane (rows (i & 3) + 8 (i >> 2) + 4 (l >> 5) of the block, column l & 31 of the tile: the
+//           C layout of the 32x32 MFMA does not depend on the operand type) are folded with v_max3_i32 and compared with
+//           the lane's need once, and that is all the scan asks: WHICH of the 16 rows passed is left to the drain, so the
+//           accumulator is dead after its fold and a tile's epilogue is the fold, a compare and a ballot.  The last block
+//           of a class in a chunk repeats its last row where it is short of 32; the repeated rows take part in the fold,
+//           and the drain leaves them out;
 //   order   TWO accumulators, tile t in acc[t & 1] (NSM_C3C_PIPE, NT even): the chain of tile t + 1 -- after a block's last
 //           tile that of tile 0 of the class's next block, whose A fragments are made just before -- is issued before the
-//           branch and the push of tile t, its MFMAs with the v_max3_i32 of tile t's fold between them (a chained MFMA waits
-//           for the one before it, and a wave issues in order), so the matrix pipe works under the wave's own epilogue and
-//           not only under those of the SIMD's other waves.  The pipeline is filled at the start of a length class and is empty at its end,
-//           and it is emptied in front of a drain (no accumulator lives across one); NSM_C3C_PIPE=0 is the order of before,
-//           chain, fold, chain, fold on one accumulator;
+//           branch and the push of tile t, with the v_max3_i32 of tile t's fold between and behind its MFMAs (a chained
+//           MFMA waits for the one before it, and a wave issues in order).  FP4: MFMA, four of the fold's eight, MFMA,
+//           four (NSM_C3C_FP4_SPLIT); an empty asm that names the new accumulator keeps the second MFMA in front of the
+//           branch.  So the matrix pipe works under the wave's own epilogue and not only under those of the SIMD's other
+//           waves.  The pipeline is filled at the start of a length class and is empty at its end, and it is emptied in
+//           front of a drain (no accumulator lives across one); NSM_C3C_PIPE=0 is the order of before, chain, fold,
+//           chain, fold on one accumulator;
 //   stack   lanes whose folded result passes push (block's first row, la, tile, lane, rows of the block that exist) on the
 //           wave's LDS stack, 8 bytes: one ballot per tile of 1024 pairs and one ds_write where it is not empty, at most 64
 //           entries a tile;
@@ -74,13 +107,22 @@
 //
 // Every test that drops a pair is an upper bound of the LCS: the hits are the one-stage kernel's, the exhaustive kernel's and
 // the oracle's.  Measurements: profiles/c3_mfma_ab.txt, profiles/c3_pipe_ab.txt, profiles/c3_codes_ab.txt, profiles/c3_lcs_ab.txt,
-// profiles/c3_rows_ab.txt and DESIGN 4.3.
+// profiles/c3_rows_ab.txt, profiles/c3_fp4_ab.txt and DESIGN 4.3.
 #pragma once
 
 namespace nsm {
 
 #ifndef NSM_C3C_CAP
-#define NSM_C3C_CAP 3  // code slots per bucket (4: an eighth of the survivors, a third more MFMAs)
+#define NSM_C3C_CAP 3  // i8 scan: code slots per bucket (4: an eighth of the survivors, a third more MFMAs)
+#endif
+#ifndef NSM_C3C_FP4
+#define NSM_C3C_FP4 1  // 1: FP4 codes, four slots per bucket in two MFMAs (CAP is not used); 0: the i8 scan, CAP MFMAs per tile
+#endif
+#ifndef NSM_C3C_FP4_PERM
+#define NSM_C3C_FP4_PERM 1  // 1: the left operand words from a v_perm_b32 byte table; 0: two adds, a shift and three ands each
+#endif
+#ifndef NSM_C3C_FP4_SPLIT
+#define NSM_C3C_FP4_SPLIT 4  // instructions of a tile's fold between the two MFMAs of the next tile's chain (the rest behind them)
 #endif
 #ifndef NSM_C3C_NT
 #define NSM_C3C_NT 4  // right tiles of 32 strings per wave
@@ -116,10 +158,87 @@ static inline size_t c3c_lds_bytes() {
 
 typedef int c3c_v4i __attribute__((ext_vector_type(4)));
 typedef int c3c_v16i __attribute__((ext_vector_type(16)));
+typedef int c3c_v8i __attribute__((ext_vector_type(8)));
+typedef float c3c_v16f __attribute__((ext_vector_type(16)));
 
 // 64 [c >= k] in each of the four bytes of w (0 <= c <= 64, 1 <= k <= 8: c + 0x40 - k is 56 .. 127, bit 6 where c >= k)
 __device__ __forceinline__ uint32_t c3c_ge64(uint32_t w, int k) {
   return (w + static_cast<uint32_t>(0x40 - k) * 0x01010101u) & 0x40404040u;
+}
+
+// --- the FP4 codes (NSM_C3C_FP4).  E2M1 nibbles: 0, 0.5, 1, 1.5, 2, 3, 4, 6 for codes 0 .. 7 (bit 3 is the sign: never set).
+
+// the scale exponent k of a right string from its eight histogram words: the smallest k with max(r_b) - 3 <= 12 x 2^k, so
+// that its largest excess fits the grid {0, 1, 2, 3, 4, 6, 8, 12} 2^k.  k = 0 exactly where no count has a bit above 15
+__device__ __forceinline__ int c3c_fp4_scale(const uint4& f0, const uint4& f1) {
+  const uint32_t ws[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+  uint32_t any = 0u;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) any |= ws[q];
+  if ((any & 0xf0f0f0f0u) == 0u) return 0;
+  uint32_t top = 0u;
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) top = max(top, (ws[q] >> (8 * b)) & 0xffu);
+  return top <= 27u ? 1 : top <= 51u ? 2 : 3;
+}
+// the right operand words of four counts.  m1: 0.5 [r >= 1] in the low nibble of a count's byte, 0.5 [r >= 2] in the high
+// one.  m2: 0.5 [r >= 3] in the low nibble; in the high one E, the excess max(r - 3, 0) over 2^k rounded UP to the next of
+// 0, 1, 2, 3, 4, 6, 8, 12, as the code of its half (the left indicator is 2.0).
+// k = 0 (every count <= 15, nearly every string): both bytes of a count from 8-entry byte tables, v_perm_b32 with the
+// count's low three bits as the selector, the table of 0 .. 7 or that of 8 .. 15 by its bit 3 -- ten instructions a word
+// where a byte at a time takes forty, and a wave that scans a short chunk pays for its set-up
+__device__ __forceinline__ void c3c_fp4_right_k0(uint32_t fw, int& m1, int& m2) {
+  const uint32_t sel = fw & 0x07070707u;
+  const uint32_t big = ((fw >> 3) & 0x01010101u) * 0xffu;  // 0xff where 8 <= r <= 15
+  const uint32_t lo1 = __builtin_amdgcn_perm(0x11111111u, 0x11110100u, sel);
+  const uint32_t lo2 = __builtin_amdgcn_perm(0x41312111u, 0x01000000u, sel), hi2 = __builtin_amdgcn_perm(0x71717171u, 0x61615151u, sel);
+  m1 = static_cast<int>((big & 0x11111111u) | (~big & lo1));
+  m2 = static_cast<int>((big & hi2) | (~big & lo2));
+}
+// k > 0: byte by byte, E from the table's nibble 4 q for q = 0 .. 12
+__device__ __forceinline__ void c3c_fp4_right_scaled(uint32_t fw, int k, int& m1, int& m2) {
+  m1 = static_cast<int>((c3c_ge64(fw, 1) >> 6) | (c3c_ge64(fw, 2) >> 2));
+  uint32_t w2 = c3c_ge64(fw, 3) >> 6;
+  const uint32_t round_up = (1u << k) - 1u;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const uint32_t r = (fw >> (8 * b)) & 0xffu;
+    const uint32_t q = (max(r, 3u) - 3u + round_up) >> k;  // 0 .. 12 by the choice of k
+    w2 |= (static_cast<uint32_t>(0x7777665543210ull >> (4u * q)) & 0xfu) << (8 * b + 4);
+  }
+  m2 = static_cast<int>(w2);
+}
+// the left operand words of four counts: 2.0 [c >= 1] (low nibble) and 2.0 [c >= 2] (high) in m1, 2.0 [c >= 3] and
+// 2.0 [c >= 4] in m2.  With the byte table: c + 0x3c is 60 .. 124, so (c + 0x3c) & 0x43 is c where c < 4 and 0x40 or more
+// where c >= 4; v_perm_b32 reads selector bytes 0 .. 3 from the table and gives 0xff for 13 and above, which the mask
+// turns into "both set"
+__device__ __forceinline__ void c3c_fp4_left(uint32_t w, int& m1, int& m2) {
+#if NSM_C3C_FP4_PERM
+  const uint32_t sel = (w + 0x3c3c3c3cu) & 0x43434343u;
+  m1 = static_cast<int>(__builtin_amdgcn_perm(0u, 0x44440400u, sel) & 0x44444444u);
+  m2 = static_cast<int>(__builtin_amdgcn_perm(0u, 0x04000000u, sel) & 0x44444444u);
+#else
+  m1 = static_cast<int>(((c3c_ge64(w, 1) >> 4)) | c3c_ge64(w, 2));
+  m2 = static_cast<int>(((c3c_ge64(w, 3) >> 4)) | c3c_ge64(w, 4));
+#endif
+}
+// slots 1 and 2: the unscaled form (both scale arguments literal 0)
+__device__ __forceinline__ c3c_v16f c3c_fp4_mfma1(const c3c_v4i& a, const c3c_v4i& b) {
+  const c3c_v8i a8 = {a.x, a.y, a.z, a.w, 0, 0, 0, 0}, b8 = {b.x, b.y, b.z, b.w, 0, 0, 0, 0};  // (FP4: the upper half is not read)
+  const c3c_v16f zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, zero, 4, 4, 0, 0, 0, 0);
+}
+// slots 3 and 4: A scale 1.0, B scale byte t of `scales` (op_sel has to be a literal)
+__device__ __forceinline__ c3c_v16f c3c_fp4_mfma2(const c3c_v4i& a, const c3c_v4i& b, const c3c_v16f& acc, int scales, int t) {
+  const c3c_v8i a8 = {a.x, a.y, a.z, a.w, 0, 0, 0, 0}, b8 = {b.x, b.y, b.z, b.w, 0, 0, 0, 0};
+  switch (t) {
+    case 0: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 4, 4, 0, 0x7f7f7f7f, 0, scales);
+    case 1: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 4, 4, 0, 0x7f7f7f7f, 1, scales);
+    case 2: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 4, 4, 0, 0x7f7f7f7f, 2, scales);
+    default: return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 4, 4, 0, 0x7f7f7f7f, 3, scales);
+  }
 }
 
 #ifndef NSM_C3C_OCC
@@ -200,6 +319,60 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   // tiles: the drain has the loads of eight rows per lane in flight, and 48 registers of fragments alive across it would not
   // leave room for that at four waves per SIMD
   bool valid[NT];
+#if NSM_C3C_FP4
+  // FP4: two fragments a tile, and the tiles' scale bytes (E8M0, 0x7f + k) in one register, tile t in byte t, for op_sel.  A
+  // string's scale is that of ALL its 32 buckets, so a lane reads both halves of its string here (one cache line) and both of
+  // the string's lanes get the same byte; behind a drain the words come from the LDS copy and the scales are still here
+  c3c_v4i bfrag[NT][2];
+  uint32_t bscales = 0u;
+  // the two fragments of tile t from the lane's four words: one branch a tile, and only a string with a scale takes the
+  // byte-by-byte form
+  auto code_tile = [&](int t, const uint4& f, int k) __attribute__((always_inline)) {
+    const uint32_t ws[4] = {f.x, f.y, f.z, f.w};
+    if (k == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        int m1, m2;
+        c3c_fp4_right_k0(ws[q], m1, m2);
+        bfrag[t][0][q] = m1;
+        bfrag[t][1][q] = m2;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        int m1, m2;
+        c3c_fp4_right_scaled(ws[q], k, m1, m2);
+        bfrag[t][0][q] = m1;
+        bfrag[t][1][q] = m2;
+      }
+    }
+  };
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int j = j0 + t * kC3cBlock + col;
+    valid[t] = j < p.n_right;
+    const int jcl = valid[t] ? j : p.n_right - 1;
+    const uint4* fp = reinterpret_cast<const uint4*>(rhist + static_cast<size_t>(jcl) * 8);
+    const uint4 f0 = fp[0], f1 = fp[1];
+    const int k = c3c_fp4_scale(f0, f1);
+    bscales |= static_cast<uint32_t>(0x7f + k) << (8 * t);
+    uint4 f = half ? f1 : f0;
+    if (!valid[t]) f = make_uint4(0u, 0u, 0u, 0u);
+    code_tile(t, f, k);
+  }
+  auto make_bfrag = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const uint32_t* rp = rh_lds + (4 * half) * kRights + t * kC3cBlock + col;
+      const int k = static_cast<int>((bscales >> (8 * t)) & 0xffu) - 0x7f;
+      uint4 f = make_uint4(rp[0], rp[kRights], rp[2 * kRights], rp[3 * kRights]);
+      if (!valid[t]) f = make_uint4(0u, 0u, 0u, 0u);
+      code_tile(t, f, k);
+    }
+  };
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#else
   c3c_v4i bfrag[NT][CAP];
   auto code_b = [&](int t, int q, uint32_t fw) {
     const uint32_t full = c3c_ge64(fw, CAP);  // the last slot: 64 [r >= CAP]
@@ -227,6 +400,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   };
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
+#endif
   const int i0 = blockIdx.y * p.rows_per_chunk;
   const int i1 = min(p.n_left, i0 + p.rows_per_chunk);
   int q_cnt = 0;  // wave-uniform: entries on the stack
@@ -240,7 +414,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   // 16 s + u, lane 4 u + m its rows 8 g + 4 eh + m, g = 0 .. 3 (eh = the entry's lane half of the scan; the C layout of the
   // 32x32 MFMA).  So the four lanes of an entry read 128 contiguous bytes of lhist with each load -- with an entry per lane
   // (16 rows each) every lane of a load was in a cache line of its own, and the pass was bound by that: DESIGN 4.3 step 10.
-  auto drain_pass = [&]() {
+  // (always_inline, here and on drain_full: with the FP4 set-up the compiler stopped inlining the drain at its call sites, and
+  // a lambda that is called keeps what it captures by reference -- the kernel's parameters among it -- in scratch memory.  The
+  // i8 build inlined them by itself: its code, 124 VGPRs and no scratch, is what it was without the attribute)
+  auto drain_pass = [&]() __attribute__((always_inline)) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const int n = min(q_cnt, kWave);
@@ -362,7 +539,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     }
   };
   // the drain between the tiles of the scan: full passes only (the rest waits for more), then the B fragments again
-  auto drain_full = [&]() {
+  auto drain_full = [&]() __attribute__((always_inline)) {
     while (q_cnt >= kWave) drain_pass();
     make_bfrag();
   };
@@ -377,7 +554,9 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     if (a >= b) continue;
     const int la = 64 - c;
     // per tile: the lane's right string can only hit a row of this class if D >= need (kNever: it cannot fit)
-    int nm1[NT];  // 64 need - 1: "D' > nm1" is the fold's test, and the sign of nm1 - D' is a pair's pass bit
+    // i8: 64 need - 1, "D' > nm1" is the fold's test.  FP4: the bits of the f32 need - 1/2 (D is a multiple of 1/2, exact in
+    // f32, and never negative: its bits compare as integers, and those of -1/2, need = 0, are below them all)
+    int nm1[NT];
     bool some = false;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -385,7 +564,11 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       const int nd = valid[t] ? need_of(la, lb) : static_cast<int>(kNever);
       const bool fits = min(la, lb) >= nd;  // exact length filter: LCS <= min(la, lb)
       some = some || fits;
+#if NSM_C3C_FP4
+      nm1[t] = __float_as_int(static_cast<float>(fits ? nd : static_cast<int>(kNever)) - 0.5f);  // (no D reaches kNever: D <= 128)
+#else
       nm1[t] = 64 * (fits ? nd : static_cast<int>(kNever)) - 1;
+#endif
     }
     if (!__any(some)) continue;
 
@@ -395,6 +578,35 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       const uint32_t off = min(static_cast<uint32_t>(i - i0) * 32u + lane_off, last_off);
       return *reinterpret_cast<const uint4*>(chunk + off);
     };
+#if NSM_C3C_FP4
+    // the A fragments of a block: two, of two indicator slots each; the loaded words are no operand
+    typedef c3c_v16f acc_t;
+    c3c_v4i afrag[2];
+    auto make_afrag = [&](const uint4& w) {
+      const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        int m1, m2;
+        c3c_fp4_left(ws[q], m1, m2);
+        afrag[0][q] = m1;
+        afrag[1][q] = m2;
+      }
+    };
+    // the two chained MFMAs of the current block against tile t
+    auto chain = [&](int t, const uint4&) -> acc_t {
+      return c3c_fp4_mfma2(afrag[1], bfrag[t][1], c3c_fp4_mfma1(afrag[0], bfrag[t][0]), static_cast<int>(bscales), t);
+    };
+    // no result is negative, so the f32 bit patterns order as integers do: the fold is the i8 scan's, v_max3_i32 (fmaxf
+    // would canonicalise its first two operands, two instructions more)
+    auto fold = [&](const acc_t& acc) -> int {
+      const c3c_v16i bits = __builtin_bit_cast(c3c_v16i, acc);
+      int top = max(max(bits[0], bits[1]), bits[2]);
+#pragma unroll
+      for (int k = 3; k < 15; k += 2) top = max(max(top, bits[k]), bits[k + 1]);
+      return max(top, bits[15]);
+    };
+#else
+    typedef c3c_v16i acc_t;
     // the A fragments of a block: CAP - 1 indicator slots, two instructions a word; the last slot is the loaded word itself
     c3c_v4i afrag[CAP - 1];
     auto make_afrag = [&](const uint4& w) {
@@ -418,6 +630,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       for (int k = 3; k < 15; k += 2) top = max(max(top, acc[k]), acc[k + 1]);
       return max(top, acc[15]);
     };
+#endif
     // compare and push of tile t of the block at row i: the lanes whose folded result passes push one entry, at most 64 a
     // tile as before (kC3cStack, kC3cDrainAt and their static_assert hold unchanged).  Which of a lane's 16 rows passed is
     // not worked out here: the accumulator is dead after the fold, and the drain's exact test decides every row by itself
@@ -425,6 +638,9 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       const bool ps = top > nm1[t];
       const unsigned long long m = __ballot(ps);
       if (m == 0ull) return;
+#ifdef NSM_C3C_X_COUNTPUSH  // (experiments, with NSM_C3C_X_NOLCS: the launch's count is the number of entries pushed)
+      if (lane == 0) atomicAdd(count, static_cast<unsigned long long>(__popcll(m)));
+#endif
       if (ps) {
         const int slot = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), static_cast<uint32_t>(q_cnt)));
         // (the wave-uniform part first: one v_or at the push instead of a register per tile)
@@ -443,7 +659,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     // the branch and the push of tile t, so that the matrix pipe works under the wave's own epilogue.  Filled here, empty
     // again at the end of the class.
     static_assert(NT % 2 == 0, "tile 0 of the next block takes the accumulator of tile NT: NT must be even (or NSM_C3C_PIPE=0)");
-    c3c_v16i acc[2];
+    acc_t acc[2];
     // one block at row i.  wc: the block's loaded words, its last A slot, which the chains read until the block's last tile
     // is issued; wn: those of the block after, loaded a block ahead.  The load of the block after that goes to wc, so the
     // two register sets change places from block to block and no word is copied.
@@ -469,11 +685,21 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         // a chained MFMA waits for the one before it, so a fold behind the whole chain would start 64 cycles later.  The
         // branch ends the scheduling region: the chain cannot sink below it
         const int top = fold(acc[t & 1]);
+#if NSM_C3C_FP4
+        // (two MFMAs: MFMA, NSM_C3C_FP4_SPLIT VALU, MFMA, the rest of the fold's eight behind it)
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, NSM_C3C_FP4_SPLIT, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 8 - NSM_C3C_FP4_SPLIT, 0);
+        // (the chain's second MFMA would otherwise be moved behind the branch and the push, in front of its own fold)
+        if (t + 1 < NT || (more && !flush)) asm volatile("" : "+v"(acc[(t + 1) & 1]));
+#else
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+#endif
         finish(top, t, i);
       }
       if (flush) {
@@ -509,7 +735,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       make_afrag(w);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const c3c_v16i acc = chain(t, w);
+        const acc_t acc = chain(t, w);
         finish(fold(acc), t, i);
       }
     }
