@@ -27,8 +27,10 @@
  * Conventions
  *   - every pointer marked "device" is HBM memory owned by the caller (the Python host keeps them
  *     as torch tensors); the library keeps no pointer after a call returns and allocates no device memory of
- *     its own that outlives a call (the builders' scratch is stream-ordered and freed inside the call; the one
- *     grid that wants scratch -- nsm_indel_levels_grid -- takes it from the caller as `workspace`);
+ *     its own that outlives a call (the builders' scratch is stream-ordered and freed inside the call; so is that of
+ *     the large two-stage nsm_indel_raw_grid, 64 bytes per left row and a second kernel, neither of which a call
+ *     that is being captured into a graph uses; the one grid that wants scratch beyond the call's own --
+ *     nsm_indel_levels_grid -- takes it from the caller as `workspace`);
  *   - calls are asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream);
  *   - return value: 0 on success, otherwise a hipError_t or one of the NSM_E_* codes below;
  *     nsm_last_error() gives a thread-local message;
@@ -235,6 +237,10 @@ typedef struct nsm_level_items {
                               SAMPLE of the left rows this way and sizes / routes the real call from the count */
 #define NSM_FLAG_ONE_STAGE 1024u /* nsm_indel_raw_grid: the 32-bucket histogram test for every pair even when both tables carry
                                     hist16 (A/B runs, tests) */
+#define NSM_FLAG_PACK 2048u /* nsm_indel_raw_grid, two-stage filter: code the scan's left operand words once per call, in
+                               stream-ordered scratch (chosen by itself where the grid is large enough; this forces it: A/B
+                               runs, tests).  A call that is being captured into a graph never packs */
+#define NSM_FLAG_NO_PACK 4096u /* the same grid: never pack (A/B runs, tests) */
 #define NSM_FLAG_WAVE_WIDE 2u /* nsm_indel_levels_grid: score every step wave-wide (no block-cooperative
                                  parking of the surviving pairs); same hits, kept for A/B runs and tests */
 
@@ -307,7 +313,12 @@ int nsm_jaccard_levels_grid(const nsm_set_table* left, const nsm_set_table* righ
                             int32_t category_mode, uint32_t flags, nsm_hit* hits, uint64_t capacity,
                             unsigned long long* hit_count, void* stream);
 
-/* RAW Indel ratio: ((1 - (la+lb-2*LCS)/(la+lb)) * 100) / 100, 0 when either string is empty. */
+/* RAW Indel ratio: ((1 - (la+lb-2*LCS)/(la+lb)) * 100) / 100, 0 when either string is empty.
+ * With NSM_FLAG_PRUNE and both tables' hist16 (the two-stage filter), a grid that is large enough -- or any with
+ * NSM_FLAG_PACK, none with NSM_FLAG_NO_PACK -- is two kernels: a pre-pass that codes the scan's left operand words into
+ * stream-ordered scratch of 64 bytes per left row (hipMallocAsync / hipFreeAsync on `stream`, freed inside the call), then
+ * the scan.  A call on a stream that is being captured into a graph allocates nothing and is the one scan kernel, and so
+ * is a call whose allocation fails.  The hits are the same either way. */
 int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table* right, double threshold,
                        uint32_t flags, nsm_hit* hits, uint64_t capacity,
                        unsigned long long* hit_count, void* stream);

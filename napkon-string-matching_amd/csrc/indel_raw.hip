@@ -485,10 +485,41 @@ extern "C" int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table
       set_error("nsm_indel_raw_grid: %d left rows per chunk", p.rows_per_chunk);
       return NSM_E_UNSUPPORTED;
     }
-    hipLaunchKernelGGL((indel_raw_coarse_kernel<NSM_C3C_NT, NSM_C3C_CAP>), grid, dim3(kBlock), c3c_lds_bytes(),
-                       static_cast<hipStream_t>(stream), left->codes, left->len, left->len_start, left->orig,
-                       reinterpret_cast<const uint32_t*>(left->hist), right->codes, right->len, right->orig,
-                       reinterpret_cast<const uint32_t*>(right->hist), hits, hit_count, p);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const uint32_t* lh32 = reinterpret_cast<const uint32_t*>(left->hist);
+    const uint32_t* rh32 = reinterpret_cast<const uint32_t*>(right->hist);
+#if NSM_C3C_FP4
+    // The packed path: the left operand words of the scan made once per call (c3c_pack_left_kernel) in stream-ordered
+    // scratch of 64 bytes a left row, freed behind the scan.  Forced by NSM_FLAG_PACK, barred by NSM_FLAG_NO_PACK, else by
+    // size: the pre-pass is a launch plus work per left row, the saving is per pair scanned.  A call that is being captured
+    // allocates nothing and runs the unpacked kernel, and so does a call whose allocation fails.
+    bool pack = !(flags & NSM_FLAG_NO_PACK) &&
+                ((flags & NSM_FLAG_PACK) || c3c_pack_pays(static_cast<long long>(left->n) * static_cast<long long>(right->n)));
+    if (pack) {
+      hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(hs, &capture) != hipSuccess) capture = hipStreamCaptureStatusNone;
+      pack = capture == hipStreamCaptureStatusNone;
+    }
+    void* packed = nullptr;
+    if (pack && hipMallocAsync(&packed, static_cast<size_t>(left->n) * kC3cPackedRow, hs) != hipSuccess) {
+      (void)hipGetLastError();  // (cleared: the call does not fail for want of an optimisation)
+      packed = nullptr;
+    }
+    if (packed) {
+      const long long units = 2ll * left->n;
+      hipLaunchKernelGGL(c3c_pack_left_kernel, dim3(static_cast<unsigned>((units + kBlock - 1) / kBlock)), dim3(kBlock), 0, hs,
+                         lh32, static_cast<c3c_v4i*>(packed), left->n);
+      hipLaunchKernelGGL((indel_raw_coarse_kernel<NSM_C3C_NT, NSM_C3C_CAP, true>), grid, dim3(kBlock), c3c_lds_bytes(), hs,
+                         left->codes, left->len, left->len_start, left->orig, lh32, right->codes, right->len, right->orig,
+                         rh32, hits, hit_count, p, static_cast<const char*>(packed));
+      const int st = hip_status(hipGetLastError(), "indel_raw_coarse_kernel launch (packed)");
+      const int fst = hip_status(hipFreeAsync(packed, hs), "nsm_indel_raw_grid: packed rows");
+      return st ? st : fst;
+    }
+#endif
+    hipLaunchKernelGGL((indel_raw_coarse_kernel<NSM_C3C_NT, NSM_C3C_CAP, false>), grid, dim3(kBlock), c3c_lds_bytes(), hs,
+                       left->codes, left->len, left->len_start, left->orig, lh32, right->codes, right->len, right->orig,
+                       rh32, hits, hit_count, p, static_cast<const char*>(nullptr));
     return hip_status(hipGetLastError(), "indel_raw_coarse_kernel launch");
   }
   // wavefronts along the right side: one per T tiles of 64 strings

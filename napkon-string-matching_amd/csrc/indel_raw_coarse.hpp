@@ -37,6 +37,12 @@
 //           where it is below 4 and 0x40 or more where it is not.  As the selector of v_perm_b32 it reads a four-byte
 //           table for 0 .. 3 and gives 0xff from 13 on, which a mask turns into "both nibbles set".
 //           (NSM_C3C_FP4_PERM=0: two adds, two ands, a shift and an or a word and MFMA; slower)
+//   packed  the left words depend on the row alone, and a row is scanned by every right wave that fits its class: about
+//           800 times a launch of configs[2].  Where the grid is large enough (NSM_C3C_PACK_MIN_PAIRS; NSM_FLAG_PACK /
+//           NSM_FLAG_NO_PACK) c3c_pack_left_kernel makes them ONCE per call, 64 bytes a row in stream-ordered scratch,
+//           and the scan is indel_raw_coarse_kernel<.., true>: a lane loads its two operand fragments, 2 x 16 bytes, and
+//           the chains read the loaded registers (no A fragment is made, none is copied; the two sets still swap from
+//           block to block).  A captured call never packs.  DESIGN 4.3 step 12, profiles/c3_pack_ab.txt.
 //   right   made once by the wave and again behind a drain.  k = 0: byte tables too, v_perm_b32 with the count's low
 //           three bits as the selector and the table of 0 .. 7 or of 8 .. 15 by its bit 3.  k > 0: byte by byte, the
 //           excess through a 13-nibble table in a 64-bit constant.
@@ -241,17 +247,66 @@ __device__ __forceinline__ c3c_v16f c3c_fp4_mfma2(const c3c_v4i& a, const c3c_v4
   }
 }
 
+// --- the packed left rows (NSM_C3C_FP4): c3c_fp4_left of a row depends on the row alone, and a row is scanned by every
+// right wave whose strings fit its length class.  The pre-pass codes every row ONCE per call; the packed scan
+// (indel_raw_coarse_kernel<.., true>) loads the operand words and makes no A fragment.  A packed row is 64 bytes,
+// [half 0: m1 words 16 B | m2 words 16 B][half 1: m1 | m2], rows in table order: lane (col, half) of a block reads the 32
+// contiguous bytes at row * 64 + half * 32.  tests/support/scan_pack.py restates the layout.
+constexpr int kC3cPackedRow = 64;
+#ifndef NSM_C3C_PACK_MIN_PAIRS
+// the smallest grid (left rows x right rows) that packs by itself.  Measured, forced pack against the parent's kernel
+// (profiles/c3_pack_ab.txt): 8k x 8k +0.009 ms, 20k x 20k +0.008, 50k x 50k +0.020, 100k x 100k -0.011, 200k x 200k -0.147.
+// The pre-pass, the allocation and the doubled bytes at the start of every length class cost more than the coding saves
+// where a wave scans a short chunk; the floor is the smallest measured grid at which every packed run beat every parent run
+#define NSM_C3C_PACK_MIN_PAIRS 10000000000ll
+#endif
+static inline bool c3c_pack_pays(long long pairs) { return pairs >= static_cast<long long>(NSM_C3C_PACK_MIN_PAIRS); }
+struct c3c_packed_rows {
+  c3c_v4i m1, m2;
+};
+template <bool PACKED>
+struct c3c_rows {
+  typedef uint4 type;  // the lane's 16 histogram bytes
+};
+template <>
+struct c3c_rows<true> {
+  typedef c3c_packed_rows type;  // the lane's two A fragments
+};
+
+// one thread per (row, half) of the whole table: 16 histogram bytes in, 32 operand bytes out
+__global__ __launch_bounds__(kBlock) void c3c_pack_left_kernel(const uint32_t* __restrict__ lhist, c3c_v4i* __restrict__ packed,
+                                                               int n_left) {
+  const int u = blockIdx.x * kBlock + threadIdx.x;  // 2 row + half
+  if (u >= 2 * n_left) return;
+  const uint4 w = reinterpret_cast<const uint4*>(lhist)[u];
+  const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+  c3c_v4i m1, m2;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    int a1, a2;
+    c3c_fp4_left(ws[q], a1, a2);
+    m1[q] = a1;
+    m2[q] = a2;
+  }
+  packed[2 * static_cast<size_t>(u)] = m1;
+  packed[2 * static_cast<size_t>(u) + 1] = m2;
+}
+
 #ifndef NSM_C3C_OCC
 // two waves per SIMD or more: a budget of 256 registers, with which the compiler keeps the accumulators in VGPRs (beyond it
 // they go to AGPRs and every result costs a v_accvgpr_read before the fold)
 #define NSM_C3C_OCC __attribute__((amdgpu_waves_per_eu(2)))
 #endif
-template <int NT, int CAP>
+// PACKED: the scan reads its A fragments from `lpacked` (c3c_pack_left_kernel's rows of the whole left table); the drain
+// reads the raw lhist rows either way.  Without it `lpacked` is not read.
+template <int NT, int CAP, bool PACKED>
 __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const uint8_t* __restrict__ lcodes, const int32_t* __restrict__ llen, const int32_t* __restrict__ lstart,
     const int32_t* __restrict__ lorig, const uint32_t* __restrict__ lhist, const uint8_t* __restrict__ rcodes,
     const int32_t* __restrict__ rlen, const int32_t* __restrict__ rorig, const uint32_t* __restrict__ rhist,
-    nsm_hit* __restrict__ hits, unsigned long long* __restrict__ count, const IndelRawParams p) {
+    nsm_hit* __restrict__ hits, unsigned long long* __restrict__ count, const IndelRawParams p,
+    const char* __restrict__ lpacked) {
+  static_assert(!PACKED || NSM_C3C_FP4, "only the FP4 scan has packed left rows");
   constexpr int kRights = NT * kC3cBlock;
   // the stack's invariant: a drain check leaves at most kC3cDrainAt entries (above that the drain runs, down to fewer than 64;
   // in the pipelined scan after one more tile's pushes) and at most NT x 64 are pushed before the next check, so no slot past
@@ -409,6 +464,8 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
 
   // a left row's bytes as a 32-bit offset from the chunk's first row (a chunk has at most 2^15 rows of 32 bytes)
   const char* chunk = reinterpret_cast<const char*>(lhist + static_cast<size_t>(i0) * 8);
+  // ... and a packed row's from the chunk's first packed row (the scan's; the drain reads `chunk`)
+  const char* pchunk = PACKED ? lpacked + static_cast<size_t>(i0) * kC3cPackedRow : nullptr;
 
   // pop up to 64 entries and test their rows, a ROW per lane: in quarter s of the pass the four lanes 4 u .. 4 u + 3 have entry
   // 16 s + u, lane 4 u + m its rows 8 g + 4 eh + m, g = 0 .. 3 (eh = the entry's lane half of the scan; the C layout of the
@@ -573,28 +630,43 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     if (!__any(some)) continue;
 
     // the lane's 16 bytes of row i + col (the class's last row again past its end)
-    const uint32_t last_off = static_cast<uint32_t>(b - 1 - i0) * 32u + static_cast<uint32_t>(half * 16);
-    auto load_rows = [&](int i) -> uint4 {
-      const uint32_t off = min(static_cast<uint32_t>(i - i0) * 32u + lane_off, last_off);
-      return *reinterpret_cast<const uint4*>(chunk + off);
+    // PACKED: its 32 bytes of packed row i + col, the same clamp in the packed rows' stride (a chunk has at most 2^15 rows
+    // of 64 bytes: the offset stays a 32-bit value from the chunk's first packed row)
+    typedef typename c3c_rows<PACKED>::type rows_t;
+    const uint32_t last_off = static_cast<uint32_t>(b - 1 - i0) * (PACKED ? 64u : 32u) + static_cast<uint32_t>(half * (PACKED ? 32 : 16));
+    auto load_rows = [&](int i) -> rows_t {
+      if constexpr (PACKED) {
+        const uint32_t off = min(static_cast<uint32_t>(i - i0) * 64u + 2u * lane_off, last_off);
+        const c3c_v4i* pp = reinterpret_cast<const c3c_v4i*>(pchunk + off);
+        return c3c_packed_rows{pp[0], pp[1]};
+      } else {
+        const uint32_t off = min(static_cast<uint32_t>(i - i0) * 32u + lane_off, last_off);
+        return *reinterpret_cast<const uint4*>(chunk + off);
+      }
     };
 #if NSM_C3C_FP4
-    // the A fragments of a block: two, of two indicator slots each; the loaded words are no operand
+    // the A fragments of a block: two, of two indicator slots each; the loaded words are no operand.  PACKED: the loaded
+    // words ARE the two fragments, nothing is made and the chains read the loaded set
     typedef c3c_v16f acc_t;
     c3c_v4i afrag[2];
-    auto make_afrag = [&](const uint4& w) {
-      const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+    auto make_afrag = [&](const rows_t& w) {
+      if constexpr (!PACKED) {
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        int m1, m2;
-        c3c_fp4_left(ws[q], m1, m2);
-        afrag[0][q] = m1;
-        afrag[1][q] = m2;
+        for (int q = 0; q < 4; ++q) {
+          int m1, m2;
+          c3c_fp4_left(ws[q], m1, m2);
+          afrag[0][q] = m1;
+          afrag[1][q] = m2;
+        }
       }
     };
     // the two chained MFMAs of the current block against tile t
-    auto chain = [&](int t, const uint4&) -> acc_t {
-      return c3c_fp4_mfma2(afrag[1], bfrag[t][1], c3c_fp4_mfma1(afrag[0], bfrag[t][0]), static_cast<int>(bscales), t);
+    auto chain = [&](int t, const rows_t& w) -> acc_t {
+      if constexpr (PACKED)
+        return c3c_fp4_mfma2(w.m2, bfrag[t][1], c3c_fp4_mfma1(w.m1, bfrag[t][0]), static_cast<int>(bscales), t);
+      else
+        return c3c_fp4_mfma2(afrag[1], bfrag[t][1], c3c_fp4_mfma1(afrag[0], bfrag[t][0]), static_cast<int>(bscales), t);
     };
     // no result is negative, so the f32 bit patterns order as integers do: the fold is the i8 scan's, v_max3_i32 (fmaxf
     // would canonicalise its first two operands, two instructions more)
@@ -663,7 +735,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     // one block at row i.  wc: the block's loaded words, its last A slot, which the chains read until the block's last tile
     // is issued; wn: those of the block after, loaded a block ahead.  The load of the block after that goes to wc, so the
     // two register sets change places from block to block and no word is copied.
-    auto block = [&](int i, uint4& wc, uint4& wn) __attribute__((always_inline)) {
+    auto block = [&](int i, rows_t& wc, rows_t& wn) __attribute__((always_inline)) {
       const bool more = i + kC3cBlock < b;
       // the drain check sits in front of a block's LAST tile: at most NT tiles, NT x 64 entries, between two checks.  Where
       // the drain has to run, the pipeline is emptied first (one more tile's entries: kC3cStack's extra 64 slots), so that
@@ -677,6 +749,8 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
           flush = q_cnt > kC3cDrainAt;
           if (more && !flush) {
             make_afrag(wn);
+            // (PACKED: the wait for wn, loaded a block ago, stands HERE and not behind the next load, which it would wait for too)
+            if constexpr (PACKED) asm volatile("" : "+v"(wn.m1), "+v"(wn.m2));
             if (i + 2 * kC3cBlock < b) wc = load_rows(i + 2 * kC3cBlock);
             acc[0] = chain(0, wn);
           }
@@ -713,10 +787,17 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     };
     if (q_cnt > kC3cDrainAt)  // (a class of one block has no other check in front of its first NT - 1 tiles)
       drain_full();
-    uint4 w0 = load_rows(a);
+    rows_t w0 = load_rows(a);
     make_afrag(w0);
-    uint4 w1 = w0;  // (once per class, outside the block loop: a class of one block never loads the second set)
-    if (a + kC3cBlock < b) w1 = load_rows(a + kC3cBlock);
+    // (once per class, outside the block loop: a class of one block never loads the second set.  PACKED: it does, the
+    // class's last row by load_rows' clamp -- nothing waits for the first set before the second load is under way)
+    rows_t w1;
+    if constexpr (PACKED) {
+      w1 = load_rows(a + kC3cBlock);
+    } else {
+      w1 = w0;
+      if (a + kC3cBlock < b) w1 = load_rows(a + kC3cBlock);
+    }
     acc[0] = chain(0, w0);
     for (int i = a;;) {
       block(i, w0, w1);
@@ -725,9 +806,9 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       if ((i += kC3cBlock) >= b) break;
     }
 #else
-    uint4 w_next = load_rows(a);
+    rows_t w_next = load_rows(a);
     for (int i = a; i < b; i += kC3cBlock) {
-      const uint4 w = w_next;
+      const rows_t w = w_next;
       if (i + kC3cBlock < b) w_next = load_rows(i + kC3cBlock);
       // a block pushes up to NT x 64 entries
       if (q_cnt > kC3cDrainAt)
