@@ -43,6 +43,30 @@
 //           and the scan is indel_raw_coarse_kernel<.., true>: a lane loads its two operand fragments, 2 x 16 bytes, and
 //           the chains read the loaded registers (no A fragment is made, none is copied; the two sets still swap from
 //           block to block).  A captured call never packs.  DESIGN 4.3 step 12, profiles/c3_pack_ab.txt.
+//   or fold the packed scan (NSM_C3C_ORFOLD) puts TWO tiles on an accumulator.  A lane's 16 results of a tile are integers of at
+//           most 128, so tiles 2 p ("hi") and 2 p + 1 ("lo") of the wave share a register as two 9-bit fixed-point fields on
+//           a bias that carries the threshold:
+//             acc = BIAS + 2^9 (A.m1 B[hi].m1 + 2^k_hi A.m2 B[hi].m2) + (A.m1 B[lo].m1 + 2^k_lo A.m2 B[lo].m2)
+//             BIAS = 2^23 + (256 - need_hi) 2^9 + (256 - need_lo)
+//           FOUR chained MFMAs, all in the scaled form: the first reads BIAS as srcC (a tuple of 16 equal registers, made
+//           once per run of blocks); the B scale bytes are 0x7f + 9 and 0x7f + 9 + k for an even tile, 0x7f and 0x7f + k for
+//           an odd one, in two registers (slots 1 and 2: bytes 0x88, 0x7f in turn; slots 3 and 4: those + k).  Every term
+//           is an integer and the sum is below 2^24, so every partial sum is exact and the result, in [2^23, 2^24), has the
+//           integer as its mantissa bits: field lo = D_lo + 256 - need_lo in bits 0 .. 8, field hi in bits 9 .. 17.  A field
+//           is at most 128 + 256 = 384 < 512: no carry.  Bit 8 of a field is [D >= need]: need = kNever gives at most 129,
+//           never flagged; need = 0 always.  The fold is the OR of the 16 registers under the mask 0x20100, seven
+//           v_or3_b32 and a v_bitop3_b32, and one v_cmp_ne_u32 and one branch a tile PAIR: 9 VALU for 2048 pairs where the
+//           max fold takes 18.  Where the branch is taken, a ballot per flag pushes for tile 2 p (bit 17) and 2 p + 1
+//           (bit 8), a column that does not exist masked out, in the same entry format.
+//           ONE bias serves the wave's tile pairs, so need_hi is the SMALLEST need of the lane's even tiles and need_lo
+//           that of its odd ones (kNever where a column fits no row of the class or does not exist).  A wave whose 128 right
+//           strings straddle a length boundary pushes a few entries too many; the drain tests every pair by its own need.
+//           tools/mfma_fp4_probe checks the chain bit for bit (k = 0 .. 3) and times it: no slower than two chains of two.
+//           128 VGPRs at four waves (amdgpu_waves_per_eu(4): under the budget of two waves the compiler keeps hoisted
+//           constants in 133), no scratch, no AGPRs; for that nothing lives across a drain (below), and what a class needs
+//           once (the column, the half) is worked out again from the lane.  The unpacked scan keeps the max fold: the grids
+//           that do not pack scan short runs of blocks, where the bias tuple and the longer chain cost more than the fold
+//           saves.  tests/support/scan_orfold.py restates it.  DESIGN 4.3 step 13, profiles/c3_orfold_ab.txt.
 //   right   made once by the wave and again behind a drain.  k = 0: byte tables too, v_perm_b32 with the count's low
 //           three bits as the selector and the table of 0 .. 7 or of 8 .. 15 by its bit 3.  k > 0: byte by byte, the
 //           excess through a 13-nibble table in a 64-bit constant.
@@ -84,12 +108,16 @@
 //           MFMA waits for the one before it, and a wave issues in order).  FP4: MFMA, four of the fold's eight, MFMA,
 //           four (NSM_C3C_FP4_SPLIT); an empty asm that names the new accumulator keeps the second MFMA in front of the
 //           branch.  So the matrix pipe works under the wave's own epilogue and not only under those of the SIMD's other
-//           waves.  The pipeline is filled at the start of a length class and is empty at its end, and it is emptied in
-//           front of a drain (no accumulator lives across one); NSM_C3C_PIPE=0 is the order of before, chain, fold,
-//           chain, fold on one accumulator;
+//           waves.  OR fold: the units are tile pairs, MFMA, two of the fold's eight, four times (NSM_C3C_OR_SPLIT), and the
+//           first chain of the block after is issued without a branch around it (a pair is every other unit; behind a
+//           branch no fold stands between its MFMAs), its result dropped where that block does not run.  The pipeline is
+//           filled at the start of a run of blocks -- a length class, or what is left of it behind a drain -- and is empty
+//           at its end: the block that decides on a drain ends the run, and the next run drains first and loads its words
+//           again, so no accumulator, no word, no bias lives across a drain; NSM_C3C_PIPE=0 is the order of before, chain,
+//           fold, chain, fold on one accumulator;
 //   stack   lanes whose folded result passes push (block's first row, la, tile, lane, rows of the block that exist) on the
 //           wave's LDS stack, 8 bytes: one ballot per tile of 1024 pairs and one ds_write where it is not empty, at most 64
-//           entries a tile;
+//           entries a tile (OR fold: 128 a tile pair: the stack has room for NT x 64 between two checks and one more pair);
 //   drain   whenever more than 128 entries are on the stack, checked every NT tiles (in front of a block's last tile, whose
 //           entries are still pushed before the drain runs, and at the start of a class), 64 entries at a time (64 of 64
 //           lanes busy), an entry handled ONCE for all its rows (nothing goes back on the stack).  A pass has four quarters
@@ -133,8 +161,19 @@ namespace nsm {
 #ifndef NSM_C3C_NT
 #define NSM_C3C_NT 4  // right tiles of 32 strings per wave
 #endif
+#ifndef NSM_C3C_ORFOLD
+// 1: the PACKED FP4 scan puts two tiles on an accumulator as fixed-point fields on a bias that holds the lane's needs, and
+// folds with OR on the fields' flag bits (NT even); 0, and the unpacked scan always: a tile per accumulator, max fold and a
+// compare with the tile's need (the i8 scan's)
+#define NSM_C3C_ORFOLD (NSM_C3C_FP4 && NSM_C3C_NT % 2 == 0)
+#endif
 #ifndef NSM_C3C_PIPE
-#define NSM_C3C_PIPE (NSM_C3C_NT % 2 == 0)  // 1: two accumulators, a tile's MFMAs are issued around the fold of the tile before
+// 1: two accumulators, a tile's (OR fold: a tile pair's) MFMAs are issued around the fold of the one before; the number of
+// tiles (tile pairs) of a wave must be even
+#define NSM_C3C_PIPE (NSM_C3C_NT % (NSM_C3C_ORFOLD ? 4 : 2) == 0)
+#endif
+#ifndef NSM_C3C_OR_SPLIT
+#define NSM_C3C_OR_SPLIT 2  // OR fold: instructions of a tile pair's fold behind each of the first three MFMAs of the next chain
 #endif
 #ifndef NSM_C3C_LCS_PREFETCH
 #define NSM_C3C_LCS_PREFETCH 1  // 1: the drain requests the next surviving pair's rows before the current pair's LCS chain
@@ -145,8 +184,10 @@ namespace nsm {
 constexpr int kC3cBlock = 32;                // left rows per block = right strings per tile: the M and N of the MFMA
 constexpr int kC3cRights = NSM_C3C_NT * kC3cBlock;  // right strings per wave
 // entries per wave; drained when more than kC3cDrainAt are on it.  NT x 64 pushes between two drain checks, and the pipelined scan
-// pushes one more tile's before the drain it has decided on runs (the pipeline is emptied first)
-constexpr int kC3cStack = (NSM_C3C_NT + 2 + (NSM_C3C_PIPE ? 1 : 0)) * kWave;
+// pushes one more tile's before the drain it has decided on runs (the pipeline is emptied first); with the OR fold that is a
+// tile PAIR's, 128 entries
+constexpr int kC3cPipeExtra = NSM_C3C_PIPE ? (NSM_C3C_ORFOLD ? 2 : 1) : 0;
+constexpr int kC3cStack = (NSM_C3C_NT + 2 + kC3cPipeExtra) * kWave;
 constexpr int kC3cDrainAt = 2 * kWave;
 // a stack entry: one lane of the scan whose folded result passed, that is its 16 left rows (k & 3) + 8 (k >> 2) + 4 (lane >> 5)
 // of the block, k = 0 .. 15, against right string tile * 32 + (lane & 31) of the wave.  Low word = the number of rows of the block
@@ -295,7 +336,9 @@ __global__ __launch_bounds__(kBlock) void c3c_pack_left_kernel(const uint32_t* _
 #ifndef NSM_C3C_OCC
 // two waves per SIMD or more: a budget of 256 registers, with which the compiler keeps the accumulators in VGPRs (beyond it
 // they go to AGPRs and every result costs a v_accvgpr_read before the fold)
-#define NSM_C3C_OCC __attribute__((amdgpu_waves_per_eu(2)))
+// OR fold: FOUR.  The bias tuple brings the scan to 133 registers under the budget of two waves, which the compiler fills
+// with hoisted constants and addresses; told that it has 128, it makes them where they are used: 128, no scratch, no AGPRs
+#define NSM_C3C_OCC __attribute__((amdgpu_waves_per_eu((NSM_C3C_ORFOLD && PACKED) ? 4 : 2)))
 #endif
 // PACKED: the scan reads its A fragments from `lpacked` (c3c_pack_left_kernel's rows of the whole left table); the drain
 // reads the raw lhist rows either way.  Without it `lpacked` is not read.
@@ -311,8 +354,13 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   // the stack's invariant: a drain check leaves at most kC3cDrainAt entries (above that the drain runs, down to fewer than 64;
   // in the pipelined scan after one more tile's pushes) and at most NT x 64 are pushed before the next check, so no slot past
   // kC3cStack is written; the drain's trigger level must itself be at least 64, so that it only ever runs full passes
-  static_assert(kC3cDrainAt >= kWave && kC3cDrainAt + (NT + (NSM_C3C_PIPE ? 1 : 0)) * kWave <= kC3cStack,
+  static_assert(kC3cDrainAt >= kWave && kC3cDrainAt + (NT + kC3cPipeExtra) * kWave <= kC3cStack,
                 "the drain is triggered above kC3cDrainAt entries and runs full passes");
+  // the OR fold is the packed scan's: the grids that do not pack (c3c_pack_pays) are short runs of blocks, where the bias
+  // tuple of every class and the longer chain cost more than the fold saves
+  constexpr bool kOrFold = NSM_C3C_ORFOLD && PACKED;
+  constexpr int kFlagHi = 1 << 17, kFlagLo = 1 << 8;  // bit 8 of the upper and of the lower field
+  static_assert(!kOrFold || (NSM_C3C_FP4 && NT % 2 == 0), "the OR fold puts tiles 2 p and 2 p + 1 of the FP4 scan on one accumulator");
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_mem[];
   unsigned long long* s_stack = s_mem;
   uint32_t* s_rh = reinterpret_cast<uint32_t*>(s_stack + kWavesPerBlock * kC3cStack);
@@ -327,6 +375,13 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   const int half = lane >> 5;              // ... and its 16 buckets of the 32
   const int j0 = (blockIdx.x * kWavesPerBlock + wave) * kRights;
   if (j0 >= p.n_right) return;
+  // the lane again, opaque: what is used once per length class or behind a drain (the column, the half) is worked out from it
+  // THERE, one instruction, and holds no register across the scan, which has none to spare at four waves per SIMD
+  auto lane_again = [&]() -> int {
+    int l = lane;
+    asm volatile("" : "+v"(l));
+    return l;
+  };
 #if NSM_C3C_EARLY_OUT
   // A wave whose right strings fit no length class of its chunk has nothing to scan: it leaves before it builds its LDS copy
   // and its B fragments.  For a right string of lb > 0 units the left lengths that fit, min(la, lb) >= lcsmin[la + lb], are an
@@ -378,8 +433,17 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   // FP4: two fragments a tile, and the tiles' scale bytes (E8M0, 0x7f + k) in one register, tile t in byte t, for op_sel.  A
   // string's scale is that of ALL its 32 buckets, so a lane reads both halves of its string here (one cache line) and both of
   // the string's lanes get the same byte; behind a drain the words come from the LDS copy and the scales are still here
+  // OR fold: an even tile's results go to the accumulator's upper field, so its scale bytes are 0x7f + 9 and 0x7f + 9 + k.
+  // The slots 1 and 2 then need a scale too, the same in every lane: bscales1, bytes 0x88 and 0x7f in turn
   c3c_v4i bfrag[NT][2];
   uint32_t bscales = 0u;
+  auto scale_base = [](int t) -> uint32_t { return (kOrFold && t % 2 == 0) ? 0x7fu + 9u : 0x7fu; };
+  uint32_t bscales1 = 0u;
+  if constexpr (kOrFold) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) bscales1 |= scale_base(t) << (8 * t);
+    asm volatile("" : "+v"(bscales1));  // (one register for the whole scan: not a v_mov in front of every MFMA)
+  }
   // the two fragments of tile t from the lane's four words: one branch a tile, and only a string with a scale takes the
   // byte-by-byte form
   auto code_tile = [&](int t, const uint4& f, int k) __attribute__((always_inline)) {
@@ -410,16 +474,18 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     const uint4* fp = reinterpret_cast<const uint4*>(rhist + static_cast<size_t>(jcl) * 8);
     const uint4 f0 = fp[0], f1 = fp[1];
     const int k = c3c_fp4_scale(f0, f1);
-    bscales |= static_cast<uint32_t>(0x7f + k) << (8 * t);
+    bscales |= (scale_base(t) + static_cast<uint32_t>(k)) << (8 * t);
     uint4 f = half ? f1 : f0;
     if (!valid[t]) f = make_uint4(0u, 0u, 0u, 0u);
     code_tile(t, f, k);
   }
   auto make_bfrag = [&]() __attribute__((always_inline)) {
+    const int l = lane_again();
+    const uint32_t* rp0 = rh_lds + (4 * (l >> 5)) * kRights + (l & (kC3cBlock - 1));
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const uint32_t* rp = rh_lds + (4 * half) * kRights + t * kC3cBlock + col;
-      const int k = static_cast<int>((bscales >> (8 * t)) & 0xffu) - 0x7f;
+      const uint32_t* rp = rp0 + t * kC3cBlock;
+      const int k = static_cast<int>(((bscales >> (8 * t)) & 0xffu) - scale_base(t));
       uint4 f = make_uint4(rp[0], rp[kRights], rp[2 * kRights], rp[3 * kRights]);
       if (!valid[t]) f = make_uint4(0u, 0u, 0u, 0u);
       code_tile(t, f, k);
@@ -613,27 +679,52 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     // per tile: the lane's right string can only hit a row of this class if D >= need (kNever: it cannot fit)
     // i8: 64 need - 1, "D' > nm1" is the fold's test.  FP4: the bits of the f32 need - 1/2 (D is a multiple of 1/2, exact in
     // f32, and never negative: its bits compare as integers, and those of -1/2, need = 0, are below them all)
+    // OR fold: ONE bias for all the wave's tile pairs, so the lane's need of the upper field is the SMALLEST of its even
+    // tiles' and that of the lower field the smallest of its odd tiles'.  A lane whose columns differ in need (the wave's 128
+    // right strings straddle a length boundary) pushes a few entries too many, and the drain tests every pair by its own need
+    int need2[2] = {static_cast<int>(kNever), static_cast<int>(kNever)};
     int nm1[NT];
     bool some = false;
+    const int l_c = lane_again();
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int lb = rl_lds[t * kC3cBlock + col];  // (from the wave's copy: no register holds it across the classes)
+      const int lb = rl_lds[t * kC3cBlock + (l_c & (kC3cBlock - 1))];  // (from the wave's copy: no register holds it across the classes)
       const int nd = valid[t] ? need_of(la, lb) : static_cast<int>(kNever);
       const bool fits = min(la, lb) >= nd;  // exact length filter: LCS <= min(la, lb)
       some = some || fits;
 #if NSM_C3C_FP4
-      nm1[t] = __float_as_int(static_cast<float>(fits ? nd : static_cast<int>(kNever)) - 0.5f);  // (no D reaches kNever: D <= 128)
+      if constexpr (kOrFold)
+        need2[t & 1] = min(need2[t & 1], fits ? nd : static_cast<int>(kNever));  // (fits: nd <= min(la, lb) <= 64)
+      else
+        nm1[t] = __float_as_int(static_cast<float>(fits ? nd : static_cast<int>(kNever)) - 0.5f);  // (no D reaches kNever: D <= 128)
 #else
       nm1[t] = 64 * (fits ? nd : static_cast<int>(kNever)) - 1;
 #endif
     }
     if (!__any(some)) continue;
+    // OR fold: the C operand of a chain's first MFMA: 2^23 + (256 - need_hi) 2^9 + (256 - need_lo) in all 16 registers.  The chain
+    // adds 2^9 D_hi + D_lo, D <= 128: an integer in [2^23, 2^24), exact in f32, whose mantissa bits ARE the integer.  Field
+    // D + 256 - need <= 384 < 512 does not carry, and its bit 8 is set exactly where D >= need (need = kNever: the field
+    // is at most 129; need = 0: always set)
+    // (made here and again behind a drain between the tiles, like the B fragments: the drain needs the registers)
+    c3c_v16f bias;
+    const float bias1 = __int_as_float(0x4b000000 | ((256 - need2[0]) << 9) | (256 - need2[1]));
+    auto make_bias = [&]() {
+      // (16 registers that stay across the blocks: srcC is a tuple.  The moves are written out: a splat that the compiler
+      // sees is made once per class in 16 registers MORE and copied from there behind every drain)
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        float x;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(x) : "v"(bias1));
+        bias[k] = x;
+      }
+    };
 
     // the lane's 16 bytes of row i + col (the class's last row again past its end)
     // PACKED: its 32 bytes of packed row i + col, the same clamp in the packed rows' stride (a chunk has at most 2^15 rows
     // of 64 bytes: the offset stays a 32-bit value from the chunk's first packed row)
     typedef typename c3c_rows<PACKED>::type rows_t;
-    const uint32_t last_off = static_cast<uint32_t>(b - 1 - i0) * (PACKED ? 64u : 32u) + static_cast<uint32_t>(half * (PACKED ? 32 : 16));
+    const uint32_t last_off = static_cast<uint32_t>(b - 1 - i0) * (PACKED ? 64u : 32u) + static_cast<uint32_t>((l_c >> 5) * (PACKED ? 32 : 16));
     auto load_rows = [&](int i) -> rows_t {
       if constexpr (PACKED) {
         const uint32_t off = min(static_cast<uint32_t>(i - i0) * 64u + 2u * lane_off, last_off);
@@ -661,24 +752,42 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         }
       }
     };
-    // the two chained MFMAs of the current block against tile t
-    auto chain = [&](int t, const rows_t& w) -> acc_t {
-      if constexpr (PACKED)
-        return c3c_fp4_mfma2(w.m2, bfrag[t][1], c3c_fp4_mfma1(w.m1, bfrag[t][0]), static_cast<int>(bscales), t);
-      else
-        return c3c_fp4_mfma2(afrag[1], bfrag[t][1], c3c_fp4_mfma1(afrag[0], bfrag[t][0]), static_cast<int>(bscales), t);
+    // a unit of the scan is a tile: its two chained MFMAs of the current block, the first in the unscaled form.  OR fold: a
+    // tile PAIR, four chained MFMAs against tiles 2 u (scaled by 2^9: the upper field) and 2 u + 1 on the bias, all in the
+    // scaled form (the unscaled one cannot carry 2^9)
+    constexpr int NU = kOrFold ? NT / 2 : NT;
+    auto chain = [&](int u, const rows_t& w) -> acc_t {
+      if constexpr (kOrFold) {
+        acc_t acc = c3c_fp4_mfma2(w.m1, bfrag[2 * u][0], bias, static_cast<int>(bscales1), 2 * u);
+        acc = c3c_fp4_mfma2(w.m2, bfrag[2 * u][1], acc, static_cast<int>(bscales), 2 * u);
+        acc = c3c_fp4_mfma2(w.m1, bfrag[2 * u + 1][0], acc, static_cast<int>(bscales1), 2 * u + 1);
+        return c3c_fp4_mfma2(w.m2, bfrag[2 * u + 1][1], acc, static_cast<int>(bscales), 2 * u + 1);
+      } else if constexpr (PACKED) {
+        return c3c_fp4_mfma2(w.m2, bfrag[u][1], c3c_fp4_mfma1(w.m1, bfrag[u][0]), static_cast<int>(bscales), u);
+      } else {
+        return c3c_fp4_mfma2(afrag[1], bfrag[u][1], c3c_fp4_mfma1(afrag[0], bfrag[u][0]), static_cast<int>(bscales), u);
+      }
     };
     // no result is negative, so the f32 bit patterns order as integers do: the fold is the i8 scan's, v_max3_i32 (fmaxf
-    // would canonicalise its first two operands, two instructions more)
+    // would canonicalise its first two operands, two instructions more).  OR fold: "some row passes" is a flag bit: OR the 16
+    // registers (seven v_or3_b32) and mask the two flags (v_bitop3_b32)
     auto fold = [&](const acc_t& acc) -> int {
       const c3c_v16i bits = __builtin_bit_cast(c3c_v16i, acc);
-      int top = max(max(bits[0], bits[1]), bits[2]);
+      if constexpr (kOrFold) {
+        int top = bits[0] | bits[1] | bits[2];
 #pragma unroll
-      for (int k = 3; k < 15; k += 2) top = max(max(top, bits[k]), bits[k + 1]);
-      return max(top, bits[15]);
+        for (int k = 3; k < 15; k += 2) top = top | bits[k] | bits[k + 1];
+        return (top | bits[15]) & (kFlagHi | kFlagLo);
+      } else {
+        int top = max(max(bits[0], bits[1]), bits[2]);
+#pragma unroll
+        for (int k = 3; k < 15; k += 2) top = max(max(top, bits[k]), bits[k + 1]);
+        return max(top, bits[15]);
+      }
     };
 #else
     typedef c3c_v16i acc_t;
+    constexpr int NU = NT;
     // the A fragments of a block: CAP - 1 indicator slots, two instructions a word; the last slot is the loaded word itself
     c3c_v4i afrag[CAP - 1];
     auto make_afrag = [&](const uint4& w) {
@@ -704,11 +813,9 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     };
 #endif
     // compare and push of tile t of the block at row i: the lanes whose folded result passes push one entry, at most 64 a
-    // tile as before (kC3cStack, kC3cDrainAt and their static_assert hold unchanged).  Which of a lane's 16 rows passed is
-    // not worked out here: the accumulator is dead after the fold, and the drain's exact test decides every row by itself
-    auto finish = [&](int top, int t, int i) {
-      const bool ps = top > nm1[t];
-      const unsigned long long m = __ballot(ps);
+    // tile.  Which of a lane's 16 rows passed is not worked out here: the accumulator is dead after the fold, and the drain's
+    // exact test decides every row by itself
+    auto push = [&](bool ps, unsigned long long m, int t, int i) {
       if (m == 0ull) return;
 #ifdef NSM_C3C_X_COUNTPUSH  // (experiments, with NSM_C3C_X_NOLCS: the launch's count is the number of entries pushed)
       if (lane == 0) atomicAdd(count, static_cast<unsigned long long>(__popcll(m)));
@@ -725,29 +832,49 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       }
       q_cnt += __popcll(m);
     };
+    // OR fold: one branch a tile pair; where it is taken a ballot per flag, bit 17 for tile 2 u and bit 8 for tile 2 u + 1, in
+    // the same entry format -- up to 128 entries a pair
+    auto finish = [&](int top, int u, int i) {
+      if constexpr (kOrFold) {
+        if (__ballot(top != 0) == 0ull) return;
+        // (a column that does not exist has the flag of the lane's other tile of its parity: with need = 0 that one passes
+        // everything, and the drain would take the missing string for an empty one)
+        const bool hi = (top & kFlagHi) != 0 && valid[2 * u], lo = (top & kFlagLo) != 0 && valid[2 * u + 1];
+        push(hi, __ballot(hi), 2 * u, i);
+        push(lo, __ballot(lo), 2 * u + 1, i);
+      } else {
+        const bool ps = top > nm1[u];
+        push(ps, __ballot(ps), u, i);
+      }
+    };
 #if NSM_C3C_PIPE
     // software pipeline over the tiles and the blocks of the class: acc[t & 1] holds tile t, and the chain of the tile after
     // (tile 0 of the next block after a block's last, with that block's A fragments) is issued around the fold and before
     // the branch and the push of tile t, so that the matrix pipe works under the wave's own epilogue.  Filled here, empty
     // again at the end of the class.
-    static_assert(NT % 2 == 0, "tile 0 of the next block takes the accumulator of tile NT: NT must be even (or NSM_C3C_PIPE=0)");
+    // (units: tiles, or the tile pairs of the OR fold)
+    static_assert(NU % 2 == 0, "unit 0 of the next block takes the accumulator of unit NU: NU must be even (or NSM_C3C_PIPE=0)");
     acc_t acc[2];
     // one block at row i.  wc: the block's loaded words, its last A slot, which the chains read until the block's last tile
     // is issued; wn: those of the block after, loaded a block ahead.  The load of the block after that goes to wc, so the
     // two register sets change places from block to block and no word is copied.
-    auto block = [&](int i, rows_t& wc, rows_t& wn) __attribute__((always_inline)) {
+    auto block = [&](int i, rows_t& wc, rows_t& wn) __attribute__((always_inline)) -> bool {
       const bool more = i + kC3cBlock < b;
-      // the drain check sits in front of a block's LAST tile: at most NT tiles, NT x 64 entries, between two checks.  Where
-      // the drain has to run, the pipeline is emptied first (one more tile's entries: kC3cStack's extra 64 slots), so that
-      // no accumulator and no A fragment lives across the drain.
+      // the drain check sits in front of a block's LAST unit: at most NT tiles, NT x 64 entries, between two checks.  Where
+      // the drain has to run, the pipeline is emptied first (one more unit's entries: kC3cPipeExtra x 64 slots of kC3cStack)
+      // and the block returns true: the class loop below drains and starts again behind this block, so that no accumulator,
+      // no A fragment, no loaded word and no bias lives across the drain.
       bool flush = false;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        if (t + 1 < NT) {
+      for (int t = 0; t < NU; ++t) {
+        if (t + 1 < NU) {
           acc[(t + 1) & 1] = chain(t + 1, wc);
         } else {
           flush = q_cnt > kC3cDrainAt;
-          if (more && !flush) {
+          // OR fold: the first chain of the block after is issued whether that block exists and runs or not (at the end of a
+          // run its result is dropped: the words are the class's last rows again, or this block's).  A pair is every other
+          // unit, and behind a branch the chain would stand in a basic block of its own, where no fold goes between its MFMAs
+          if (kOrFold || (more && !flush)) {
             make_afrag(wn);
             // (PACKED: the wait for wn, loaded a block ago, stands HERE and not behind the next load, which it would wait for too)
             if constexpr (PACKED) asm volatile("" : "+v"(wn.m1), "+v"(wn.m2));
@@ -760,13 +887,25 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         // branch ends the scheduling region: the chain cannot sink below it
         const int top = fold(acc[t & 1]);
 #if NSM_C3C_FP4
-        // (two MFMAs: MFMA, NSM_C3C_FP4_SPLIT VALU, MFMA, the rest of the fold's eight behind it)
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, NSM_C3C_FP4_SPLIT, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 8 - NSM_C3C_FP4_SPLIT, 0);
-        // (the chain's second MFMA would otherwise be moved behind the branch and the push, in front of its own fold)
-        if (t + 1 < NT || (more && !flush)) asm volatile("" : "+v"(acc[(t + 1) & 1]));
+        if constexpr (kOrFold) {
+          // (four MFMAs and the fold's eight: NSM_C3C_OR_SPLIT VALU behind each of the first three, the rest behind the last)
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, NSM_C3C_OR_SPLIT, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, NSM_C3C_OR_SPLIT, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, NSM_C3C_OR_SPLIT, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 8 - 3 * NSM_C3C_OR_SPLIT, 0);
+        } else {
+          // (two MFMAs: MFMA, NSM_C3C_FP4_SPLIT VALU, MFMA, the rest of the fold's eight behind it)
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, NSM_C3C_FP4_SPLIT, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 8 - NSM_C3C_FP4_SPLIT, 0);
+        }
+        // (the chain's last MFMA would otherwise be moved behind the branch and the push, in front of its own fold)
+        if (t + 1 < NU || kOrFold || (more && !flush)) asm volatile("" : "+v"(acc[(t + 1) & 1]));
 #else
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
@@ -776,36 +915,35 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
 #endif
         finish(top, t, i);
       }
-      if (flush) {
-        drain_full();
-        if (more) {
-          make_afrag(wn);
-          if (i + 2 * kC3cBlock < b) wc = load_rows(i + 2 * kC3cBlock);
-          acc[0] = chain(0, wn);
-        }
-      }
+      return flush;
     };
-    if (q_cnt > kC3cDrainAt)  // (a class of one block has no other check in front of its first NT - 1 tiles)
-      drain_full();
-    rows_t w0 = load_rows(a);
-    make_afrag(w0);
-    // (once per class, outside the block loop: a class of one block never loads the second set.  PACKED: it does, the
-    // class's last row by load_rows' clamp -- nothing waits for the first set before the second load is under way)
-    rows_t w1;
-    if constexpr (PACKED) {
-      w1 = load_rows(a + kC3cBlock);
-    } else {
-      w1 = w0;
-      if (a + kC3cBlock < b) w1 = load_rows(a + kC3cBlock);
-    }
-    acc[0] = chain(0, w0);
-    for (int i = a;;) {
-      block(i, w0, w1);
-      if ((i += kC3cBlock) >= b) break;
-      block(i, w1, w0);
-      if ((i += kC3cBlock) >= b) break;
+    // a run of blocks from row i on: to the end of the class, or to the block that decides on a drain (the next run drains
+    // first; the words that were loaded ahead are loaded again, a drain is rare)
+    for (int i = a; i < b;) {
+      if (q_cnt > kC3cDrainAt)  // (at the start of a class too: one of a single block has no other check in front of its first units)
+        drain_full();
+      if constexpr (kOrFold) make_bias();
+      rows_t w0 = load_rows(i);
+      make_afrag(w0);
+      // (once per run, outside the block loop: a run of one block never loads the second set.  PACKED: it does, the
+      // class's last row by load_rows' clamp -- nothing waits for the first set before the second load is under way)
+      rows_t w1;
+      if constexpr (PACKED) {
+        w1 = load_rows(i + kC3cBlock);
+      } else {
+        w1 = w0;
+        if (i + kC3cBlock < b) w1 = load_rows(i + kC3cBlock);
+      }
+      acc[0] = chain(0, w0);
+      for (;;) {
+        const bool f0 = block(i, w0, w1);
+        if ((i += kC3cBlock) >= b || f0) break;
+        const bool f1 = block(i, w1, w0);
+        if ((i += kC3cBlock) >= b || f1) break;
+      }
     }
 #else
+    if constexpr (kOrFold) make_bias();
     rows_t w_next = load_rows(a);
     for (int i = a; i < b; i += kC3cBlock) {
       const rows_t w = w_next;
@@ -815,7 +953,7 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         drain_full();
       make_afrag(w);
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
+      for (int t = 0; t < NU; ++t) {
         const acc_t acc = chain(t, w);
         finish(fold(acc), t, i);
       }

@@ -7,11 +7,16 @@
 //    k = 32 (l >> 5) + j, j = 0 .. 31, element j in nibble j & 1 (0 = low) of byte j >> 1 of its first four registers;
 //    C/D: column l & 31, row (i & 3) + 8 (i >> 2) + 4 (l >> 5) in register i.
 // 2. perm: the scan's packing of four counts 0 .. 64 into the two left operand words, every count in every byte position.
-// 3. rate: back-to-back chains, one wave per SIMD: ns per MFMA of the i8 32x32x32 form and of the two FP4 forms.
-// Exit status 0 where 1 and 2 agree with the host.
+// 2b. chain4: the OR-fold scan's chain of four MFMAs on one accumulator -- a bias of 2^23 + two need offsets as srcC, one
+//    tile through B scales 2^9 and 2^(9 + k), the other through 2^0 and 2^k, k = 0 .. 3 by column -- against a host integer
+//    loop, bit for bit.
+// 3. rate: back-to-back chains, one wave per SIMD: ns per MFMA of the i8 32x32x32 form and of the two FP4 forms; and a
+//    tile pair as two chains of two (zero C) against one chain of four (bias C), at one and at four waves per SIMD.
+// Exit status 0 where 1, 2 and 2b agree with the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include <vector>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -46,6 +51,28 @@ __global__ void perm_kernel(const uint32_t* w, uint32_t* m1, uint32_t* m2, int n
   m2[i] = __builtin_amdgcn_perm(0u, 0x04000000u, sel) & 0x44444444u;
 }
 
+// the OR-fold scan's chain of FOUR on one accumulator: bias as srcC of the first, tile `hi` through B scales 2^9 and
+// 2^(9 + k_hi), tile `lo` through 2^0 and 2^k_lo.  a[lane][8]: m1 and m2 words of the left rows; bh, bl[lane][8]: those
+// of the two right tiles; s1, s2[lane]: the scale registers of the m1 and of the m2 MFMAs, tile hi in byte 0, lo in byte 1
+__global__ void chain4_kernel(const uint32_t* a, const uint32_t* bh, const uint32_t* bl, const uint32_t* s1, const uint32_t* s2,
+                              const float* bias, float* out) {
+  const int l = threadIdx.x;
+  const v8i A1 = {(int)a[8 * l], (int)a[8 * l + 1], (int)a[8 * l + 2], (int)a[8 * l + 3], 0, 0, 0, 0};
+  const v8i A2 = {(int)a[8 * l + 4], (int)a[8 * l + 5], (int)a[8 * l + 6], (int)a[8 * l + 7], 0, 0, 0, 0};
+  const v8i H1 = {(int)bh[8 * l], (int)bh[8 * l + 1], (int)bh[8 * l + 2], (int)bh[8 * l + 3], 0, 0, 0, 0};
+  const v8i H2 = {(int)bh[8 * l + 4], (int)bh[8 * l + 5], (int)bh[8 * l + 6], (int)bh[8 * l + 7], 0, 0, 0, 0};
+  const v8i L1 = {(int)bl[8 * l], (int)bl[8 * l + 1], (int)bl[8 * l + 2], (int)bl[8 * l + 3], 0, 0, 0, 0};
+  const v8i L2 = {(int)bl[8 * l + 4], (int)bl[8 * l + 5], (int)bl[8 * l + 6], (int)bl[8 * l + 7], 0, 0, 0, 0};
+  const float bv = bias[l];
+  const v16f c = {bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv};
+  const int m1 = (int)s1[l], m2 = (int)s2[l];
+  v16f acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A1, H1, c, 4, 4, 0, 0x7f7f7f7f, 0, m1);
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A2, H2, acc, 4, 4, 0, 0x7f7f7f7f, 0, m2);
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A1, L1, acc, 4, 4, 0, 0x7f7f7f7f, 1, m1);
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A2, L2, acc, 4, 4, 0, 0x7f7f7f7f, 1, m2);
+  for (int i = 0; i < 16; ++i) out[l * 16 + i] = acc[i];
+}
+
 template <int KIND>
 __global__ __launch_bounds__(256) void rate_kernel(float* out, int iters, int seed) {
   v16f acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -65,6 +92,60 @@ __global__ __launch_bounds__(256) void rate_kernel(float* out, int iters, int se
   float s = 0.f;
   for (int i = 0; i < 16; ++i) s += acc[i] + (float)acci[i];
   if (s == 12345.678f) out[threadIdx.x] = s;  // (keeps the chain)
+}
+
+// a tile PAIR: KIND 3 the two chains of two of the max-fold scan (zero C, unscaled then scaled, two accumulators), KIND 4
+// the chain of four on one accumulator with the bias as srcC.  The operands are made opaque every turn, so that no MFMA
+// leaves the loop; the accumulators are only named (no fold: this is the matrix pipe's time alone)
+template <int KIND>
+__global__ __launch_bounds__(256) void pair_rate_kernel(float* out, int iters, int seed) {
+  int x = (int)(threadIdx.x * 0x01010101u) & 0x11111111 & seed;
+  const float bv = 8388608.f + (float)(seed & 0xffff);
+  const v16f bias = {bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv, bv};
+  const v16f z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int s1 = 0x7f887f88 + (seed & 1), s2 = 0x7f887f88 + (seed & 2);
+  v16f acc0 = z, acc1 = z;
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      asm volatile("" : "+v"(x));
+      const v8i A = {x, x, x, x, 0, 0, 0, 0}, B = {x, x ^ 0x10101010, x, x, 0, 0, 0, 0}, B2 = {x ^ 0x01010101, x, x, x, 0, 0, 0, 0};
+      if (KIND == 3) {
+        acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, z, 4, 4, 0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, acc0, 4, 4, 0, 0x7f7f7f7f, 0, s2);
+        acc1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B2, z, 4, 4, 0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B2, acc1, 4, 4, 0, 0x7f7f7f7f, 1, s2);
+        asm volatile("" : "+v"(acc0), "+v"(acc1));
+      } else {
+        acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, bias, 4, 4, 0, 0x7f7f7f7f, 0, s1);
+        acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, acc0, 4, 4, 0, 0x7f7f7f7f, 0, s2);
+        acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B2, acc0, 4, 4, 0, 0x7f7f7f7f, 1, s1);
+        acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B2, acc0, 4, 4, 0, 0x7f7f7f7f, 1, s2);
+        asm volatile("" : "+v"(acc0));
+      }
+    }
+  }
+  float s = 0.f;
+  for (int i = 0; i < 16; ++i) s += acc0[i] + acc1[i];
+  if (s == 12345.678f) out[threadIdx.x] = s;
+}
+
+template <int KIND>
+static int pair_rate(const char* name, float* d_out, int cus, int waves) {
+  const int iters = 1 << 13;
+  hipEvent_t e0, e1;
+  CHECK(hipEventCreate(&e0));
+  CHECK(hipEventCreate(&e1));
+  hipLaunchKernelGGL(pair_rate_kernel<KIND>, dim3(cus * waves), dim3(256), 0, 0, d_out, 64, 0x11111111);
+  CHECK(hipDeviceSynchronize());
+  CHECK(hipEventRecord(e0));
+  hipLaunchKernelGGL(pair_rate_kernel<KIND>, dim3(cus * waves), dim3(256), 0, 0, d_out, iters, 0x11111111);
+  CHECK(hipEventRecord(e1));
+  CHECK(hipEventSynchronize(e1));
+  float ms = 0.f;
+  CHECK(hipEventElapsedTime(&ms, e0, e1));
+  printf("rate %-34s %8.3f ns per tile pair and wave (%d waves per SIMD)\n", name, ms * 1e6 / (iters * 4.0 * waves), waves);
+  return 0;
 }
 
 template <int KIND>
@@ -163,11 +244,92 @@ int main() {
   }
   printf("perm: %d of %d words differ\n", bad_perm, n);
 
+  // --- 2b. the biased chain of four (the OR-fold scan): left indicators 2.0, right codes 0 .. 7, column c of tile hi with
+  // k = c & 3 and of tile lo with k = (c >> 2) & 3, needs per column; every result against a host INTEGER loop, bit for bit
+  int bad_chain = 0;
+  {
+    static int A4[2][32][64], B4[2][2][64][32];  // [m][row][k]; [tile][m][k][col]
+    uint32_t rng = 12345u;
+    auto rnd = [&]() { rng = rng * 1664525u + 1013904223u; return rng >> 8; };
+    for (int m = 0; m < 2; ++m)
+      for (int i = 0; i < 32; ++i)
+        for (int k = 0; k < 64; ++k) {
+          A4[m][i][k] = (rnd() & 1) ? 4 : 0;
+          for (int t = 0; t < 2; ++t) B4[t][m][k][i] = (rnd() & 3) ? 0 : (int)(rnd() & 7);
+        }
+    std::vector<uint32_t> qa(512, 0), qh(512, 0), ql(512, 0), q1(64), q2(64);
+    std::vector<float> qb(64);
+    int nh[32], nl[32];
+    for (int c = 0; c < 32; ++c) {
+      nh[c] = c == 7 ? 255 : (c * 5) % 65;
+      nl[c] = c == 9 ? 255 : (c * 11 + 3) % 65;
+    }
+    for (int l = 0; l < 64; ++l) {
+      const int c = l & 31;
+      for (int m = 0; m < 2; ++m)
+        for (int j = 0; j < 32; ++j) {
+          const int k = 32 * (l >> 5) + j, sh = 4 * (j & 7), w = 8 * l + 4 * m + (j >> 3);
+          qa[w] |= (uint32_t)A4[m][c][k] << sh;
+          qh[w] |= (uint32_t)B4[0][m][k][c] << sh;
+          ql[w] |= (uint32_t)B4[1][m][k][c] << sh;
+        }
+      q1[l] = 0x55aa7f88u;  // (bytes 2 and 3 are not picked)
+      q2[l] = 0xaa550000u | (uint32_t)(0x7f + ((c >> 2) & 3)) << 8 | (uint32_t)(0x88 + (c & 3));
+      qb[l] = (float)((1 << 23) + (256 - nh[c]) * 512 + (256 - nl[c]));
+    }
+    uint32_t *ea, *eh, *el, *e1, *e2;
+    float *eb, *eo;
+    CHECK(hipMalloc(&ea, 2048));
+    CHECK(hipMalloc(&eh, 2048));
+    CHECK(hipMalloc(&el, 2048));
+    CHECK(hipMalloc(&e1, 256));
+    CHECK(hipMalloc(&e2, 256));
+    CHECK(hipMalloc(&eb, 256));
+    CHECK(hipMalloc(&eo, 4096));
+    CHECK(hipMemcpy(ea, qa.data(), 2048, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(eh, qh.data(), 2048, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(el, ql.data(), 2048, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(e1, q1.data(), 256, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(e2, q2.data(), 256, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(eb, qb.data(), 256, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(chain4_kernel, dim3(1), dim3(64), 0, 0, ea, eh, el, e1, e2, eb, eo);
+    CHECK(hipDeviceSynchronize());
+    std::vector<float> qo(1024);
+    CHECK(hipMemcpy(qo.data(), eo, 4096, hipMemcpyDeviceToHost));
+    const int twice[8] = {0, 1, 2, 3, 4, 6, 8, 12};  // 2 x the FP4 value
+    int top = 0;
+    for (int l = 0; l < 64; ++l)
+      for (int i = 0; i < 16; ++i) {
+        const int col = l & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (l >> 5);
+        int d[2] = {0, 0};
+        for (int t = 0; t < 2; ++t) {
+          const int k = t ? (col >> 2) & 3 : col & 3;
+          for (int m = 0; m < 2; ++m) {
+            int s = 0;  // 2.0 x code / 2 = twice[code] / 2 x [indicator] x 2: an integer
+            for (int kk = 0; kk < 64; ++kk) s += A4[m][row][kk] ? twice[B4[t][m][kk][col]] : 0;
+            d[t] += m ? s << k : s;
+          }
+        }
+        const int n = (1 << 23) + (256 - nh[col]) * 512 + (256 - nl[col]) + 512 * d[0] + d[1];
+        top = n > top ? n : top;
+        uint32_t got;
+        memcpy(&got, &qo[l * 16 + i], 4);
+        if (got != (0x4b000000u | (uint32_t)(n - (1 << 23))) && bad_chain++ < 4)
+          printf("chain4: row %d col %d: bits %08x, host N %d (D hi %d lo %d)\n", row, col, got, n, d[0], d[1]);
+      }
+    if (top >= 1 << 24) { printf("chain4: the host sum leaves [2^23, 2^24)\n"); return 2; }
+    printf("chain4 (bias + 2^9 hi + lo, k = 0 .. 3): %d of 1024 differ (largest N - 2^23: %d)\n", bad_chain, top - (1 << 23));
+  }
+
   // --- 3. the rate
   hipDeviceProp_t prop;
   CHECK(hipGetDeviceProperties(&prop, 0));
   if (rate<0>("v_mfma_i32_32x32x32_i8", dout, prop.multiProcessorCount)) return 2;
   if (rate<1>("v_mfma_f32_32x32x64_f8f6f4 fp4", dout, prop.multiProcessorCount)) return 2;
   if (rate<2>("v_mfma_scale_f32_32x32x64_f8f6f4 fp4", dout, prop.multiProcessorCount)) return 2;
-  return (bad[0] || bad[1] || bad_perm) ? 1 : 0;
+  for (int waves = 1; waves <= 4; waves += 3) {
+    if (pair_rate<3>("two chains of two, zero C", dout, prop.multiProcessorCount, waves)) return 2;
+    if (pair_rate<4>("one chain of four, bias C", dout, prop.multiProcessorCount, waves)) return 2;
+  }
+  return (bad[0] || bad[1] || bad_perm || bad_chain) ? 1 : 0;
 }
