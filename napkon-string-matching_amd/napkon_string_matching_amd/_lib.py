@@ -17,6 +17,7 @@ FLAG_PACK, FLAG_NO_PACK = 2048, 4096  # nsm_indel_raw_grid, two-stage: force / f
 FLAG_SPLIT, FLAG_TILE, FLAG_PROBE = 128, 256, 512  # nsm_indel_levels_grid, one-word strings: force the split path / the tile kernel; scan only
 FLAG_PARK = 16  # nsm_indel_levels_grid, strings > 64 code units: the round-2 park kernel instead of the shared-tile kernel
 BUILD_PARTITION, BUILD_VALIDATE, BUILD_SORT = 1, 2, 4
+ASSIGN_ROUNDS_ONLY, ASSIGN_STREAM_ONLY = 1, 2  # nsm_assign_hits (include/nsm_hip_assign.h): one stage only (A/B runs, tests)
 CAT_NONE, CAT_INTERSECT, CAT_INTERSECT_OR_BOTH_EMPTY = 0, 1, 2
 
 c_i32p = ctypes.c_void_p  # device pointers travel as integers
@@ -131,6 +132,9 @@ EXPORTS = (
     "nsm_jaccard_levels_floor_grid",
 )
 
+# include/nsm_hip_assign.h: additive entries, bound when the library has them (a call without one raises NsmLibraryError)
+ASSIGN_EXPORTS = ("nsm_assign_hits",)
+
 _lib = None
 
 
@@ -224,8 +228,24 @@ def load() -> ctypes.CDLL:
             fn.restype = ctypes.c_int
     lib.nsm_indel_levels_workspace_bytes.restype = c_u64
     lib.nsm_last_error.restype = ctypes.c_char_p
+    # hits, n, left_ids, right_ids, flags, out, out_count, stats, stream
+    assign_args = {"nsm_assign_hits": [vp, c_u64, i32, i32, u32, vp, vp, vp, vp]}
+    for name in ASSIGN_EXPORTS:
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # an older library: everything else still works
+            continue
+        fn.argtypes, fn.restype = assign_args[name], ctypes.c_int
     _lib = lib
     return lib
+
+
+def entry(name: str):
+    """A C entry of the loaded library; ``NsmLibraryError`` when this build of the library lacks it."""
+    try:
+        return getattr(load(), name)
+    except AttributeError:
+        raise NsmLibraryError(f"{LIB_PATH} has no {name}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')") from None
 
 
 def check(status: int, what: str) -> None:

@@ -25,6 +25,9 @@ Same names, call convention and error behaviour as the reference's
   everything within ``margin`` of it -- all its ties at ``margin=0``, which no fixed ``k`` returns -- and with
   ``mutual=True`` only the pairs that are best from both sides (reciprocal best hits).
 
+* ``plugin.assign(left_items, right_items, threshold)`` turns the match list into a one-to-one mapping: the best pair, both
+  its items removed, and again (``grid.assign_of_hits``), assigned on the device.
+
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
 """
@@ -292,6 +295,30 @@ class _IntersectionVsUnion:
                      wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]), len(l_rows), len(r_rows), margin,
                      threshold, mutual, fast, general)
 
+    def assign(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+               prune: bool = True) -> grid.Hits:
+        """``grid.assign_of_hits(raw_grid(left_items, right_items, threshold))``: a one-to-one mapping between the two lists
+        -- the best pair, both its items removed, and again (ties by left then right index) -- of the pairs scoring
+        ``>= threshold``.  ``threshold`` is required: at 0 the hit list is the whole N x M grid.  The hits are ordered and
+        assigned on the device and only the assignment (at most min(N, M) records) comes back; where wide items send part
+        of the grid through the general kernels the merged host list goes through ``grid.assign_hits``."""
+        from .. import wide
+
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_rows = [list(set_operand(v)) for v in left_items]
+        r_rows = [list(set_operand(v)) for v in right_items]
+        if not l_rows or not r_rows:
+            return wide.merge([])
+        if wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]) is not None:
+            return grid.assign_hits(self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune), len(l_rows),
+                                    len(r_rows), device=dev)
+        vocab = tables.Vocabulary()
+        width = tables.pick_width(max((len(set(r)) for r in l_rows), default=1), max((len(set(r)) for r in r_rows), default=1))
+        lt = tables.SetTable.from_rows(l_rows, "left", dev, vocab, width=width)
+        rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
+        return grid.jaccard_raw_assign(lt, rt, threshold, prune=prune)
+
 
 class _FuzzyMatch:
     __name__ = "fuzzy_match"
@@ -423,6 +450,26 @@ class _FuzzyMatch:
         return _best(lambda t: self.profile(left_items, right_items, t, device=dev, prune=prune),
                      wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]), len(l_ops), len(r_ops), margin,
                      threshold, mutual, fast, general)
+
+    def assign(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+               prune: bool = True) -> grid.Hits:
+        """``grid.assign_of_hits(raw_grid(left_items, right_items, threshold))``: a one-to-one mapping between the two lists
+        -- the best pair, both its items removed, and again (ties by left then right index) -- of the pairs scoring
+        ``>= threshold``.  ``threshold`` is required: at 0 the hit list is the whole N x M grid.  The hits are ordered and
+        assigned on the device and only the assignment (at most min(N, M) records) comes back; where wide items send part
+        of the grid through the general kernels the merged host list goes through ``grid.assign_hits``."""
+        from .. import wide
+
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        if not l_ops or not r_ops:
+            return wide.merge([])
+        if wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]) is not None:
+            return grid.assign_hits(self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune), len(l_ops),
+                                    len(r_ops), device=dev)
+        lt, rt = tables.encode_strings(l_ops, r_ops, dev)
+        return grid.indel_raw_assign(lt, rt, threshold, prune=prune)
 
 
 intersection_vs_union = _IntersectionVsUnion()

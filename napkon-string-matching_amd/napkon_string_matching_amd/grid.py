@@ -131,7 +131,7 @@ def run_grid(launch: Callable[[HitBuffer, int], int], device, capacity: Optional
 # ------------------------------------------------------------------------------- RAW grids
 def jaccard_raw_grid(
     left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
-    index: Optional[bool] = None,
+    index: Optional[bool] = None, defer: bool = False,
 ) -> Hits:
     """``intersection_vs_union`` on one set per item, all N x M pairs, hits ``>= threshold``.
     ``index``: None = the library decides (candidates from the right table's global inverted index where its posting
@@ -156,12 +156,12 @@ def jaccard_raw_grid(
 
     # (0 = unknown on either side: the sort keeps all 32 bits of the ids)
     id_limit = max(left.id_limit, right.id_limit) if left.id_limit and right.id_limit else 0
-    return run_grid(launch, left.ids.device, capacity, "nsm_jaccard_raw_grid", id_limit=id_limit)
+    return run_grid(launch, left.ids.device, capacity, "nsm_jaccard_raw_grid", id_limit=id_limit, defer=defer)
 
 
 def indel_raw_grid(
     left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
-    two_stage: bool = True, pack: Optional[bool] = None,
+    two_stage: bool = True, pack: Optional[bool] = None, defer: bool = False,
 ) -> Hits:
     """``fuzzy_match`` (QRatio/100 = Indel ratio after default_process) on one string per item.
     ``two_stage=False``: the 32-bucket histogram test for every pair even when both tables carry the ``hist16``
@@ -178,7 +178,7 @@ def indel_raw_grid(
             ls, rs, float(threshold), flags, buf.records.data_ptr(), buf.capacity, buf.count.data_ptr(), stream
         )
 
-    return run_grid(launch, left.codes.device, capacity, "nsm_indel_raw_grid")
+    return run_grid(launch, left.codes.device, capacity, "nsm_indel_raw_grid", defer=defer)
 
 
 # ------------------------------------------------------------------------------- RAW top-k
@@ -1008,3 +1008,129 @@ def split_workspace(nbytes: int, device) -> Optional[torch.Tensor]:
         return torch.empty(words, dtype=torch.int64, device=device)
     except torch.cuda.OutOfMemoryError:
         return None
+
+
+# ------------------------------------------------------------------------------- one-to-one assignment
+ASSIGN_ROUTES = {None: 0, "rounds": _lib.ASSIGN_ROUNDS_ONLY, "stream": _lib.ASSIGN_STREAM_ONLY}
+
+
+def assign_of_hits(hits: Hits) -> Hits:
+    """The definition of a one-to-one assignment on a hit list: walk the records in canonical order, take a record iff
+    neither its ``i`` nor its ``j`` has been taken, and mark both.  The taken records, in canonical order.  A record that
+    repeats an ``(i, j)`` is a record like any other: the second one is never taken.  The result is one-to-one and maximal
+    (no record of ``hits`` has both items free), and a prefix in the score: assigning the records ``>= t`` gives the
+    records ``>= t`` of the assignment."""
+    h = _canonical(np.asarray(hits.score, np.float64), np.asarray(hits.i, np.int32), np.asarray(hits.j, np.int32))
+    left, right, keep = set(), set(), []
+    for r, (a, b) in enumerate(zip(h.i.tolist(), h.j.tolist())):
+        if a not in left and b not in right:
+            left.add(a)
+            right.add(b)
+            keep.append(r)
+    keep = np.asarray(keep, dtype=np.int64)
+    return Hits(h.score[keep], h.i[keep], h.j[keep])
+
+
+def _assign_flags(route) -> int:
+    if route not in ASSIGN_ROUTES:
+        raise ValueError(f"route must be None, 'rounds' or 'stream', got {route!r}")
+    return ASSIGN_ROUTES[route]
+
+
+def assign_hits_device(buf: HitBuffer, n: int, n_left: int, n_right: int, id_limit: int = 0, route=None,
+                       stats: Optional[list] = None) -> Hits:
+    """``assign_of_hits`` of the ``n`` records in ``buf`` without the list leaving the device: canonical order
+    (``nsm_sort_hits``, in place), ``nsm_assign_hits``, the order again for the at most min(n, n_left, n_right) records of
+    the assignment, and one D2H copy of those.  ``n_left`` / ``n_right``: exclusive bounds of the records' ids."""
+    flags = _assign_flags(route)
+    if n == 0:
+        if stats is not None:
+            stats[:] = [0, 0, 0, 0]
+        return Hits(np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.int32))
+    fn = _lib.entry("nsm_assign_hits")
+    lib = _lib.load()
+    dev = buf.records.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    limit = max(0, min(int(id_limit), 0x7FFFFFFF))
+    scratch_ptr = 0
+    if n > SMALL_SORT_MAX:
+        if buf.scratch is None or buf.scratch.shape[0] < n:
+            buf.scratch = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        scratch_ptr = buf.scratch.data_ptr()
+    _lib.check(lib.nsm_sort_hits(buf.records.data_ptr(), scratch_ptr, buf.capacity, buf.count.data_ptr(), n, limit, stream),
+               "nsm_sort_hits")
+    out = HitBuffer(max(1, min(n, int(n_left), int(n_right))), dev)
+    st = torch.zeros(4, dtype=torch.int64, device=dev)
+    _lib.check(fn(buf.records.data_ptr(), n, int(n_left), int(n_right), flags, out.records.data_ptr(), out.count.data_ptr(),
+                  st.data_ptr(), stream), "nsm_assign_hits")
+    if stats is not None:
+        stats[:] = [int(v) for v in st.tolist()]
+    return sort_hits_device(out, int(out.count.item()), limit)
+
+
+def assign_hits(hits: Hits, n_left: Optional[int] = None, n_right: Optional[int] = None, device=None, route=None,
+                stats: Optional[list] = None) -> Hits:
+    """``assign_of_hits(hits)`` on the device for any host hit list: canonical order, upload, ``nsm_assign_hits``,
+    ``nsm_sort_hits`` on the result, and a copy back of at most min(N, M) records.  ``n_left`` / ``n_right``: exclusive
+    bounds of the ids (None = the largest id in ``hits`` + 1); ids must be ``>= 0``.  ``route``: None = the library routes
+    (parallel rounds while they pay, then the one-workgroup stream stage), "rounds" / "stream" = one stage only (same
+    records).  ``stats`` receives [rounds run, records live when the stream stage started, matches made by rounds, matches
+    made by the stream stage]."""
+    _assign_flags(route)
+    dev = _require_gpu("cuda" if device is None else device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    h = _canonical(np.asarray(hits.score, np.float64), np.asarray(hits.i, np.int32), np.asarray(hits.j, np.int32))
+    n = len(h)
+    nl = max(int(n_left or 0), int(h.i.max()) + 1 if n else 0)
+    nr = max(int(n_right or 0), int(h.j.max()) + 1 if n else 0)
+    if n and (int(h.i.min()) < 0 or int(h.j.min()) < 0):
+        raise ValueError("assign_hits: ids must be >= 0")
+    buf = HitBuffer(n, dev)
+    if n:
+        host = np.empty((n, 2), dtype=np.float64)
+        host[:, 0] = h.score
+        ij = host.view(np.int32).reshape(n, 4)
+        ij[:, 2], ij[:, 3] = h.i, h.j
+        buf.records[:n] = torch.from_numpy(host).to(dev)
+        buf.count.fill_(n)
+    return assign_hits_device(buf, n, nl, nr, max(nl, nr), route, stats)
+
+
+def _assign_pending(pending: PendingHits, left, right, route, stats: Optional[list]) -> Hits:
+    ids_l, ids_r = _left_id_limit(left.orig, left.n), _left_id_limit(right.orig, right.n)
+    return assign_hits_device(pending.buf, pending.n, ids_l, ids_r, max(ids_l, ids_r) if ids_l and ids_r else 0, route, stats)
+
+
+def indel_raw_assign(left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
+                     two_stage: bool = True, pack: Optional[bool] = None, route=None, stats: Optional[list] = None) -> Hits:
+    """``assign_of_hits(indel_raw_grid(left, right, threshold, ...))``: the grid's hits stay in their device buffer, are
+    ordered and assigned there, and only the assignment (at most min(N, M) records) crosses to the host."""
+    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True)
+    return _assign_pending(pending, left, right, route, stats)
+
+
+def jaccard_raw_assign(left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
+                       index: Optional[bool] = None, route=None, stats: Optional[list] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_raw_assign``."""
+    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True)
+    return _assign_pending(pending, left, right, route, stats)
+
+
+def indel_levels_assign(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, threshold: float,
+                        category_mode: int = _lib.CAT_NONE, prune: bool = True, capacity: Optional[int] = None, route=None,
+                        stats: Optional[list] = None, **grid_options) -> Hits:
+    """``assign_of_hits(indel_levels_grid(...))`` without the grid's hits leaving the device (``grid_options``: the grid's
+    other keywords)."""
+    pending = indel_levels_grid(left, left_strings, right, right_strings, threshold, category_mode=category_mode, prune=prune,
+                                capacity=capacity, defer=True, **grid_options)
+    return _assign_pending(pending, left, right, route, stats)
+
+
+def jaccard_levels_assign(left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE,
+                          prune: bool = True, capacity: Optional[int] = None, index: Optional[bool] = None, route=None,
+                          stats: Optional[list] = None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_levels_assign``."""
+    pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
+                                  index=index, defer=True)
+    return _assign_pending(pending, left, right, route, stats)

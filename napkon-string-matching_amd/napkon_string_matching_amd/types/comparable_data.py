@@ -350,6 +350,7 @@ class ComparableData:
         top_k: Optional[int] = None,
         best_margin: Optional[float] = None,
         mutual_best: bool = False,
+        one_to_one: bool = False,
         **kwargs,
     ) -> Comparable:
         """:69-128.  Scores at ``cache_threshold or score_threshold``, keeps ``>= score_threshold``,
@@ -369,6 +370,14 @@ class ComparableData:
         ``score_threshold`` has no rows either way, and one whose best is above it has the same best at both thresholds.
         Restrictions as for ``top_k`` (at most 64 category labels; one rank); not together with ``top_k``.
 
+        ``one_to_one=True``: a mapping instead of a match list -- of the frame ``compare()`` returns without it (after
+        ``dropna``, whitelist removal, blacklist and categories, zero-level pairs included) the rows that
+        ``grid.assign_of_hits`` takes: the best pair, both its items removed, and again; equal scores in the order (left
+        position, right position).  Every item appears in at most one row, and no row of the plain frame has both its
+        items unused.  Assigned at ``cache_threshold`` and filtered at ``score_threshold`` afterwards, which keeps the
+        meaning: rows below a threshold are walked after all rows at or above it.  Not together with ``top_k`` or
+        ``best_margin``; one rank.
+
         Compare cache: the reference keys ``compared__score_{md5}.json`` by a hash
         that embeds object addresses (``str(kwargs.items())`` of ``Mapping`` objects, :61-67), so it
         never hits, and it leaves ``score_func`` out of the key.  Here the key is a stable content
@@ -380,12 +389,13 @@ class ComparableData:
         if top_k is not None:
             top_k = grid.check_k(top_k)
         best_margin = _check_best_args(best_margin, mutual_best, top_k)
+        one_to_one = _check_one_to_one(one_to_one, top_k, best_margin)
         first = cache_threshold if cache_threshold else score_threshold
         cache_file = None
         if cached and cache_dir is not None:
             cache_file = Path(cache_dir) / CACHE_FILE_PATTERN.format(
                 self._hash_compare_args(other, existing_mappings_whitelist, existing_mappings_blacklist,
-                                        compare_column, first, kwargs, top_k, best_margin, mutual_best))
+                                        compare_column, first, kwargs, top_k, best_margin, mutual_best, one_to_one))
         # hit or miss is decided ONCE for all ranks of a sharded run (rank 0 looks, everybody follows): with a
         # rank-local exists() the ranks can disagree -- a cache_dir that is not shared between nodes, or a repeated
         # compare() where one rank looks before rank 0's rename has landed -- and the ranks that miss would then
@@ -411,6 +421,7 @@ class ComparableData:
                 top_k=top_k,
                 best_margin=best_margin,
                 mutual_best=mutual_best,
+                one_to_one=one_to_one,
                 **kwargs,
             )
             if cache_file is not None:
@@ -448,7 +459,8 @@ class ComparableData:
         t = grid.check_thresholds(thresholds)
         if distributed.world()[1] > 1:
             raise NotImplementedError("compare_profile on more than one rank (sharded profiles are not implemented)")
-        for name in ("score_threshold", "cached", "cache_threshold", "cache_dir", "top_k", "best_margin", "mutual_best"):
+        for name in ("score_threshold", "cached", "cache_threshold", "cache_dir", "top_k", "best_margin", "mutual_best",
+                     "one_to_one"):
             kwargs.pop(name, None)
         pre = self._compare_prelude(
             other, existing_mappings_whitelist, existing_mappings_blacklist, kwargs.get("score_func"), compare_column,
@@ -531,7 +543,7 @@ class ComparableData:
         return Comparable(data=pd.DataFrame(out), left_name=pre.lp, right_name=pre.rp)
 
     def _hash_compare_args(self, other, whitelist, blacklist, compare_column, cache_threshold, kwargs, top_k=None,
-                           best_margin=None, mutual_best=False) -> str:
+                           best_margin=None, mutual_best=False, one_to_one=False) -> str:
         other_csv = other.to_csv() if hasattr(other, "to_csv") else pd.DataFrame(other).to_csv(index=False)
         parts = [
             self.to_csv(), other_csv,
@@ -547,6 +559,8 @@ class ComparableData:
             parts.append(f"best_margin={float(best_margin)!r}")
             if mutual_best:
                 parts.append("mutual_best=True")
+        if one_to_one:
+            parts.append("one_to_one=True")
         return md5("\x1f".join(parts).encode("utf-8"), usedforsecurity=False).hexdigest()
 
     def _compare_prelude(self, right, existing_mappings_whitelist, existing_mappings_blacklist, score_func, compare_column,
@@ -645,15 +659,22 @@ class ComparableData:
         top_k: Optional[int] = None,
         best_margin: Optional[float] = None,
         mutual_best: bool = False,
+        one_to_one: bool = False,
         **kwargs,
     ) -> Comparable:
         """:133-246 (steps 1-12 of SURVEY.md 3.2), the per-pair part on the GPU.  ``top_k``: per left item only the
         first ``top_k`` pairs (score descending, right item ascending) of what would be returned (``compare``).
         ``best_margin`` / ``mutual_best``: only the pairs within ``best_margin`` of their left (and right) item's best score
-        among what would be returned (``compare``): a profile sweep for the bests, then a floor grid."""
+        among what would be returned (``compare``): a profile sweep for the bests, then a floor grid.
+        ``one_to_one``: ``grid.assign_of_hits`` of what would be returned, by position in the compared frames
+        (``grid.assign_hits`` on the final host arrays: after the blacklist, the host-side category filter and the
+        zero-level pairs)."""
         if top_k is not None:
             top_k = grid.check_k(top_k)
         best_margin = _check_best_args(best_margin, mutual_best, top_k)
+        one_to_one = _check_one_to_one(one_to_one, top_k, best_margin)
+        if one_to_one and distributed.world()[1] > 1:
+            raise NotImplementedError("one_to_one on more than one rank (sharded assignment is not implemented)")
         if best_margin is not None and distributed.world()[1] > 1:
             raise NotImplementedError("best_margin on more than one rank (sharded best matches are not implemented)")
         pre = self._compare_prelude(right, existing_mappings_whitelist, existing_mappings_blacklist, score_func, compare_column,
@@ -768,6 +789,10 @@ class ComparableData:
             if world_size > 1:  # (host-filtered hits: packed, copied to the device, gathered, copied back)
                 hs, hi, hj = distributed.all_gather_hits(hs, hi, hj)
 
+        if one_to_one and len(hs):
+            taken = grid.assign_hits(grid.Hits(hs, hi.astype(np.int32), hj.astype(np.int32)), n_l, n_r)
+            hi, hj, hs = taken.i.astype(np.int64), taken.j.astype(np.int64), taken.score
+
         # ---- output frame in the reference's row order (pair label ascending)
         label = hi.astype(np.int64) * n_r + hj.astype(np.int64)
         order = np.argsort(label, kind="stable")
@@ -821,6 +846,18 @@ def _check_best_args(best_margin, mutual_best, top_k):
     if top_k is not None:
         raise ValueError("best_margin and top_k cannot be combined")
     return grid.check_margin(best_margin)
+
+
+def _check_one_to_one(one_to_one, top_k, best_margin) -> bool:
+    """``one_to_one`` of ``compare``: a bool that excludes the per-item queries, else ``ValueError`` -- before any device
+    work."""
+    if not isinstance(one_to_one, (bool, np.bool_)):
+        raise ValueError(f"one_to_one must be a bool, got {one_to_one!r}")
+    if one_to_one and top_k is not None:
+        raise ValueError("one_to_one and top_k cannot be combined")
+    if one_to_one and best_margin is not None:
+        raise ValueError("one_to_one and best_margin cannot be combined")
+    return bool(one_to_one)
 
 
 def _prelude_profile(pre, t) -> grid.ThresholdProfile:
