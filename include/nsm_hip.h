@@ -621,6 +621,20 @@ int nsm_jaccard_any_grid(const nsm_any_sets* left, const nsm_any_sets* right, do
  * touches at most n_hint records of `scratch` and of `hits`: a scratch of n_hint records is enough and the records of `hits`
  * from n_hint on stay as they are.  What the records of `hits` between the live ones and n_hint (n_hint == 0: `capacity`)
  * hold afterwards is unspecified.  With more live records than promised, records of `hits` beyond n_hint may be moved too.
+ * When *hit_count exceeds `capacity` (a grid that overflowed), the first `capacity` records are ordered and the counter
+ * stays as it is.
+ *
+ * The order is ONE order on every path (eager or on a capturing stream, any size): ascending in the 128-bit integer key
+ *     key(record) = K(score) : I(i) : I(j)            (most significant part first)
+ *     K(score)    = ~A,  A = B ^ (B >> 63 ? ~0 : 1 << 63),  B = the 64 bits of the double `score`
+ *     I(id)       = the 32 bits of `id` with the sign bit flipped (so negative ids sort first, as int32 values do)
+ * A is ascending in the score for every non-NaN double, K descending.  Scores are compared by these bits, not as doubles:
+ * +0.0 sorts before -0.0 (they are different records and come back as they went in), -inf last, +inf first.  NaN scores are
+ * out of contract: no record is lost or altered, the records come back in key order (positive NaNs before +inf, negative
+ * ones behind -inf), which is no order a caller should rely on.
+ * With id_limit in [1, 2^31] the key is narrowed for sorting: bits = max(1, ceil(log2(id_limit))) and
+ *     key = K(score) : i : j  with i and j as `bits`-bit fields (no flip), 64 + 2 * bits key bits in all --
+ * the same order for ids in [0, id_limit).  id_limit == 0 or above 2^31 keeps the full key.
  *   n_hint    0, or the caller's promise that at most n_hint records are live (a host that has read the counter knows):
  *             the launch geometry then follows n_hint instead of capacity -- one launch up to 8192 records whatever the
  *             buffer's size.  With more live records than promised the order is unspecified (no record is lost).

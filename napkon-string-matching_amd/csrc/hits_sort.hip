@@ -28,8 +28,18 @@
 
 namespace nsm {
 
+// Order-preserving integer image of a double, inverted: larger score -> smaller key.
+__device__ __forceinline__ unsigned long long score_key(double score) {
+  const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(score));
+  const unsigned long long asc = bits ^ ((bits >> 63) ? ~0ull : (1ull << 63));
+  return ~asc;
+}
+
+// The order of all three paths is the order of the integer keys (score_key, i, j): +0.0 comes before -0.0, and NaN
+// records (out of contract) still have a place, so the network stays a permutation that terminates sorted by key.
 __device__ __forceinline__ bool hit_before(const nsm_hit& a, const nsm_hit& b) {
-  if (a.score != b.score) return a.score > b.score;
+  const unsigned long long ka = score_key(a.score), kb = score_key(b.score);
+  if (ka != kb) return ka < kb;
   if (a.i != b.i) return a.i < b.i;
   return a.j < b.j;
 }
@@ -43,13 +53,6 @@ __device__ __forceinline__ unsigned long long live_count(const unsigned long lon
 constexpr int kSmallSortMax = 8192;  // one workgroup, 128-bit keys in LDS: 128 KB of the CU's 160 KB at the maximum
 constexpr unsigned long long kRankSortMax = 8192;
 constexpr int kSmallSortThreads = 1024;
-
-// Order-preserving integer image of a double, inverted: larger score -> smaller key.
-__device__ __forceinline__ unsigned long long score_key(double score) {
-  const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(score));
-  const unsigned long long asc = bits ^ ((bits >> 63) ? ~0ull : (1ull << 63));
-  return ~asc;
-}
 
 __global__ __launch_bounds__(kSmallSortThreads) void small_sort_kernel(
     nsm_hit* __restrict__ hits, unsigned long long capacity, const unsigned long long* __restrict__ count, int lds_records) {

@@ -327,7 +327,20 @@ def banned_csr(banned, n_ids: int, device):
 
 
 def _left_id_limit(orig: torch.Tensor, n: int) -> int:
-    return int(orig[:n].max().item()) + 1 if n else 0
+    """An exclusive upper bound of a device table's caller ids, as ``tables._id_limit`` gives it: max(orig) + 1, and 0
+    (= unknown: ``nsm_sort_hits`` then keeps all 32 bits) for an empty table or one that holds a negative id."""
+    if not n:
+        return 0
+    lo, hi = torch.stack(torch.aminmax(orig[:n])).tolist()  # (one synchronisation)
+    return 0 if lo < 0 else int(hi) + 1
+
+
+def _id_count(orig: torch.Tensor, n: int, what: str) -> int:
+    """``_left_id_limit`` as the length of an array the kernels index by caller id: a negative id has no slot there."""
+    ids = _left_id_limit(orig, n)
+    if n and not ids:
+        raise ValueError(f"{what}: caller ids must be >= 0")
+    return ids
 
 
 def _levels_top_k(entry: str, tables: tuple, left, right, device, k: int, threshold: float, category_mode: int, prune: bool,
@@ -339,7 +352,7 @@ def _levels_top_k(entry: str, tables: tuple, left, right, device, k: int, thresh
         category_mode = left.category_mode
     structs = [t.struct() for t in tables]
     flags = _lib.FLAG_PRUNE if prune else 0
-    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), device)
+    bs, bj = banned_csr(banned, _id_count(left.orig, left.n, "banned") if banned is not None else 0, device)
     ptr = lambda t: 0 if t is None else t.data_ptr()
     return _top_k(lambda out, cnt, st, kk, stream: fn(
         *structs, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
@@ -443,7 +456,7 @@ def _profile(launch: Callable, t: np.ndarray, left_orig: torch.Tensor, n_left: i
     import ctypes
 
     dev = _require_gpu(device)
-    ids_l, ids_r = _left_id_limit(left_orig, n_left), _left_id_limit(right_orig, n_right)
+    ids_l, ids_r = _id_count(left_orig, n_left, what), _id_count(right_orig, n_right, what)
     pairs = torch.zeros(len(t), dtype=torch.int64, device=dev)
     left_best = torch.full((max(1, ids_l),), -1.0, dtype=torch.float64, device=dev)
     right_best = torch.full((max(1, ids_r),), -1.0, dtype=torch.float64, device=dev)
@@ -491,7 +504,7 @@ def _levels_profile(entry: str, tables: tuple, left, right, device, t: np.ndarra
         category_mode = left.category_mode
     structs = [tab.struct() for tab in tables]
     flags = _lib.FLAG_PRUNE if prune else 0
-    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), device)
+    bs, bj = banned_csr(banned, _id_count(left.orig, left.n, "banned") if banned is not None else 0, device)
     ptr = lambda x: 0 if x is None else x.data_ptr()
     return _profile(lambda lad, n, pairs, lb, rb, st, stream: fn(*structs, lad, n, int(category_mode), flags, ptr(bs), ptr(bj),
                                                                  pairs, lb, rb, st, stream),
@@ -597,6 +610,10 @@ def _floor_grid(entry: str, structs: list, middle: tuple, left, right, device, t
     dev = _require_gpu(device)
     fn = getattr(_lib.load(), entry)
     ids_l, ids_r = _left_id_limit(left.orig, left.n), _left_id_limit(right.orig, right.n)
+    if left_floor is not None:  # (the kernels index a floor array by caller id)
+        _id_count(left.orig, left.n, entry + ": left_floor")
+    if right_floor is not None:
+        _id_count(right.orig, right.n, entry + ": right_floor")
     lf = _floor_column(left_floor, ids_l, dev, entry + ": left_floor")
     rf = _floor_column(right_floor, ids_r, dev, entry + ": right_floor")
     st = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -641,7 +658,7 @@ def _levels_floor_grid(entry: str, tables: tuple, left, right, device, threshold
                        category_mode: int, prune: bool, banned, stats: Optional[list], capacity: Optional[int]) -> Hits:
     if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
         category_mode = left.category_mode
-    bs, bj = banned_csr(banned, _left_id_limit(left.orig, left.n), device)
+    bs, bj = banned_csr(banned, _id_count(left.orig, left.n, "banned") if banned is not None else 0, device)
     ptr = lambda t: 0 if t is None else t.data_ptr()
     middle = (int(category_mode), _lib.FLAG_PRUNE if prune else 0, ptr(bs), ptr(bj))
     return _floor_grid(entry, [t.struct() for t in tables], middle, left, right, device, threshold, left_floor, right_floor,
@@ -778,7 +795,7 @@ def lookup_pairs(hits, i, j) -> np.ndarray:
 def _row_map(orig: torch.Tensor, n: int, device) -> torch.Tensor:
     """The inverse of a table's ``orig`` column as the entries read it: row_map[id] = the row of caller id ``id``, -1 for
     an id no row carries -- one scatter of ``arange`` by ``orig``."""
-    ids = _left_id_limit(orig, n)
+    ids = _id_count(orig, n, "pairs")
     rows = torch.full((max(1, ids),), -1, dtype=torch.int32, device=device)
     if n:
         rows[orig[:n].long()] = torch.arange(n, dtype=torch.int32, device=device)
@@ -1098,7 +1115,8 @@ def assign_hits(hits: Hits, n_left: Optional[int] = None, n_right: Optional[int]
 
 
 def _assign_pending(pending: PendingHits, left, right, route, stats: Optional[list]) -> Hits:
-    ids_l, ids_r = _left_id_limit(left.orig, left.n), _left_id_limit(right.orig, right.n)
+    # (nsm_assign_hits marks taken items in arrays indexed by caller id)
+    ids_l, ids_r = _id_count(left.orig, left.n, "assign"), _id_count(right.orig, right.n, "assign")
     return assign_hits_device(pending.buf, pending.n, ids_l, ids_r, max(ids_l, ids_r) if ids_l and ids_r else 0, route, stats)
 
 
