@@ -18,6 +18,7 @@ FLAG_SPLIT, FLAG_TILE, FLAG_PROBE = 128, 256, 512  # nsm_indel_levels_grid, one-
 FLAG_PARK = 16  # nsm_indel_levels_grid, strings > 64 code units: the round-2 park kernel instead of the shared-tile kernel
 BUILD_PARTITION, BUILD_VALIDATE, BUILD_SORT = 1, 2, 4
 ASSIGN_ROUNDS_ONLY, ASSIGN_STREAM_ONLY = 1, 2  # nsm_assign_hits (include/nsm_hip_assign.h): one stage only (A/B runs, tests)
+GROUP_CONTINUE = 1  # nsm_group_hits (include/nsm_hip_groups.h): `label` holds a forest, link the lists into it
 CAT_NONE, CAT_INTERSECT, CAT_INTERSECT_OR_BOTH_EMPTY = 0, 1, 2
 
 c_i32p = ctypes.c_void_p  # device pointers travel as integers
@@ -26,6 +27,11 @@ c_u64 = ctypes.c_uint64
 
 class NsmHit(ctypes.Structure):
     _fields_ = [("score", ctypes.c_double), ("i", ctypes.c_int32), ("j", ctypes.c_int32)]
+
+
+class NsmHitList(ctypes.Structure):
+    _fields_ = [("hits", ctypes.c_void_p), ("n", ctypes.c_uint64), ("left_base", ctypes.c_int32), ("left_ids", ctypes.c_int32),
+                ("right_base", ctypes.c_int32), ("right_ids", ctypes.c_int32)]
 
 
 class NsmSetTable(ctypes.Structure):
@@ -134,6 +140,8 @@ EXPORTS = (
 
 # include/nsm_hip_assign.h: additive entries, bound when the library has them (a call without one raises NsmLibraryError)
 ASSIGN_EXPORTS = ("nsm_assign_hits",)
+# include/nsm_hip_groups.h, likewise
+GROUP_EXPORTS = ("nsm_group_hits",)
 
 _lib = None
 
@@ -230,12 +238,15 @@ def load() -> ctypes.CDLL:
     lib.nsm_last_error.restype = ctypes.c_char_p
     # hits, n, left_ids, right_ids, flags, out, out_count, stats, stream
     assign_args = {"nsm_assign_hits": [vp, c_u64, i32, i32, u32, vp, vp, vp, vp]}
-    for name in ASSIGN_EXPORTS:
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:  # an older library: everything else still works
-            continue
-        fn.argtypes, fn.restype = assign_args[name], ctypes.c_int
+    # lists (host), n_lists, nodes, min_score, flags, label, stats, stream
+    group_args = {"nsm_group_hits": [P(NsmHitList), i32, i32, ctypes.c_double, u32, vp, vp, vp]}
+    for names, args in ((ASSIGN_EXPORTS, assign_args), (GROUP_EXPORTS, group_args)):
+        for name in names:
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:  # an older library: everything else still works
+                continue
+            fn.argtypes, fn.restype = args[name], ctypes.c_int
     _lib = lib
     return lib
 

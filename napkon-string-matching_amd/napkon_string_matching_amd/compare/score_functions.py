@@ -28,6 +28,10 @@ Same names, call convention and error behaviour as the reference's
 * ``plugin.assign(left_items, right_items, threshold)`` turns the match list into a one-to-one mapping: the best pair, both
   its items removed, and again (``grid.assign_of_hits``), assigned on the device.
 
+* ``plugin.groups(left_items, right_items, threshold)`` closes the match list transitively: the connected components of
+  the pairs scoring ``>= threshold`` (``grid.groups_of_hits``), linked on the device; ``plugin.clusters(items, threshold)``
+  is the self-join -- near-duplicate clusters inside one list.
+
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
 """
@@ -319,6 +323,37 @@ class _IntersectionVsUnion:
         rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
         return grid.jaccard_raw_assign(lt, rt, threshold, prune=prune)
 
+    def groups(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+               prune: bool = True, same: bool = False) -> grid.MatchGroups:
+        """``grid.groups_of_hits`` of ``raw_grid(left_items, right_items, threshold)``: the items of both lists grouped by
+        the pairs scoring ``>= threshold``, closed transitively (left item k is node k, right item k node N + k; with
+        ``same`` both lists are the same items in one node space).  The hits are linked on the device, unsorted, and only
+        the labels come back; where wide items send part of the grid through the general kernels the merged host list goes
+        through ``grid.group_hits``."""
+        from .. import wide
+
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_rows = [list(set_operand(v)) for v in left_items]
+        r_rows = [list(set_operand(v)) for v in right_items]
+        n_l, n_r = len(l_rows), len(r_rows)
+        layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
+        if not l_rows or not r_rows:
+            return grid.MatchGroups(np.arange(sum(layout[1]), dtype=np.int32), *layout)
+        if wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]) is not None:
+            hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
+            return grid.MatchGroups(grid.group_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float("-inf"), device=dev), *layout)
+        vocab = tables.Vocabulary()
+        width = tables.pick_width(max((len(set(r)) for r in l_rows), default=1), max((len(set(r)) for r in r_rows), default=1))
+        lt = tables.SetTable.from_rows(l_rows, "left", dev, vocab, width=width)
+        rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
+        return grid.jaccard_raw_groups(lt, rt, threshold, prune=prune, same=same)
+
+    def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> List[np.ndarray]:
+        """Near-duplicate clusters inside ONE list (dedupe): the self-join's groups of at least two items, each an
+        ascending array of positions in ``items``, ordered by their smallest member."""
+        return [members[0] for members in self.groups(items, items, threshold, device=device, prune=prune, same=True).members(2)]
+
 
 class _FuzzyMatch:
     __name__ = "fuzzy_match"
@@ -470,6 +505,33 @@ class _FuzzyMatch:
                                     len(r_ops), device=dev)
         lt, rt = tables.encode_strings(l_ops, r_ops, dev)
         return grid.indel_raw_assign(lt, rt, threshold, prune=prune)
+
+    def groups(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+               prune: bool = True, same: bool = False) -> grid.MatchGroups:
+        """``grid.groups_of_hits`` of ``raw_grid(left_items, right_items, threshold)``: the items of both lists grouped by
+        the pairs scoring ``>= threshold``, closed transitively (left item k is node k, right item k node N + k; with
+        ``same`` both lists are the same items in one node space).  The hits are linked on the device, unsorted, and only
+        the labels come back; where wide items send part of the grid through the general kernels the merged host list goes
+        through ``grid.group_hits``."""
+        from .. import wide
+
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        n_l, n_r = len(l_ops), len(r_ops)
+        layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
+        if not l_ops or not r_ops:
+            return grid.MatchGroups(np.arange(sum(layout[1]), dtype=np.int32), *layout)
+        if wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]) is not None:
+            hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
+            return grid.MatchGroups(grid.group_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float("-inf"), device=dev), *layout)
+        lt, rt = tables.encode_strings(l_ops, r_ops, dev)
+        return grid.indel_raw_groups(lt, rt, threshold, prune=prune, same=same)
+
+    def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> List[np.ndarray]:
+        """Near-duplicate clusters inside ONE list (rapidfuzz users' dedupe): the self-join's groups of at least two items,
+        each an ascending array of positions in ``items``, ordered by their smallest member."""
+        return [members[0] for members in self.groups(items, items, threshold, device=device, prune=prune, same=True).members(2)]
 
 
 intersection_vs_union = _IntersectionVsUnion()

@@ -1152,3 +1152,199 @@ def jaccard_levels_assign(left: SetTable, right: SetTable, threshold: float, cat
     pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
                                   index=index, defer=True)
     return _assign_pending(pending, left, right, route, stats)
+
+
+# ------------------------------------------------------------------------------- match groups
+def _check_forest(start, nodes: int) -> np.ndarray:
+    forest = np.asarray(start)
+    if forest.shape != (nodes,) or not np.issubdtype(forest.dtype, np.integer):
+        raise ValueError(f"start must be an integer array of {nodes} labels")
+    if nodes and ((forest < 0).any() or (forest > np.arange(nodes)).any()):
+        raise ValueError("start: every label[v] must lie in [0, v]")
+    return forest.astype(np.int32)
+
+
+def _list_nodes(hits: Hits, left_base: int, right_base: int, nodes: int, what: str):
+    """The two node columns of a list (int64), range-checked: ALL records, whatever their score."""
+    i, j = np.asarray(hits.i, dtype=np.int64), np.asarray(hits.j, dtype=np.int64)
+    left_base, right_base = int(left_base), int(right_base)
+    if left_base < 0 or right_base < 0 or left_base > nodes or right_base > nodes:
+        raise ValueError(f"{what}: a list's bases must lie in [0, nodes]")
+    if len(i) and (int(i.min()) < 0 or int(j.min()) < 0):
+        raise ValueError(f"{what}: ids must be >= 0")
+    if len(i) and (int(i.max()) + left_base >= nodes or int(j.max()) + right_base >= nodes):
+        raise ValueError(f"{what}: a record reaches beyond the {nodes} nodes")
+    return i + left_base, j + right_base
+
+
+def groups_of_hits(lists, nodes: int, min_score: float = 0.0, start=None) -> np.ndarray:
+    """The definition of match groups.  ``lists = [(Hits, left_base, right_base), ...]``: record ``(score, i, j)`` is an edge
+    between node ``left_base + i`` and node ``right_base + j`` if ``score >= min_score`` (a NaN links nothing).  Returns
+    int32 ``label[nodes]``: the smallest node of every node's connected component over all lists together; a node no
+    record touches is its own label.  ``start``: a forest to link into (``0 <= start[v] <= v``, e.g. an earlier result).
+    Plain union-find on the host; the order of records and lists does not matter."""
+    nodes = int(nodes)
+    if nodes < 0:
+        raise ValueError("groups_of_hits: nodes must be >= 0")
+    parent = list(range(nodes)) if start is None else _check_forest(start, nodes).tolist()
+
+    def find(v: int) -> int:
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+
+    for hits, left_base, right_base in lists:
+        u, v = _list_nodes(hits, left_base, right_base, nodes, "groups_of_hits")
+        keep = np.asarray(hits.score, dtype=np.float64) >= min_score
+        for a, b in zip(u[keep].tolist(), v[keep].tolist()):
+            a, b = find(a), find(b)
+            if a != b:
+                parent[max(a, b)] = min(a, b)  # (the smaller root stays: the last root is the component's minimum)
+    return np.fromiter((find(v) for v in range(nodes)), dtype=np.int32, count=nodes)
+
+
+def _records_to_device(hits: Hits, dev) -> Optional[torch.Tensor]:
+    """A host list as device records (16 bytes each: score, i, j), in the order given."""
+    n = len(hits)
+    if n == 0:
+        return None
+    host = np.empty((n, 2), dtype=np.float64)
+    host[:, 0] = hits.score
+    ij = host.view(np.int32).reshape(n, 4)
+    ij[:, 2], ij[:, 3] = hits.i, hits.j
+    return torch.from_numpy(host).to(dev)
+
+
+def group_lists_device(entries, nodes: int, min_score: float, dev, start=None, stats: Optional[list] = None) -> np.ndarray:
+    """One ``nsm_group_hits`` call over device lists and one D2H copy of the ``nodes`` labels.  ``entries``: per list
+    ``(records pointer, n, left_base, left_ids, right_base, right_ids)``."""
+    fn = _lib.entry("nsm_group_hits")
+    nodes = int(nodes)
+    if nodes == 0:
+        if stats is not None:
+            stats[:] = [0, 0]
+        return np.zeros(0, dtype=np.int32)
+    flags = 0
+    if start is None:
+        label = torch.empty(nodes, dtype=torch.int32, device=dev)
+    else:
+        label = torch.from_numpy(_check_forest(start, nodes)).to(dev)
+        flags = _lib.GROUP_CONTINUE
+    lists = (_lib.NsmHitList * max(1, len(entries)))()
+    for slot, (ptr, n, left_base, left_ids, right_base, right_ids) in zip(lists, entries):
+        slot.hits, slot.n = (ptr if n else None), int(n)
+        slot.left_base, slot.left_ids, slot.right_base, slot.right_ids = int(left_base), int(left_ids), int(right_base), int(right_ids)
+    st = torch.zeros(2, dtype=torch.int64, device=dev) if stats is not None else None
+    status = fn(lists, len(entries), nodes, float(min_score), flags, label.data_ptr(), st.data_ptr() if st is not None else None,
+                torch.cuda.current_stream(dev).cuda_stream)
+    if status == 10001:
+        raise ValueError("nsm_group_hits: " + _lib.load().nsm_last_error().decode("utf-8", "replace"))
+    _lib.check(status, "nsm_group_hits")
+    if stats is not None:
+        stats[:] = [int(v) for v in st.tolist()]
+    return label.cpu().numpy()
+
+
+def group_hits(lists, nodes: int, min_score: float = 0.0, start=None, device=None, stats: Optional[list] = None) -> np.ndarray:
+    """``groups_of_hits(lists, nodes, min_score, start)`` on the device for host hit lists: upload (in any order), one
+    ``nsm_group_hits`` call over all lists, one D2H copy of ``nodes`` words.  Ids must be ``>= 0`` and every record must
+    stay inside the nodes (``ValueError``).  ``stats`` receives [records with score >= min_score, hooks made]."""
+    dev = _require_gpu("cuda" if device is None else device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    nodes = int(nodes)
+    if nodes < 0:
+        raise ValueError("group_hits: nodes must be >= 0")
+    entries, keep = [], []
+    for hits, left_base, right_base in lists:
+        _list_nodes(hits, left_base, right_base, nodes, "group_hits")
+        recs = _records_to_device(hits, dev)
+        keep.append(recs)
+        # (any id that stays inside the nodes is a node: the id counts reach to the end of the node space)
+        entries.append((recs.data_ptr() if recs is not None else 0, len(hits), int(left_base), nodes - int(left_base),
+                        int(right_base), nodes - int(right_base)))
+    return group_lists_device(entries, nodes, min_score, dev, start, stats)
+
+
+@dataclass
+class MatchGroups:
+    """Match groups over one or more cohorts that share a node space: cohort ``c``'s item ``k`` is node ``bases[c] + k``."""
+
+    label: np.ndarray  # int32 [nodes]: the smallest node of every node's group
+    bases: tuple  # per cohort: its first node
+    cohort_sizes: tuple  # per cohort: its number of items (ids)
+
+    def of(self, c: int) -> np.ndarray:
+        """The labels of cohort ``c``'s items."""
+        return self.label[self.bases[c]: self.bases[c] + self.cohort_sizes[c]]
+
+    def sizes(self) -> np.ndarray:
+        """Per node the number of nodes it labels: the group's size at its smallest node, 0 elsewhere."""
+        return np.bincount(self.label, minlength=len(self.label))
+
+    def members(self, min_size: int = 2):
+        """The groups of at least ``min_size`` nodes, ordered by label, each as a tuple of per-cohort item-index arrays."""
+        order = np.argsort(self.label, kind="stable")  # (within a group: nodes ascending)
+        sorted_label = self.label[order]
+        starts = np.r_[0, np.flatnonzero(sorted_label[1:] != sorted_label[:-1]) + 1, len(order)] if len(order) else np.zeros(1, int)
+        out = []
+        for a, b in zip(starts[:-1].tolist(), starts[1:].tolist()):
+            if b - a < min_size:
+                continue
+            nodes = order[a:b]
+            out.append(tuple((nodes[(nodes >= base) & (nodes < base + size)] - base).astype(np.int64)
+                             for base, size in zip(self.bases, self.cohort_sizes)))
+        return out
+
+
+def _groups_pending(pending: PendingHits, left, right, same: bool, min_score, stats: Optional[list]) -> MatchGroups:
+    # (nsm_group_hits indexes the labels by caller id)
+    ids_l, ids_r = _id_count(left.orig, left.n, "groups"), _id_count(right.orig, right.n, "groups")
+    if same:  # one node space: left item k and right item k are the same node
+        nodes, bases, sizes = max(ids_l, ids_r), (0,), (max(ids_l, ids_r),)
+    else:
+        nodes, bases, sizes = ids_l + ids_r, (0, ids_l), (ids_l, ids_r)
+    floor = float("-inf") if min_score is None else float(min_score)
+    # the buffer goes in UNSORTED: components need no order
+    label = group_lists_device([(pending.buf.records.data_ptr(), pending.n, 0, ids_l, bases[-1], ids_r)], nodes, floor,
+                               pending.buf.records.device, None, stats)
+    return MatchGroups(label, bases, sizes)
+
+
+def indel_raw_groups(left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
+                     two_stage: bool = True, pack: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
+                     stats: Optional[list] = None) -> MatchGroups:
+    """``groups_of_hits([(indel_raw_grid(left, right, threshold, ...), 0, right's base)], ...)``: the grid's hits stay in
+    their device buffer, unsorted, are linked there, and only the labels cross to the host.  ``same``: both tables
+    describe the same items (a self-join), numbered in ONE node space -- near-duplicate clusters.  ``min_score``: only
+    records scoring at least that link (None: every hit of the grid)."""
+    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True)
+    return _groups_pending(pending, left, right, same, min_score, stats)
+
+
+def jaccard_raw_groups(left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
+                       index: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
+                       stats: Optional[list] = None) -> MatchGroups:
+    """``intersection_vs_union`` counterpart of ``indel_raw_groups``."""
+    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True)
+    return _groups_pending(pending, left, right, same, min_score, stats)
+
+
+def indel_levels_groups(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, threshold: float,
+                        category_mode: int = _lib.CAT_NONE, prune: bool = True, capacity: Optional[int] = None, same: bool = False,
+                        min_score: Optional[float] = None, stats: Optional[list] = None, **grid_options) -> MatchGroups:
+    """``groups_of_hits`` of ``indel_levels_grid(...)``'s hits without them leaving the device (``grid_options``: the grid's
+    other keywords)."""
+    pending = indel_levels_grid(left, left_strings, right, right_strings, threshold, category_mode=category_mode, prune=prune,
+                                capacity=capacity, defer=True, **grid_options)
+    return _groups_pending(pending, left, right, same, min_score, stats)
+
+
+def jaccard_levels_groups(left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE,
+                          prune: bool = True, capacity: Optional[int] = None, index: Optional[bool] = None, same: bool = False,
+                          min_score: Optional[float] = None, stats: Optional[list] = None) -> MatchGroups:
+    """``intersection_vs_union`` counterpart of ``indel_levels_groups``."""
+    pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
+                                  index=index, defer=True)
+    return _groups_pending(pending, left, right, same, min_score, stats)

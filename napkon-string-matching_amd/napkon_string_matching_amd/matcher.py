@@ -102,6 +102,14 @@ class Matcher:
             score_threshold=self.config[CONFIG_FIELD_MATCHING][CONFIG_VARIABLE_THRESHOLD],
         )
 
+    def match_groups(self, min_score: Optional[float] = None, id_reference: Optional[Mapping] = None) -> Mapping:
+        """The run's results as a ``Mapping``: the rows of ALL cohort pairs scoring ``>= min_score`` (None: every row)
+        closed transitively into entries ``{id: {cohort: [identifier, ...]}}`` (``groups.mapping_of_results``; linked on the
+        device).  ``id_reference``: a mapping whose entry ids are kept where its members are found again."""
+        from .groups import mapping_of_results
+
+        return mapping_of_results(self.results, min_score=min_score, id_reference=id_reference)
+
     # ---- result consumers (matcher.py:286-331)
     def _analyse(self) -> Dict[str, Dict[str, str]]:
         gecco_prefix = "gec_"

@@ -2,8 +2,9 @@
 
 Only the lookups the match loop touches are provided (reference: napkon_string_matching/types/
 mapping.py:66-72 ``get_group_combination``, :173-176 ``filter_by_group``, :200-203 ``get_filtered``,
-:281-289 ``get_all_mapping_for_groups``); mapping curation (add / update / merge, Excel import)
-is out of scope for this package.
+:281-289 ``get_all_mapping_for_groups``).  Building a mapping from match results -- merging pairs that share an item
+into entries, the reference's ``update_mapping`` -- is ``groups.mapping_of_results`` / ``Matcher.match_groups``; the rest
+of mapping curation (hand edits, Excel import) is out of scope for this package.
 """
 from __future__ import annotations
 
