@@ -27,10 +27,11 @@
  * Conventions
  *   - every pointer marked "device" is HBM memory owned by the caller (the Python host keeps them
  *     as torch tensors); the library keeps no pointer after a call returns and allocates no device memory of
- *     its own that outlives a call (the builders' scratch is stream-ordered and freed inside the call; so is that of
- *     the large two-stage nsm_indel_raw_grid, 64 bytes per left row and a second kernel, neither of which a call
- *     that is being captured into a graph uses; the one grid that wants scratch beyond the call's own --
- *     nsm_indel_levels_grid -- takes it from the caller as `workspace`);
+ *     its own that outlives a call, with ONE exception: the large two-stage nsm_indel_raw_grid keeps the buffer of its
+ *     pre-pass (64 bytes per left row of the largest table seen) per device and stream until nsm_release(); a call that
+ *     is being captured into a graph uses neither the buffer nor the pre-pass.  The builders' scratch is stream-ordered
+ *     and freed inside the call; the one grid that wants scratch beyond the call's own -- nsm_indel_levels_grid --
+ *     takes it from the caller as `workspace`;
  *   - calls are asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream);
  *   - return value: 0 on success, otherwise a hipError_t or one of the NSM_E_* codes below;
  *     nsm_last_error() gives a thread-local message;
@@ -315,10 +316,13 @@ int nsm_jaccard_levels_grid(const nsm_set_table* left, const nsm_set_table* righ
 
 /* RAW Indel ratio: ((1 - (la+lb-2*LCS)/(la+lb)) * 100) / 100, 0 when either string is empty.
  * With NSM_FLAG_PRUNE and both tables' hist16 (the two-stage filter), a grid that is large enough -- or any with
- * NSM_FLAG_PACK, none with NSM_FLAG_NO_PACK -- is two kernels: a pre-pass that codes the scan's left operand words into
- * stream-ordered scratch of 64 bytes per left row (hipMallocAsync / hipFreeAsync on `stream`, freed inside the call), then
- * the scan.  A call on a stream that is being captured into a graph allocates nothing and is the one scan kernel, and so
- * is a call whose allocation fails.  The hits are the same either way. */
+ * NSM_FLAG_PACK, none with NSM_FLAG_NO_PACK -- is two kernels: a pre-pass that codes the scan's left operand words, 64 bytes
+ * per left row, then the scan.  The rows live in a buffer the library keeps per (current device, `stream`): allocated by the
+ * first such call (hipMalloc), grown (hipFree + hipMalloc, which wait for the device) when a table has more left rows than
+ * any before, freed by nsm_release(stream) / nsm_release_all().  Only the allocation is kept: the pre-pass codes the rows
+ * again in every call, and calls on one stream share the buffer in the stream's order.  Calls that overlap on DIFFERENT
+ * streams have a buffer each.  A call on a stream that is being captured into a graph allocates nothing and is the one scan
+ * kernel, and so is a call whose allocation fails.  The hits are the same either way. */
 int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table* right, double threshold,
                        uint32_t flags, nsm_hit* hits, uint64_t capacity,
                        unsigned long long* hit_count, void* stream);
@@ -513,7 +517,9 @@ int nsm_jaccard_levels_pairs(const nsm_set_table* left, const nsm_set_table* rig
                              int32_t left_ids, const int32_t* right_row, int32_t right_ids, nsm_hit* pairs, uint64_t n_pairs,
                              void* stream);
 
-/* Destroy the side stream and events the library created for `stream` on the current device.  The caller makes sure no nsm_indel_levels_grid work is still queued on that stream.  Returns 0. */
+/* Destroy the side stream and events the library created for `stream` on the current device, and free the packed-row buffer
+ * nsm_indel_raw_grid keeps for it.  The caller makes sure no nsm_indel_levels_grid or nsm_indel_raw_grid work is still queued
+ * on that stream.  Everything is created again by the next call that wants it.  Returns 0. */
 int nsm_release(void* stream);
 int nsm_release_all(void); /* the same for every stream of every device */
 

@@ -445,6 +445,7 @@ extern "C" int nsm_release(void* stream) {
   using namespace nsm;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
+  release_pack_scratch(dev, stream, false);
   std::lock_guard<std::mutex> lock(g_side_mu);
   auto it = g_sides.find(std::make_pair(dev, stream));
   if (it != g_sides.end()) {
@@ -456,6 +457,7 @@ extern "C" int nsm_release(void* stream) {
 
 extern "C" int nsm_release_all(void) {
   using namespace nsm;
+  release_pack_scratch(0, nullptr, true);
   std::lock_guard<std::mutex> lock(g_side_mu);
   for (auto& kv : g_sides) destroy_side(kv.second);  // (streams and events of another device are destroyed from here just as well)
   g_sides.clear();

@@ -22,6 +22,10 @@
 #include "nsm_common.hpp"
 #include "indel_score.hpp"
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 namespace nsm {
 
 // Table columns travel as __restrict__ kernel arguments so that the wave-uniform left side is
@@ -407,6 +411,49 @@ static int pick_rows_per_chunk(int n_left, int n_tiles) {
   return static_cast<int>(rows);
 }
 
+// The packed rows of the two-stage scan (below): ONE buffer per (device, stream), kept between calls and grown on demand;
+// nsm_release() / nsm_release_all() free it with the split path's per-stream state.  Only the allocation is kept, never its
+// contents: the pre-pass writes every row a call's scan reads, every call.  Calls on one stream run in stream order, so the
+// pre-pass of the next call overwrites the rows behind the scan of the one before; growing frees the old buffer with hipFree,
+// which waits for the device.  A stream-ordered allocation per call (hipMallocAsync / hipFreeAsync) left the stream idle
+// for ~6 us behind every scan, DESIGN 6.  nullptr = no buffer (the caller scans unpacked), never an error.
+struct PackScratch {
+  void* rows = nullptr;
+  size_t bytes = 0;
+};
+static std::mutex g_pack_mu;
+static std::map<std::pair<int, void*>, PackScratch> g_pack;
+
+static void* pack_scratch(hipStream_t stream, size_t bytes) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(g_pack_mu);
+  PackScratch& w = g_pack[std::make_pair(dev, static_cast<void*>(stream))];
+  if (w.bytes >= bytes && w.rows) return w.rows;
+  if (w.rows) (void)hipFree(w.rows);
+  w.rows = nullptr;
+  w.bytes = 0;
+  if (hipMalloc(&w.rows, bytes) != hipSuccess) {
+    (void)hipGetLastError();  // (cleared: the call does not fail for want of an optimisation)
+    w.rows = nullptr;
+    return nullptr;
+  }
+  w.bytes = bytes;
+  return w.rows;
+}
+
+void release_pack_scratch(int dev, void* stream, bool all) {
+  std::lock_guard<std::mutex> lock(g_pack_mu);
+  for (auto it = g_pack.begin(); it != g_pack.end();) {
+    if (all || it->first == std::make_pair(dev, stream)) {
+      if (it->second.rows) (void)hipFree(it->second.rows);
+      it = g_pack.erase(it);
+    } else {
+      ++it;
+    }
+  }
+}
+
 int indel_raw_wide(const nsm_str_table* left, const nsm_str_table* right, double threshold, uint32_t flags,
                    nsm_hit* hits, uint64_t capacity, unsigned long long* hit_count, hipStream_t stream);
 
@@ -489,8 +536,8 @@ extern "C" int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table
     const uint32_t* lh32 = reinterpret_cast<const uint32_t*>(left->hist);
     const uint32_t* rh32 = reinterpret_cast<const uint32_t*>(right->hist);
 #if NSM_C3C_FP4
-    // The packed path: the left operand words of the scan made once per call (c3c_pack_left_kernel) in stream-ordered
-    // scratch of 64 bytes a left row, freed behind the scan.  Forced by NSM_FLAG_PACK, barred by NSM_FLAG_NO_PACK, else by
+    // The packed path: the left operand words of the scan made once per call (c3c_pack_left_kernel), 64 bytes a left row, in
+    // the buffer kept for this device and stream (pack_scratch above).  Forced by NSM_FLAG_PACK, barred by NSM_FLAG_NO_PACK, else by
     // size: the pre-pass is a launch plus work per left row, the saving is per pair scanned.  A call that is being captured
     // allocates nothing and runs the unpacked kernel, and so does a call whose allocation fails.
     bool pack = !(flags & NSM_FLAG_NO_PACK) &&
@@ -500,11 +547,7 @@ extern "C" int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table
       if (hipStreamIsCapturing(hs, &capture) != hipSuccess) capture = hipStreamCaptureStatusNone;
       pack = capture == hipStreamCaptureStatusNone;
     }
-    void* packed = nullptr;
-    if (pack && hipMallocAsync(&packed, static_cast<size_t>(left->n) * kC3cPackedRow, hs) != hipSuccess) {
-      (void)hipGetLastError();  // (cleared: the call does not fail for want of an optimisation)
-      packed = nullptr;
-    }
+    void* packed = pack ? pack_scratch(hs, static_cast<size_t>(left->n) * kC3cPackedRow) : nullptr;
     if (packed) {
       const long long units = 2ll * left->n;
       hipLaunchKernelGGL(c3c_pack_left_kernel, dim3(static_cast<unsigned>((units + kBlock - 1) / kBlock)), dim3(kBlock), 0, hs,
@@ -512,9 +555,7 @@ extern "C" int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table
       hipLaunchKernelGGL((indel_raw_coarse_kernel<NSM_C3C_NT, NSM_C3C_CAP, true>), grid, dim3(kBlock), c3c_lds_bytes(), hs,
                          left->codes, left->len, left->len_start, left->orig, lh32, right->codes, right->len, right->orig,
                          rh32, hits, hit_count, p, static_cast<const char*>(packed));
-      const int st = hip_status(hipGetLastError(), "indel_raw_coarse_kernel launch (packed)");
-      const int fst = hip_status(hipFreeAsync(packed, hs), "nsm_indel_raw_grid: packed rows");
-      return st ? st : fst;
+      return hip_status(hipGetLastError(), "indel_raw_coarse_kernel launch (packed)");
     }
 #endif
     hipLaunchKernelGGL((indel_raw_coarse_kernel<NSM_C3C_NT, NSM_C3C_CAP, false>), grid, dim3(kBlock), c3c_lds_bytes(), hs,

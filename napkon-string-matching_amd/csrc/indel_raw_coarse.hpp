@@ -39,7 +39,7 @@
 //           (NSM_C3C_FP4_PERM=0: two adds, two ands, a shift and an or a word and MFMA; slower)
 //   packed  the left words depend on the row alone, and a row is scanned by every right wave that fits its class: about
 //           800 times a launch of configs[2].  Where the grid is large enough (NSM_C3C_PACK_MIN_PAIRS; NSM_FLAG_PACK /
-//           NSM_FLAG_NO_PACK) c3c_pack_left_kernel makes them ONCE per call, 64 bytes a row in stream-ordered scratch,
+//           NSM_FLAG_NO_PACK) c3c_pack_left_kernel makes them ONCE per call, 64 bytes a row in the stream's kept buffer,
 //           and the scan is indel_raw_coarse_kernel<.., true>: a lane loads its two operand fragments, 2 x 16 bytes, and
 //           the chains read the loaded registers (no A fragment is made, none is copied; the two sets still swap from
 //           block to block).  A captured call never packs.  DESIGN 4.3 step 12, profiles/c3_pack_ab.txt.

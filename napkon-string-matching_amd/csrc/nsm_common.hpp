@@ -16,6 +16,8 @@ constexpr uint8_t kNever = 255;      // "no count can reach the threshold"
 
 void set_error(const char* fmt, ...);
 int hip_status(hipError_t err, const char* what);
+// indel_raw.hip: free the packed-row buffer kept for (dev, stream), or every one (nsm_release / nsm_release_all)
+void release_pack_scratch(int dev, void* stream, bool all);
 
 // Host-side dispatch on a run-time property the kernels are templates over: f(tag) with the tag's ::value as the
 // template argument, one spelled-out launch per kernel family.  The entries' checks have already refused any other value.

@@ -167,7 +167,7 @@ def indel_raw_grid(
     ``two_stage=False``: the 32-bucket histogram test for every pair even when both tables carry the ``hist16``
     column that selects the two-stage kernel (A/B runs, tests; same hits).
     ``pack``: None = the library decides whether the two-stage scan codes its left operand words once per call (a
-    pre-pass into stream-ordered scratch, where the grid is large enough); True = force it, False = never (same hits)."""
+    pre-pass into a buffer the library keeps per stream, where the grid is large enough); True = force it, False = never (same hits)."""
     lib = _lib.load()
     ls, rs = left.struct(), right.struct()
     flags = ((_lib.FLAG_PRUNE if prune else 0) | (0 if two_stage else _lib.FLAG_ONE_STAGE)
