@@ -19,6 +19,7 @@ FLAG_PARK = 16  # nsm_indel_levels_grid, strings > 64 code units: the round-2 pa
 BUILD_PARTITION, BUILD_VALIDATE, BUILD_SORT = 1, 2, 4
 ASSIGN_ROUNDS_ONLY, ASSIGN_STREAM_ONLY = 1, 2  # nsm_assign_hits (include/nsm_hip_assign.h): one stage only (A/B runs, tests)
 GROUP_CONTINUE = 1  # nsm_group_hits (include/nsm_hip_groups.h): `label` holds a forest, link the lists into it
+SPAN_NO_COMPACT = 1  # nsm_span_hits (include/nsm_hip_span.h): every round visits every edge (accepted; the only route)
 CAT_NONE, CAT_INTERSECT, CAT_INTERSECT_OR_BOTH_EMPTY = 0, 1, 2
 
 c_i32p = ctypes.c_void_p  # device pointers travel as integers
@@ -143,6 +144,9 @@ ASSIGN_EXPORTS = ("nsm_assign_hits",)
 # include/nsm_hip_groups.h, likewise
 GROUP_EXPORTS = ("nsm_group_hits",)
 
+# include/nsm_hip_span.h, likewise
+SPAN_EXPORTS = ("nsm_span_hits",)
+
 _lib = None
 
 
@@ -240,7 +244,9 @@ def load() -> ctypes.CDLL:
     assign_args = {"nsm_assign_hits": [vp, c_u64, i32, i32, u32, vp, vp, vp, vp]}
     # lists (host), n_lists, nodes, min_score, flags, label, stats, stream
     group_args = {"nsm_group_hits": [P(NsmHitList), i32, i32, ctypes.c_double, u32, vp, vp, vp]}
-    for names, args in ((ASSIGN_EXPORTS, assign_args), (GROUP_EXPORTS, group_args)):
+    # lists (host), n_lists, nodes, min_score, flags, forest, forest_count, label, stats, stream
+    span_args = {"nsm_span_hits": [P(NsmHitList), i32, i32, ctypes.c_double, u32, vp, vp, vp, vp, vp]}
+    for names, args in ((ASSIGN_EXPORTS, assign_args), (GROUP_EXPORTS, group_args), (SPAN_EXPORTS, span_args)):
         for name in names:
             try:
                 fn = getattr(lib, name)

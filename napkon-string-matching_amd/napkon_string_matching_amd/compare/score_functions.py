@@ -32,6 +32,10 @@ Same names, call convention and error behaviour as the reference's
   the pairs scoring ``>= threshold`` (``grid.groups_of_hits``), linked on the device; ``plugin.clusters(items, threshold)``
   is the self-join -- near-duplicate clusters inside one list.
 
+* ``plugin.forest(left_items, right_items, threshold)`` is the groups at EVERY threshold ``>= threshold`` from one run: the
+  merge forest (``grid.forest_of_hits``), spanned on the device -- ``cut(t)``, ``ladder(thresholds)``, ``merge_score(a, b)``;
+  ``plugin.cluster_tree(items, threshold)`` is the self-join.
+
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
 """
@@ -354,6 +358,38 @@ class _IntersectionVsUnion:
         ascending array of positions in ``items``, ordered by their smallest member."""
         return [members[0] for members in self.groups(items, items, threshold, device=device, prune=prune, same=True).members(2)]
 
+    def forest(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+               prune: bool = True, same: bool = False) -> grid.MergeForest:
+        """``grid.forest_of_hits`` of ``raw_grid(left_items, right_items, threshold)``: the merge forest of the pairs scoring
+        ``>= threshold`` -- ``groups`` at every threshold from there up in one run (``cut(t)``), with the score that joined
+        two items (``merge_score``) and the group statistics of a whole ladder (``ladder``).  Nodes as in ``groups``.  The
+        hits are spanned on the device and only the forest comes back; where wide items send part of the grid through the
+        general kernels the merged host list goes through ``grid.span_hits``."""
+        from .. import wide
+
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_rows = [list(set_operand(v)) for v in left_items]
+        r_rows = [list(set_operand(v)) for v in right_items]
+        n_l, n_r = len(l_rows), len(r_rows)
+        layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
+        if not l_rows or not r_rows:
+            return grid.forest_of_hits([], sum(layout[1]), float(threshold), *layout)
+        if wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]) is not None:
+            hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
+            return grid.span_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float(threshold), device=dev, bases=layout[0],
+                                  cohort_sizes=layout[1])
+        vocab = tables.Vocabulary()
+        width = tables.pick_width(max((len(set(r)) for r in l_rows), default=1), max((len(set(r)) for r in r_rows), default=1))
+        lt = tables.SetTable.from_rows(l_rows, "left", dev, vocab, width=width)
+        rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
+        return grid.jaccard_raw_forest(lt, rt, threshold, prune=prune, same=same)
+
+    def cluster_tree(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> grid.MergeForest:
+        """The single-linkage tree of ONE list: the self-join's merge forest (node k is ``items[k]``); ``cut(t).members(2)``
+        are ``clusters(items, t)`` for every ``t >= threshold``."""
+        return self.forest(items, items, threshold, device=device, prune=prune, same=True)
+
 
 class _FuzzyMatch:
     __name__ = "fuzzy_match"
@@ -532,6 +568,34 @@ class _FuzzyMatch:
         """Near-duplicate clusters inside ONE list (rapidfuzz users' dedupe): the self-join's groups of at least two items,
         each an ascending array of positions in ``items``, ordered by their smallest member."""
         return [members[0] for members in self.groups(items, items, threshold, device=device, prune=prune, same=True).members(2)]
+
+    def forest(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+               prune: bool = True, same: bool = False) -> grid.MergeForest:
+        """``grid.forest_of_hits`` of ``raw_grid(left_items, right_items, threshold)``: the merge forest of the pairs scoring
+        ``>= threshold`` -- ``groups`` at every threshold from there up in one run (``cut(t)``), with the score that joined
+        two items (``merge_score``) and the group statistics of a whole ladder (``ladder``).  Nodes as in ``groups``.  The
+        hits are spanned on the device and only the forest comes back; where wide items send part of the grid through the
+        general kernels the merged host list goes through ``grid.span_hits``."""
+        from .. import wide
+
+        grid.check_thresholds([threshold])
+        dev = device or _device()
+        l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        n_l, n_r = len(l_ops), len(r_ops)
+        layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
+        if not l_ops or not r_ops:
+            return grid.forest_of_hits([], sum(layout[1]), float(threshold), *layout)
+        if wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]) is not None:
+            hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
+            return grid.span_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float(threshold), device=dev, bases=layout[0],
+                                  cohort_sizes=layout[1])
+        lt, rt = tables.encode_strings(l_ops, r_ops, dev)
+        return grid.indel_raw_forest(lt, rt, threshold, prune=prune, same=same)
+
+    def cluster_tree(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> grid.MergeForest:
+        """The single-linkage tree of ONE list: the self-join's merge forest (node k is ``items[k]``); ``cut(t).members(2)``
+        are ``clusters(items, t)`` for every ``t >= threshold``."""
+        return self.forest(items, items, threshold, device=device, prune=prune, same=True)
 
 
 intersection_vs_union = _IntersectionVsUnion()

@@ -1348,3 +1348,269 @@ def jaccard_levels_groups(left: SetTable, right: SetTable, threshold: float, cat
     pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
                                   index=index, defer=True)
     return _groups_pending(pending, left, right, same, min_score, stats)
+
+
+# ------------------------------------------------------------------------------- merge forests
+def _score_key(score: np.ndarray) -> np.ndarray:
+    """``nsm_sort_hits``'s K(score): ascending in this uint64 is descending in the score, by its bits (+0.0 before -0.0)."""
+    bits = np.ascontiguousarray(score, dtype=np.float64).view(np.uint64)
+    flip = np.where(bits >> np.uint64(63), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64(1) << np.uint64(63))
+    return ~(bits ^ flip)
+
+
+def _check_cut(threshold, min_score: float, what: str) -> float:
+    t = float(threshold)
+    if not t >= min_score:
+        raise ValueError(f"{what}: threshold {threshold!r} is not >= the forest's min_score {min_score!r}; "
+                         "the forest does not know what links below it")
+    return t
+
+
+@dataclass
+class MergeForest:
+    """The merge forest of hit lists over one node space: the maximum spanning forest under the canonical record order,
+    i.e. the single-linkage hierarchy.  Record ``k`` joined the groups of nodes ``u[k] < v[k]`` at ``score[k]``; cut at any
+    threshold ``>= min_score`` it gives the match groups at that threshold.  Cohort ``c``'s item ``k`` is node
+    ``bases[c] + k``, as in ``MatchGroups``."""
+
+    score: np.ndarray  # float64, canonical order (score descending by its bits, then u, then v)
+    u: np.ndarray  # int32, the smaller node
+    v: np.ndarray  # int32, the larger node
+    nodes: int
+    bases: tuple
+    cohort_sizes: tuple
+    min_score: float
+
+    def __len__(self) -> int:
+        return int(self.score.shape[0])
+
+    def as_tuples(self):
+        return list(zip(self.score.tolist(), self.u.tolist(), self.v.tolist()))
+
+    def hits(self) -> Hits:
+        """The records as a hit list over the whole node space (``left_base = right_base = 0``): what
+        ``forest(forest(A) u B)`` feeds back."""
+        return Hits(self.score, self.u, self.v)
+
+    def cut(self, threshold: float) -> MatchGroups:
+        """The match groups at ``threshold``: ``groups_of_hits`` of the lists the forest was built from, label for label.
+        ``ValueError`` below ``min_score``, where the forest does not know."""
+        t = _check_cut(threshold, self.min_score, "MergeForest.cut")
+        return MatchGroups(groups_of_hits([(self.hits(), 0, 0)], self.nodes, t), self.bases, self.cohort_sizes)
+
+    def ladder(self, thresholds) -> dict:
+        """Per threshold (any order, each ``>= min_score``): ``components`` (groups of any size), ``groups`` (of at least
+        two nodes), ``grouped`` (nodes in such groups) and ``largest`` (the largest group's size) -- the statistics of
+        ``cut(t)``, for the whole ladder in ONE pass over the records, int64 arrays in the thresholds' order."""
+        ts = np.asarray([_check_cut(t, self.min_score, "MergeForest.ladder") for t in np.asarray(thresholds, dtype=np.float64).ravel()])
+        out = {name: np.zeros(len(ts), dtype=np.int64) for name in ("components", "groups", "grouped", "largest")}
+        parent, size = list(range(self.nodes)), [1] * self.nodes
+
+        def find(x: int) -> int:
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        score, u, v = self.score.tolist(), self.u.tolist(), self.v.tolist()
+        k, groups, grouped, largest = 0, 0, 0, min(self.nodes, 1)
+        for slot in np.argsort(-ts, kind="stable").tolist():  # thresholds descending: the records >= t are a growing prefix
+            while k < len(score) and score[k] >= ts[slot]:
+                a, b = find(u[k]), find(v[k])
+                sa, sb = size[a], size[b]
+                groups += 1 - (sa >= 2) - (sb >= 2)
+                grouped += (sa if sa < 2 else 0) + (sb if sb < 2 else 0)
+                parent[b], size[a] = a, sa + sb
+                largest = max(largest, sa + sb)
+                k += 1
+            out["components"][slot], out["groups"][slot] = self.nodes - k, groups
+            out["grouped"][slot], out["largest"][slot] = grouped, largest
+        return out
+
+    def merge_score(self, a, b) -> np.ndarray:
+        """Per pair of nodes ``(a[q], b[q])`` the largest threshold at which they share a group: the score of the record
+        that joined their groups; ``-1.0`` if none did (the profiles' "none"), ``+inf`` for ``a == b``."""
+        a, b = np.asarray(a, dtype=np.int64).ravel(), np.asarray(b, dtype=np.int64).ravel()
+        if a.shape != b.shape:
+            raise ValueError("merge_score: a and b must have the same length")
+        if len(a) and (min(int(a.min()), int(b.min())) < 0 or max(int(a.max()), int(b.max())) >= self.nodes):
+            raise ValueError(f"merge_score: nodes must lie in [0, {self.nodes})")
+        out = np.full(len(a), -1.0)
+        out[a == b] = np.inf
+        # offline: every component carries the open queries with one end in it; the smaller set is merged into the larger
+        parent = list(range(self.nodes))
+        open_at: dict = {}
+        for q, (x, y) in enumerate(zip(a.tolist(), b.tolist())):
+            if x != y:
+                open_at.setdefault(x, set()).add(q)
+                open_at.setdefault(y, set()).add(q)
+
+        def find(x: int) -> int:
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for s, x, y in zip(self.score.tolist(), self.u.tolist(), self.v.tolist()):
+            x, y = find(x), find(y)
+            qx, qy = open_at.pop(x, set()), open_at.pop(y, set())
+            if len(qx) < len(qy):
+                qx, qy = qy, qx
+            for q in qy:
+                if q in qx:
+                    qx.discard(q)
+                    out[q] = s
+                else:
+                    qx.add(q)
+            parent[y] = x
+            if qx:
+                open_at[x] = qx
+        return out
+
+
+def _forest_layout(nodes: int, bases, cohort_sizes):
+    return ((0,), (nodes,)) if bases is None else (tuple(bases), tuple(cohort_sizes))
+
+
+def forest_of_hits(lists, nodes: int, min_score: float = 0.0, bases=None, cohort_sizes=None) -> MergeForest:
+    """The definition of a merge forest.  ``lists = [(Hits, left_base, right_base), ...]`` as for ``groups_of_hits``: record
+    ``(score, i, j)`` joins ``u = left_base + i`` and ``v = right_base + j`` and is an edge iff ``score >= min_score`` and
+    ``u != v`` (a NaN links nothing); its value is ``(score, lo, hi)``.  All edges are walked in canonical order -- the
+    order of ``nsm_sort_hits``'s key: score descending by its bits (``+0.0`` before ``-0.0``), then lo, then hi -- and an
+    edge is taken iff its ends are not yet connected by taken edges (Kruskal).  The taken values, in that order."""
+    nodes = int(nodes)
+    if nodes < 0:
+        raise ValueError("forest_of_hits: nodes must be >= 0")
+    min_score = float(min_score)
+    parts = []
+    for hits, left_base, right_base in lists:
+        a, b = _list_nodes(hits, left_base, right_base, nodes, "forest_of_hits")
+        s = np.asarray(hits.score, dtype=np.float64)
+        keep = (s >= min_score) & (a != b)
+        parts.append((s[keep], np.minimum(a, b)[keep], np.maximum(a, b)[keep]))
+    score = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, np.float64)
+    lo = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, np.int64)
+    hi = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, np.int64)
+    order = np.lexsort((hi, lo, _score_key(score)))
+    parent = list(range(nodes))
+
+    def find(x: int) -> int:
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    taken = []
+    for r, a, b in zip(order.tolist(), lo[order].tolist(), hi[order].tolist()):
+        a, b = find(a), find(b)
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+            taken.append(r)
+    taken = np.asarray(taken, dtype=np.int64)
+    return MergeForest(score[taken], lo[taken].astype(np.int32), hi[taken].astype(np.int32), nodes,
+                       *_forest_layout(nodes, bases, cohort_sizes), min_score)
+
+
+def span_lists_device(entries, nodes: int, min_score: float, dev, stats: Optional[list] = None, bases=None,
+                      cohort_sizes=None) -> MergeForest:
+    """One ``nsm_span_hits`` call over device lists, the forest ordered on the device (``nsm_sort_hits``), and one D2H copy
+    of its at most ``nodes - 1`` records.  ``entries``: per list ``(records pointer, n, left_base, left_ids, right_base,
+    right_ids)``."""
+    fn = _lib.entry("nsm_span_hits")
+    nodes = int(nodes)
+    layout = _forest_layout(nodes, bases, cohort_sizes)
+    if nodes == 0:
+        if stats is not None:
+            stats[:] = [0, 0, 0, 0]
+        return MergeForest(np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.int32), 0, *layout, float(min_score))
+    lists = (_lib.NsmHitList * max(1, len(entries)))()
+    for slot, (ptr, n, left_base, left_ids, right_base, right_ids) in zip(lists, entries):
+        slot.hits, slot.n = (ptr if n else None), int(n)
+        slot.left_base, slot.left_ids, slot.right_base, slot.right_ids = int(left_base), int(left_ids), int(right_base), int(right_ids)
+    out = HitBuffer(max(1, nodes - 1), dev)
+    st = torch.zeros(4, dtype=torch.int64, device=dev) if stats is not None else None
+    status = fn(lists, len(entries), nodes, float(min_score), 0, out.records.data_ptr(),
+                out.count.data_ptr(), None, st.data_ptr() if st is not None else None, torch.cuda.current_stream(dev).cuda_stream)
+    if status == 10001:
+        raise ValueError("nsm_span_hits: " + _lib.load().nsm_last_error().decode("utf-8", "replace"))
+    _lib.check(status, "nsm_span_hits")
+    if stats is not None:
+        stats[:] = [int(v) for v in st.tolist()]
+    taken = sort_hits_device(out, int(out.count.item()), nodes)
+    return MergeForest(taken.score, taken.i, taken.j, nodes, *layout, float(min_score))
+
+
+def span_hits(lists, nodes: int, min_score: float = 0.0, device=None, stats: Optional[list] = None, bases=None,
+              cohort_sizes=None) -> MergeForest:
+    """``forest_of_hits(lists, nodes, min_score)`` on the device for host hit lists: upload (in any order), one
+    ``nsm_span_hits`` call over all lists, the forest ordered on the device, one D2H copy of at most ``nodes - 1`` records.
+    Ids must be ``>= 0`` and every record must stay inside the nodes (``ValueError``).  ``stats`` receives [records with
+    score >= min_score, forest records, rounds run, edge visits summed over the rounds]."""
+    dev = _require_gpu("cuda" if device is None else device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    nodes = int(nodes)
+    if nodes < 0:
+        raise ValueError("span_hits: nodes must be >= 0")
+    entries, keep = [], []
+    for hits, left_base, right_base in lists:
+        _list_nodes(hits, left_base, right_base, nodes, "span_hits")
+        recs = _records_to_device(hits, dev)
+        keep.append(recs)
+        entries.append((recs.data_ptr() if recs is not None else 0, len(hits), int(left_base), nodes - int(left_base),
+                        int(right_base), nodes - int(right_base)))
+    return span_lists_device(entries, nodes, min_score, dev, stats, bases, cohort_sizes)
+
+
+def _forest_pending(pending: PendingHits, left, right, threshold: float, same: bool, min_score,
+                    stats: Optional[list]) -> MergeForest:
+    # (nsm_span_hits numbers the nodes by caller id, as nsm_group_hits does)
+    ids_l, ids_r = _id_count(left.orig, left.n, "forest"), _id_count(right.orig, right.n, "forest")
+    if same:  # one node space: left item k and right item k are the same node
+        nodes, bases, sizes = max(ids_l, ids_r), (0,), (max(ids_l, ids_r),)
+    else:
+        nodes, bases, sizes = ids_l + ids_r, (0, ids_l), (ids_l, ids_r)
+    floor = float("-inf") if min_score is None else float(min_score)
+    # the buffer goes in UNSORTED and is only read: the call orders its own copy of the edges
+    forest = span_lists_device([(pending.buf.records.data_ptr(), pending.n, 0, ids_l, bases[-1], ids_r)], nodes, floor,
+                               pending.buf.records.device, stats, bases, sizes)
+    forest.min_score = max(floor, float(threshold))  # (the grid knows nothing below its threshold either)
+    return forest
+
+
+def indel_raw_forest(left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
+                     two_stage: bool = True, pack: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
+                     stats: Optional[list] = None) -> MergeForest:
+    """``forest_of_hits([(indel_raw_grid(left, right, threshold, ...), 0, right's base)], ...)``: the grid's hits stay in
+    their device buffer, are spanned there, and only the forest (fewer records than there are items) crosses to the host.
+    ``same``: both tables describe the same items (a self-join), numbered in ONE node space.  ``min_score``: only records
+    scoring at least that are edges (None: every hit of the grid; the forest then knows every threshold the grid does)."""
+    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True)
+    return _forest_pending(pending, left, right, threshold, same, min_score, stats)
+
+
+def jaccard_raw_forest(left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
+                       index: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
+                       stats: Optional[list] = None) -> MergeForest:
+    """``intersection_vs_union`` counterpart of ``indel_raw_forest``."""
+    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True)
+    return _forest_pending(pending, left, right, threshold, same, min_score, stats)
+
+
+def indel_levels_forest(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, threshold: float,
+                        category_mode: int = _lib.CAT_NONE, prune: bool = True, capacity: Optional[int] = None, same: bool = False,
+                        min_score: Optional[float] = None, stats: Optional[list] = None, **grid_options) -> MergeForest:
+    """``forest_of_hits`` of ``indel_levels_grid(...)``'s hits without them leaving the device (``grid_options``: the grid's
+    other keywords)."""
+    pending = indel_levels_grid(left, left_strings, right, right_strings, threshold, category_mode=category_mode, prune=prune,
+                                capacity=capacity, defer=True, **grid_options)
+    return _forest_pending(pending, left, right, threshold, same, min_score, stats)
+
+
+def jaccard_levels_forest(left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE,
+                          prune: bool = True, capacity: Optional[int] = None, index: Optional[bool] = None, same: bool = False,
+                          min_score: Optional[float] = None, stats: Optional[list] = None) -> MergeForest:
+    """``intersection_vs_union`` counterpart of ``indel_levels_forest``."""
+    pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
+                                  index=index, defer=True)
+    return _forest_pending(pending, left, right, threshold, same, min_score, stats)

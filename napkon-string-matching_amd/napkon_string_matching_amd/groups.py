@@ -11,10 +11,14 @@ Three steps, the first and the last pure host functions:
 * ``lists_of_results``   frames -> node numbering and hit lists
 * ``grid.group_hits``    hit lists -> labels (the device)
 * ``mapping_of_labels``  labels -> ``Mapping``
+
+``forest_of_results`` is the same at EVERY threshold from one device call: ``grid.span_hits`` (``nsm_span_hits``,
+include/nsm_hip_span.h) in place of ``grid.group_hits``, and ``ResultForest.mapping(threshold)`` cuts it on the host.
 """
 from __future__ import annotations
 
 import hashlib
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -111,3 +115,35 @@ def mapping_of_results(results: ComparisonResults, min_score: Optional[float] = 
     floor = float("-inf") if min_score is None else float(min_score)
     label = grid.group_hits(lists, nodes, floor, device=device)
     return mapping_of_labels(label, cohorts, identifiers, id_reference)
+
+
+@dataclass
+class ResultForest:
+    """The merge forest of a run's frames with the node naming of ``lists_of_results``: cohort ``c``'s identifier ``k`` is
+    node ``forest.bases[c] + k``."""
+
+    forest: grid.MergeForest
+    cohorts: List[str]
+    identifiers: List[List[str]]
+
+    def mapping(self, threshold: float, id_reference: Optional[Mapping] = None) -> Mapping:
+        """``mapping_of_results(results, min_score=threshold)`` without another pass over the frames (``ValueError`` below
+        the forest's ``min_score``)."""
+        return mapping_of_labels(self.forest.cut(threshold).label, self.cohorts, self.identifiers, id_reference)
+
+    def ladder(self, thresholds) -> dict:
+        """``forest.ladder``: per threshold the components, the entries (groups of at least two identifiers), the
+        identifiers in entries and the largest entry's size."""
+        return self.forest.ladder(thresholds)
+
+
+def forest_of_results(results: ComparisonResults, min_score: Optional[float] = None, device=None) -> ResultForest:
+    """The merge forest of a run: every frame's rows scoring ``>= min_score`` (None: all rows) are edges between
+    identifiers, spanned over ALL frames in one ``grid.span_hits`` call.  ``.mapping(t)`` is ``mapping_of_results(results,
+    min_score=t)`` for every ``t >= min_score``."""
+    cohorts, identifiers, lists = lists_of_results(results)
+    sizes = [len(ids) for ids in identifiers]
+    bases = np.r_[0, np.cumsum(sizes)].astype(np.int64)
+    floor = float("-inf") if min_score is None else float(min_score)
+    forest = grid.span_hits(lists, int(bases[-1]), floor, device=device, bases=tuple(bases[:-1].tolist()), cohort_sizes=tuple(sizes))
+    return ResultForest(forest, cohorts, identifiers)

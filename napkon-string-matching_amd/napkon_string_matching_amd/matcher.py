@@ -110,6 +110,14 @@ class Matcher:
 
         return mapping_of_results(self.results, min_score=min_score, id_reference=id_reference)
 
+    def match_forest(self, min_score: Optional[float] = None):
+        """The run's results as a merge forest (``groups.forest_of_results``): ``match_groups`` at EVERY threshold
+        ``>= min_score`` from one device call -- ``.mapping(t).dict() == match_groups(min_score=t).dict()`` -- and
+        ``.ladder(thresholds)`` to see where the entries become sensible."""
+        from .groups import forest_of_results
+
+        return forest_of_results(self.results, min_score=min_score)
+
     # ---- result consumers (matcher.py:286-331)
     def _analyse(self) -> Dict[str, Dict[str, str]]:
         gecco_prefix = "gec_"

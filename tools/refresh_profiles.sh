@@ -19,6 +19,7 @@ for part in $parts; do
     python3 tools/bench_levels.py --rows 100000 --steps 5 --check 300 > $out/levels_bench.json 2> $out/levels_bench.err; echo "levels bench done"
     python3 tools/bench_levels.py --rows 100000 --steps 5 --threshold 0.1 > $out/levels01_bench.json 2> $out/levels01_bench.err; echo "levels bench at 0.1 done"
     python3 tools/bench_terms.py --rows 50000 --check 200 > $out/terms_bench.json 2> $out/terms_bench.err; echo "terms bench done"
+    python3 tools/bench_span.py --out $out/span_bench.json > /dev/null 2> $out/span_bench.err; echo "merge forest bench done"
     ;;
   trace)
     for w in c2 c3 c5 c5w term; do
