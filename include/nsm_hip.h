@@ -242,6 +242,9 @@ typedef struct nsm_level_items {
                                stream-ordered scratch (chosen by itself where the grid is large enough; this forces it: A/B
                                runs, tests).  A call that is being captured into a graph never packs */
 #define NSM_FLAG_NO_PACK 4096u /* the same grid: never pack (A/B runs, tests) */
+#define NSM_FLAG_ONE_GROUP 8192u /* the same grid, where it packs: the persistent form of the scan (waves that pull work items
+                                    from a list the pre-pass makes), launched with ONE workgroup (tests: every wave then takes
+                                    many items; same hits) */
 #define NSM_FLAG_WAVE_WIDE 2u /* nsm_indel_levels_grid: score every step wave-wide (no block-cooperative
                                  parking of the surviving pairs); same hits, kept for A/B runs and tests */
 

@@ -22,6 +22,7 @@
 #include "nsm_common.hpp"
 #include "indel_score.hpp"
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -395,23 +396,33 @@ __global__ __launch_bounds__(kBlock) NSM_C3_OCC void indel_raw_kernel(
 #include "indel_raw_coarse.hpp"
 namespace nsm {
 
-static int pick_rows_per_chunk(int n_left, int n_tiles) {
 #ifndef NSM_C3_WANT_WAVES
 #define NSM_C3_WANT_WAVES (16ll * 256 * 32)
 #endif
-  const long long want_waves = NSM_C3_WANT_WAVES;
+#ifndef NSM_C3_CHUNK_MAX
+#define NSM_C3_CHUNK_MAX 4096
+#endif
+// The packed two-stage scan takes HALF as many chunks, twice as long (4 800 rows against 2 400 at 200k x 200k): a wave's right
+// set-up and its partly empty drain at its end are paid per chunk, and the packed grids are deep enough (10 waves per slot)
+// that the longer tail costs less than that saves.  Measured with these two knobs alone, kernel ms at 200k x 200k: 1 200 rows
+// 0.959, 2 400 rows 0.896, 4 800 rows 0.878 (profiles/c3_persist_sizing.txt)
+#ifndef NSM_C3C_PACK_WANT_WAVES
+#define NSM_C3C_PACK_WANT_WAVES (NSM_C3_WANT_WAVES / 2)
+#endif
+#ifndef NSM_C3C_PACK_CHUNK_MAX
+#define NSM_C3C_PACK_CHUNK_MAX 8192
+#endif
+static int pick_rows_per_chunk(int n_left, int n_tiles, long long want_waves = NSM_C3_WANT_WAVES, int chunk_max = NSM_C3_CHUNK_MAX) {
   long long chunks = (want_waves + n_tiles - 1) / (n_tiles > 0 ? n_tiles : 1);
   if (chunks < 1) chunks = 1;
   long long rows = (n_left + chunks - 1) / chunks;
   if (rows < 64) rows = 64;
-#ifndef NSM_C3_CHUNK_MAX
-#define NSM_C3_CHUNK_MAX 4096
-#endif
-  if (rows > NSM_C3_CHUNK_MAX) rows = NSM_C3_CHUNK_MAX;
+  if (rows > chunk_max) rows = chunk_max;
   return static_cast<int>(rows);
 }
 
-// The packed rows of the two-stage scan (below): ONE buffer per (device, stream), kept between calls and grown on demand;
+// The packed rows of the two-stage scan (below), and behind them the persistent scan's queue words and item list: ONE buffer
+// per (device, stream), kept between calls and grown on demand;
 // nsm_release() / nsm_release_all() free it with the split path's per-stream state.  Only the allocation is kept, never its
 // contents: the pre-pass writes every row a call's scan reads, every call.  Calls on one stream run in stream order, so the
 // pre-pass of the next call overwrites the rows behind the scan of the one before; growing frees the old buffer with hipFree,
@@ -440,6 +451,24 @@ static void* pack_scratch(hipStream_t stream, size_t bytes) {
   }
   w.bytes = bytes;
   return w.rows;
+}
+
+// compute units of the current device (the persistent scan's grid), asked once per device; 256 where the question fails
+static int device_cus() {
+  static std::mutex mu;
+  static std::map<int, int> cus;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cus.find(dev);
+  if (it != cus.end()) return it->second;
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) {
+    (void)hipGetLastError();
+    n = 256;
+  }
+  cus[dev] = n;
+  return n;
 }
 
 void release_pack_scratch(int dev, void* stream, bool all) {
@@ -547,8 +576,56 @@ extern "C" int nsm_indel_raw_grid(const nsm_str_table* left, const nsm_str_table
       if (hipStreamIsCapturing(hs, &capture) != hipSuccess) capture = hipStreamCaptureStatusNone;
       pack = capture == hipStreamCaptureStatusNone;
     }
+    // The persistent launch (a build with NSM_C3C_PERSIST, and any build under NSM_FLAG_ONE_GROUP, so that the tests reach it):
+    // the item list and the queue's words stand in front of the packed rows in the same kept buffer, and the pre-pass writes
+    // them, every call (indel_raw_coarse.hpp: "the persistent launch").  CUs x 4 workgroups of four waves fill the device at
+    // the kernel's four waves per SIMD; fewer where the list cannot have that many items.  NSM_FLAG_ONE_GROUP: one workgroup,
+    // whose waves then each take many items, of several tiles and bases.
+    if (pack && (NSM_C3C_PERSIST || (flags & NSM_FLAG_ONE_GROUP))) {
+      C3pItemParams ip;
+      ip.n_left = left->n; ip.n_right = right->n; ip.n_tiles = n_tiles;
+      ip.item_rows = NSM_C3P_ITEM_ROWS > 0 ? (NSM_C3P_ITEM_ROWS + kC3cBlock - 1) / kC3cBlock * kC3cBlock : p.rows_per_chunk;
+      if (ip.item_rows > kC3pWindow) ip.item_rows = kC3pWindow;
+      ip.every_row = p.zero_need == 0;
+      for (int lb = 0; lb <= 64; ++lb) {
+        ip.la_lo[lb] = 65;
+        ip.la_hi[lb] = 0;
+        for (int la = 1; la <= 64 && lb > 0; ++la) {
+          if (std::min(la, lb) < static_cast<int>(p.lcsmin[la + lb])) continue;
+          if (ip.la_lo[lb] == 65) ip.la_lo[lb] = static_cast<uint8_t>(la);
+          ip.la_hi[lb] = static_cast<uint8_t>(la);
+        }
+      }
+      const long long item_cap = static_cast<long long>(n_tiles) * c3p_items_of(left->n, ip.item_rows);
+      const size_t rows_bytes = static_cast<size_t>(left->n) * kC3cPackedRow;
+      // (the list in front, backwards from the queue, rounded up so that the packed rows stay 64-byte aligned)
+      const size_t list_bytes = (static_cast<size_t>(item_cap) * sizeof(int4) + 63) / 64 * 64;
+      if (item_cap >= (1ll << 31)) pack = false;  // (2^31 items: tables beyond any device's memory; the unpacked scan takes them)
+      ip.cap = static_cast<unsigned int>(item_cap);
+      char* kept = pack ? static_cast<char*>(pack_scratch(hs, list_bytes + kC3pQueueBytes + rows_bytes)) : nullptr;
+      if (kept) {
+        char* packed = kept + list_bytes + kC3pQueueBytes;
+        const long long units = 2ll * left->n;
+        const int item_blocks = (n_tiles + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL(c3p_prepass_kernel, dim3(static_cast<unsigned>(item_blocks + (units + kBlock - 1) / kBlock)), dim3(kBlock), 0, hs,
+                           lh32, reinterpret_cast<c3c_v4i*>(packed), right->len, left->len_start, c3p_queue(packed), ip, item_blocks);
+        long long groups = std::min<long long>((item_cap + kWavesPerBlock - 1) / kWavesPerBlock, 4ll * device_cus());
+        if (groups < 1 || (flags & NSM_FLAG_ONE_GROUP)) groups = 1;
+        hipLaunchKernelGGL((indel_raw_coarse_kernel<NSM_C3C_NT, NSM_C3C_CAP, true, true>), dim3(static_cast<unsigned>(groups)), dim3(kBlock),
+                           c3c_lds_bytes(), hs, left->codes, left->len, left->len_start, left->orig, lh32, right->codes, right->len,
+                           right->orig, rh32, hits, hit_count, p, static_cast<const char*>(packed));
+        return hip_status(hipGetLastError(), "indel_raw_coarse_kernel launch (persistent)");
+      }
+    }
     void* packed = pack ? pack_scratch(hs, static_cast<size_t>(left->n) * kC3cPackedRow) : nullptr;
     if (packed) {
+      // (the packed scan's longer chunks, above; a table with so many rows that they would not fit the grid keeps the others)
+      const int rows_packed =
+          (pick_rows_per_chunk(left->n, n_tiles, NSM_C3C_PACK_WANT_WAVES, NSM_C3C_PACK_CHUNK_MAX) + kC3cBlock - 1) / kC3cBlock * kC3cBlock;
+      if (rows_packed <= (1 << 15) && (left->n + rows_packed - 1) / rows_packed <= 65535) {
+        p.rows_per_chunk = rows_packed;
+        grid.y = (left->n + rows_packed - 1) / rows_packed;
+      }
       const long long units = 2ll * left->n;
       hipLaunchKernelGGL(c3c_pack_left_kernel, dim3(static_cast<unsigned>((units + kBlock - 1) / kBlock)), dim3(kBlock), 0, hs,
                          lh32, static_cast<c3c_v4i*>(packed), left->n);

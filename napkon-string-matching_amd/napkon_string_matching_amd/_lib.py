@@ -14,7 +14,8 @@ FLAG_TILE_INDEX = 64  # with FLAG_INDEX: the per-tile LDS index even when the ri
 FLAG_RAW_SCORE = 32  # nsm_*_any_grid: the RAW plugin call instead of compare_terms
 FLAG_ONE_STAGE = 1024  # nsm_indel_raw_grid: the 32-bucket histogram test for every pair (not the two-stage kernel)
 FLAG_PACK, FLAG_NO_PACK = 2048, 4096  # nsm_indel_raw_grid, two-stage: force / forbid the once-per-call left operand words
-FLAG_SPLIT, FLAG_TILE, FLAG_PROBE = 128, 256, 512  # nsm_indel_levels_grid, one-word strings: force the split path / the tile kernel; scan only
+FLAG_ONE_GROUP = 8192  # nsm_indel_raw_grid, where it packs: the persistent (item-pulling) scan, ONE workgroup (tests)
+FLAG_SPLIT, FLAG_TILE, FLAG_PROBE = 128, 256, 512 # nsm_indel_levels_grid, one-word strings: force the split path / the tile kernel; scan only
 FLAG_PARK = 16  # nsm_indel_levels_grid, strings > 64 code units: the round-2 park kernel instead of the shared-tile kernel
 BUILD_PARTITION, BUILD_VALIDATE, BUILD_SORT = 1, 2, 4
 ASSIGN_ROUNDS_ONLY, ASSIGN_STREAM_ONLY = 1, 2  # nsm_assign_hits (include/nsm_hip_assign.h): one stage only (A/B runs, tests)

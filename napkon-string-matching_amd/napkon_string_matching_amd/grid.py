@@ -161,17 +161,20 @@ def jaccard_raw_grid(
 
 def indel_raw_grid(
     left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
-    two_stage: bool = True, pack: Optional[bool] = None, defer: bool = False,
+    two_stage: bool = True, pack: Optional[bool] = None, defer: bool = False, one_group: bool = False,
 ) -> Hits:
     """``fuzzy_match`` (QRatio/100 = Indel ratio after default_process) on one string per item.
     ``two_stage=False``: the 32-bucket histogram test for every pair even when both tables carry the ``hist16``
     column that selects the two-stage kernel (A/B runs, tests; same hits).
     ``pack``: None = the library decides whether the two-stage scan codes its left operand words once per call (a
-    pre-pass into a buffer the library keeps per stream, where the grid is large enough); True = force it, False = never (same hits)."""
+    pre-pass into a buffer the library keeps per stream, where the grid is large enough); True = force it, False = never (same hits).
+    ``one_group``: where the call packs, the persistent form of the scan (waves that pull work items from a list) as ONE workgroup
+    (tests; same hits)."""
     lib = _lib.load()
     ls, rs = left.struct(), right.struct()
     flags = ((_lib.FLAG_PRUNE if prune else 0) | (0 if two_stage else _lib.FLAG_ONE_STAGE)
-             | (0 if pack is None else (_lib.FLAG_PACK if pack else _lib.FLAG_NO_PACK)))
+             | (0 if pack is None else (_lib.FLAG_PACK if pack else _lib.FLAG_NO_PACK))
+             | (_lib.FLAG_ONE_GROUP if one_group else 0))
 
     def launch(buf: HitBuffer, stream: int) -> int:
         return lib.nsm_indel_raw_grid(
