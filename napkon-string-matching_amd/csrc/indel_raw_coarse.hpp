@@ -67,6 +67,18 @@
 //           once (the column, the half) is worked out again from the lane.  The unpacked scan keeps the max fold: the grids
 //           that do not pack scan short runs of blocks, where the bias tuple and the longer chain cost more than the fold
 //           saves.  tests/support/scan_orfold.py restates it.  DESIGN 4.3 step 13, profiles/c3_orfold_ab.txt.
+//   codes2  the PACKED scan (NSM_C3C_CODES2) keeps slots 1 and 2 and makes slots 3 and 4 VALUE TABLES on both sides, found by
+//           tools/c3_code_search.py: D_b = min(a, r, 2) + 2^k (x3(a) y3(r') + x4(a) y4(r')), tables over the counts 0 .. 15 with
+//           x3 y3 + x4 y4 >= max(min(a, r) - 2, 0); a left count above 15 reads entry 15, a scaled right count entry
+//           r' = 2 + ceil((r - 2) / 2^k).  The code of before gives r where a >= 4 (ten times looser than sum of min on the
+//           benchmark's strings, whose 37 symbols put two in five of the 32 buckets); the tables pass 0.30 of its pairs on the
+//           tool's sample and pushed 1.21 million entries a launch where it pushed 3.52 (200k x 200k).  The left words are made
+//           by the pre-pass (c3c_fp4_left_packed), the right ones by other constants in the same ten instructions a word, so
+//           the scan loop's instructions are those of before.  Products are multiples of 1/4 and D <= 162, so the OR fold keeps
+//           4 D in two 11-bit fields: field = 4 D + 1024 - 4 need, flags in bits 10 and 21, B scale bytes 0x7f + 2 and 0x7f + 13
+//           (+ k), BIAS = 2^23 + (1024 - 4 need_hi) 2^11 + (1024 - 4 need_lo); the sum stays below 2^24 and every term is an
+//           integer (tools/mfma_fp4_probe, chain4 quarters).  The unpacked scan, and NSM_C3C_CODES2=0, keep the codes above and
+//           the 9-bit fields below.  tests/support/scan_codes2.py restates it.  DESIGN 4.3 step 15, profiles/c3_codes2_ab.txt.
 //   right   made once by the wave and again behind a drain.  k = 0: byte tables too, v_perm_b32 with the count's low
 //           three bits as the selector and the table of 0 .. 7 or of 8 .. 15 by its bit 3.  k > 0: byte by byte, the
 //           excess through a 13-nibble table in a 64-bit constant.
@@ -166,6 +178,12 @@ namespace nsm {
 // folds with OR on the fields' flag bits (NT even); 0, and the unpacked scan always: a tile per accumulator, max fold and a
 // compare with the tile's need (the i8 scan's)
 #define NSM_C3C_ORFOLD (NSM_C3C_FP4 && NSM_C3C_NT % 2 == 0)
+#endif
+#ifndef NSM_C3C_CODES2
+// 1: the PACKED scan's slots 3 and 4 are value TABLES on both sides (tools/c3_code_search.py), their products multiples of
+// 1/4, and the OR fold's fields are 11 bits of 4 D; 0: the indicator and excess codes of the unpacked scan in 9-bit fields
+// (the packed kernel of before, instruction for instruction).  The unpacked scan keeps the old codes either way
+#define NSM_C3C_CODES2 1
 #endif
 #ifndef NSM_C3C_PIPE
 // 1: two accumulators, a tile's (OR fold: a tile pair's) MFMAs are issued around the fold of the one before; the number of
@@ -282,6 +300,61 @@ __device__ __forceinline__ void c3c_fp4_left(uint32_t w, int& m1, int& m2) {
   m2 = static_cast<int>(((c3c_ge64(w, 3) >> 4)) | c3c_ge64(w, 4));
 #endif
 }
+// --- the codes of the packed scan (NSM_C3C_CODES2): slots 1 and 2 as above, slots 3 and 4 value tables by count 0 .. 15, the
+// byte of a count = slot 3's E2M1 code in the low nibble, slot 4's in the high one; words = counts 0 - 3, 4 - 7, 8 - 11, 12 - 15.
+// The output of tools/c3_code_search.py (SHIPPED there; tests/support/scan_codes2.py restates them):
+//   count        0  1  2    3    4    5    6    7    8    9   10   11   12   13   14   15
+//   x3 (left)    0  0  0    2    2    2    2    2    2    2    2    3    4    4    4    6
+//   x4 (left)    0  0  0    0    1    1  1.5    2    2    2    2    2    2    2    2    2
+//   y3 (right)   0  0  0  0.5  0.5  0.5  0.5  0.5  0.5  0.5    1    1    1  1.5  1.5  1.5
+//   y4 (right)   0  0  0    0    1    2    2    2    3    3    3    3    3    3    3    3
+// x3(a) y3(r) + x4(a) y4(r) >= max(min(a, r) - 2, 0) for all a, r <= 15.  A left count above 15 reads entry 15; a right count
+// r >= 3 of a string with scale exponent k reads entry 2 + ceil((r - 2) / 2^k) <= 15 (c3c_fp4_scale's k) and the MFMA scales
+// the product by 2^k: 2^k max(min(min(a, 15), entry) - 2, 0) >= min(a, r) - 2.
+constexpr uint32_t kC3cLeft2[4] = {0x04000000u, 0x44342424u, 0x45444444u, 0x47464646u};
+constexpr uint32_t kC3cRight2[4] = {0x01000000u, 0x41414121u, 0x52525151u, 0x53535352u};
+// the table bytes of four counts 0 .. 15: two v_perm_b32 on the counts' low three bits, the one of 0 .. 7 or of 8 .. 15 by bit 3
+__device__ __forceinline__ uint32_t c3c_codes2_bytes(uint32_t w, const uint32_t (&t)[4]) {
+  const uint32_t sel = w & 0x07070707u;
+  const uint32_t big = ((w >> 3) & 0x01010101u) * 0xffu;  // 0xff where 8 <= count <= 15
+  return (big & __builtin_amdgcn_perm(t[3], t[2], sel)) | (~big & __builtin_amdgcn_perm(t[1], t[0], sel));
+}
+// the left words of the pre-pass: m1 as c3c_fp4_left's; m2 from the table, a count above 15 (c + 0x70 has bit 7: a count is
+// at most 64, nothing carries) taken as 15
+__device__ __forceinline__ void c3c_fp4_left_packed(uint32_t w, int& m1, int& m2) {
+#if NSM_C3C_CODES2
+  int old2;
+  c3c_fp4_left(w, m1, old2);
+  const uint32_t over = (((w + 0x70707070u) >> 7) & 0x01010101u) * 0xffu;
+  m2 = static_cast<int>(c3c_codes2_bytes((w | over) & 0x0f0f0f0fu, kC3cLeft2));
+#else
+  c3c_fp4_left(w, m1, m2);
+#endif
+}
+// the right words, k = 0: other constants in c3c_fp4_right_k0's scheme, ten instructions a word
+__device__ __forceinline__ void c3c_codes2_right_k0(uint32_t fw, int& m1, int& m2) {
+  const uint32_t sel = fw & 0x07070707u;
+  const uint32_t big = ((fw >> 3) & 0x01010101u) * 0xffu;
+  const uint32_t lo1 = __builtin_amdgcn_perm(0x11111111u, 0x11110100u, sel);
+  const uint32_t lo2 = __builtin_amdgcn_perm(kC3cRight2[1], kC3cRight2[0], sel), hi2 = __builtin_amdgcn_perm(kC3cRight2[3], kC3cRight2[2], sel);
+  m1 = static_cast<int>((big & 0x11111111u) | (~big & lo1));
+  m2 = static_cast<int>((big & hi2) | (~big & lo2));
+}
+// k > 0: byte by byte, the table's entry 2 + ceil((r - 2) / 2^k) (r < 3: entry 2, which is zero like entries 0 and 1)
+__device__ __forceinline__ void c3c_codes2_right_scaled(uint32_t fw, int k, int& m1, int& m2) {
+  m1 = static_cast<int>((c3c_ge64(fw, 1) >> 6) | (c3c_ge64(fw, 2) >> 2));
+  const unsigned long long lo = (static_cast<unsigned long long>(kC3cRight2[1]) << 32) | kC3cRight2[0];
+  const unsigned long long hi = (static_cast<unsigned long long>(kC3cRight2[3]) << 32) | kC3cRight2[2];
+  const uint32_t round_up = (1u << k) - 1u;
+  uint32_t w2 = 0u;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const uint32_t r = (fw >> (8 * b)) & 0xffu;
+    const uint32_t e = min(2u + ((max(r, 2u) - 2u + round_up) >> k), 15u);  // (15 or below by the choice of k: the clamp guards the shift)
+    w2 |= (static_cast<uint32_t>((e & 8u ? hi : lo) >> (8u * (e & 7u))) & 0xffu) << (8 * b);
+  }
+  m2 = static_cast<int>(w2);
+}
 // slots 1 and 2: the unscaled form (both scale arguments literal 0)
 __device__ __forceinline__ c3c_v16f c3c_fp4_mfma1(const c3c_v4i& a, const c3c_v4i& b) {
   const c3c_v8i a8 = {a.x, a.y, a.z, a.w, 0, 0, 0, 0}, b8 = {b.x, b.y, b.z, b.w, 0, 0, 0, 0};  // (FP4: the upper half is not read)
@@ -335,7 +408,7 @@ __device__ __forceinline__ void c3c_pack_left_unit(const uint32_t* __restrict__ 
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     int a1, a2;
-    c3c_fp4_left(ws[q], a1, a2);
+    c3c_fp4_left_packed(ws[q], a1, a2);
     m1[q] = a1;
     m2[q] = a2;
   }
@@ -478,7 +551,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
   // the OR fold is the packed scan's: the grids that do not pack (c3c_pack_pays) are short runs of blocks, where the bias
   // tuple of every class and the longer chain cost more than the fold saves
   constexpr bool kOrFold = NSM_C3C_ORFOLD && PACKED;
-  constexpr int kFlagHi = 1 << 17, kFlagLo = 1 << 8;  // bit 8 of the upper and of the lower field
+  // CODES2: the packed scan's value tables, whose D is a multiple of 1/4: the fields hold 4 D in 11 bits
+  constexpr bool kCodes2 = NSM_C3C_CODES2 && PACKED;
+  constexpr int kFieldBits = kCodes2 ? 11 : 9, kFieldFrac = kCodes2 ? 2 : 0;  // a field = (D + 256 - need) << kFieldFrac
+  constexpr int kFlagLo = 1 << (kFieldBits - 1), kFlagHi = kFlagLo << kFieldBits;  // the top bit of the lower and of the upper field
   static_assert(!kOrFold || (NSM_C3C_FP4 && NT % 2 == 0), "the OR fold puts tiles 2 p and 2 p + 1 of the FP4 scan on one accumulator");
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_mem[];
   unsigned long long* s_stack = s_mem;
@@ -611,7 +687,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
     // the string's lanes get the same byte; behind a drain the words come from the LDS copy and the scales are still here
     // OR fold: an even tile's results go to the accumulator's upper field, so its scale bytes are 0x7f + 9 and 0x7f + 9 + k.
     // The slots 1 and 2 then need a scale too, the same in every lane: bscales1, bytes 0x88 and 0x7f in turn
-    auto scale_base = [](int t) -> uint32_t { return (kOrFold && t % 2 == 0) ? 0x7fu + 9u : 0x7fu; };
+    // CODES2: 4 D in 11-bit fields: 0x7f + 13 and 0x7f + 2
+    auto scale_base = [](int t) -> uint32_t {
+      return kOrFold ? 0x7fu + static_cast<uint32_t>(kFieldFrac + (t % 2 == 0 ? kFieldBits : 0)) : 0x7fu;
+    };
     uint32_t bscales1 = 0u;
     if constexpr (kOrFold) {
 #pragma unroll
@@ -626,7 +705,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           int m1, m2;
-          c3c_fp4_right_k0(ws[q], m1, m2);
+          if constexpr (kCodes2)
+            c3c_codes2_right_k0(ws[q], m1, m2);
+          else
+            c3c_fp4_right_k0(ws[q], m1, m2);
           bfrag[t][0][q] = m1;
           bfrag[t][1][q] = m2;
         }
@@ -634,7 +716,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           int m1, m2;
-          c3c_fp4_right_scaled(ws[q], k, m1, m2);
+          if constexpr (kCodes2)
+            c3c_codes2_right_scaled(ws[q], k, m1, m2);
+          else
+            c3c_fp4_right_scaled(ws[q], k, m1, m2);
           bfrag[t][0][q] = m1;
           bfrag[t][1][q] = m2;
         }
@@ -884,7 +969,8 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
         if constexpr (kOrFold)
           need2[t & 1] = min(need2[t & 1], fits ? nd : static_cast<int>(kNever));  // (fits: nd <= min(la, lb) <= 64)
         else
-          nm1[t] = __float_as_int(static_cast<float>(fits ? nd : static_cast<int>(kNever)) - 0.5f);  // (no D reaches kNever: D <= 128)
+          // (CODES2: D is a multiple of 1/4, and D >= need is D > need - 1/4)
+          nm1[t] = __float_as_int(static_cast<float>(fits ? nd : static_cast<int>(kNever)) - (kCodes2 ? 0.25f : 0.5f));  // (no D reaches kNever: D <= 128; CODES2: 162)
 #else
         nm1[t] = 64 * (fits ? nd : static_cast<int>(kNever)) - 1;
 #endif
@@ -896,7 +982,10 @@ __global__ __launch_bounds__(kBlock) NSM_C3C_OCC void indel_raw_coarse_kernel(
       // is at most 129; need = 0: always set)
       // (made here and again behind a drain between the tiles, like the B fragments: the drain needs the registers)
       c3c_v16f bias;
-      const float bias1 = __int_as_float(0x4b000000 | ((256 - need2[0]) << 9) | (256 - need2[1]));
+      // CODES2: 2^23 + (1024 - 4 need_hi) 2^11 + (1024 - 4 need_lo), the chain adds 2^11 (4 D_hi) + 4 D_lo, D <= 162 a multiple of
+      // 1/4: every term an integer, the sum below 2^24, a field 4 D + 1024 - 4 need <= 1672 < 2048, its bit 10 = [D >= need]
+      // (need = kNever: at most 4 + 648)
+      const float bias1 = __int_as_float(0x4b000000 | (((256 - need2[0]) << kFieldFrac) << kFieldBits) | ((256 - need2[1]) << kFieldFrac));
       auto make_bias = [&]() {
         // (16 registers that stay across the blocks: srcC is a tuple.  The moves are written out: a splat that the compiler
         // sees is made once per class in 16 registers MORE and copied from there behind every drain)

@@ -10,9 +10,12 @@
 // 2b. chain4: the OR-fold scan's chain of four MFMAs on one accumulator -- a bias of 2^23 + two need offsets as srcC, one
 //    tile through B scales 2^9 and 2^(9 + k), the other through 2^0 and 2^k, k = 0 .. 3 by column -- against a host integer
 //    loop, bit for bit.
+// 2c. chain4, 11-bit fields: the same chain with the value-table codes of the packed scan (NSM_C3C_CODES2) -- FP4 values on
+//    BOTH sides, products multiples of 1/4, B scales 2^13 and 2^(13 + k) for one tile, 2^2 and 2^(2 + k) for the other, a bias
+//    of 2^23 + (1024 - 4 need_hi) 2^11 + (1024 - 4 need_lo) -- against a host integer loop in quarters, bit for bit.
 // 3. rate: back-to-back chains, one wave per SIMD: ns per MFMA of the i8 32x32x32 form and of the two FP4 forms; and a
 //    tile pair as two chains of two (zero C) against one chain of four (bias C), at one and at four waves per SIMD.
-// Exit status 0 where 1, 2 and 2b agree with the host.
+// Exit status 0 where 1, 2, 2b and 2c agree with the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -321,6 +324,88 @@ int main() {
     printf("chain4 (bias + 2^9 hi + lo, k = 0 .. 3): %d of 1024 differ (largest N - 2^23: %d)\n", bad_chain, top - (1 << 23));
   }
 
+  // --- 2c. the biased chain of four with 11-bit fields of 4 D (the value-table codes): any FP4 code 0 .. 7 on both sides, sparse
+  // enough that a field stays below 2^11; the host sums (2 x) (2 y) = 4 x y as integers
+  int bad_chain2 = 0;
+  {
+    static int A4[2][32][64], B4[2][2][64][32];  // [m][row][k]; [tile][m][k][col]
+    uint32_t rng = 2468u;
+    auto rnd = [&]() { rng = rng * 1664525u + 1013904223u; return rng >> 8; };
+    for (int m = 0; m < 2; ++m)
+      for (int i = 0; i < 32; ++i)
+        for (int k = 0; k < 64; ++k) {
+          A4[m][i][k] = (rnd() & 3) ? 0 : (int)(rnd() & 7);
+          for (int t = 0; t < 2; ++t) B4[t][m][k][i] = (rnd() & 7) ? 0 : (int)(rnd() % 6);
+        }
+    std::vector<uint32_t> qa(512, 0), qh(512, 0), ql(512, 0), q1(64), q2(64);
+    std::vector<float> qb(64);
+    int nh[32], nl[32];
+    for (int c = 0; c < 32; ++c) {
+      nh[c] = c == 7 ? 255 : (c * 5) % 65;
+      nl[c] = c == 9 ? 255 : (c * 11 + 3) % 65;
+    }
+    for (int l = 0; l < 64; ++l) {
+      const int c = l & 31;
+      for (int m = 0; m < 2; ++m)
+        for (int j = 0; j < 32; ++j) {
+          const int k = 32 * (l >> 5) + j, sh = 4 * (j & 7), w = 8 * l + 4 * m + (j >> 3);
+          qa[w] |= (uint32_t)A4[m][c][k] << sh;
+          qh[w] |= (uint32_t)B4[0][m][k][c] << sh;
+          ql[w] |= (uint32_t)B4[1][m][k][c] << sh;
+        }
+      q1[l] = 0x55aa0000u | (uint32_t)(0x7f + 2) << 8 | (uint32_t)(0x7f + 13);  // (bytes 2 and 3 are not picked)
+      q2[l] = 0xaa550000u | (uint32_t)(0x7f + 2 + ((c >> 2) & 3)) << 8 | (uint32_t)(0x7f + 13 + (c & 3));
+      qb[l] = (float)((1 << 23) + (1024 - 4 * nh[c]) * 2048 + (1024 - 4 * nl[c]));
+    }
+    uint32_t *ea, *eh, *el, *e1, *e2;
+    float *eb, *eo;
+    CHECK(hipMalloc(&ea, 2048));
+    CHECK(hipMalloc(&eh, 2048));
+    CHECK(hipMalloc(&el, 2048));
+    CHECK(hipMalloc(&e1, 256));
+    CHECK(hipMalloc(&e2, 256));
+    CHECK(hipMalloc(&eb, 256));
+    CHECK(hipMalloc(&eo, 4096));
+    CHECK(hipMemcpy(ea, qa.data(), 2048, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(eh, qh.data(), 2048, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(el, ql.data(), 2048, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(e1, q1.data(), 256, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(e2, q2.data(), 256, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(eb, qb.data(), 256, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(chain4_kernel, dim3(1), dim3(64), 0, 0, ea, eh, el, e1, e2, eb, eo);
+    CHECK(hipDeviceSynchronize());
+    std::vector<float> qo(1024);
+    CHECK(hipMemcpy(qo.data(), eo, 4096, hipMemcpyDeviceToHost));
+    const int twice[8] = {0, 1, 2, 3, 4, 6, 8, 12};  // 2 x the FP4 value
+    long long top = 0;
+    int top_field = 0, quarters = 0;
+    for (int l = 0; l < 64; ++l)
+      for (int i = 0; i < 16; ++i) {
+        const int col = l & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (l >> 5);
+        int d[2] = {0, 0};  // 4 D of the two tiles
+        for (int t = 0; t < 2; ++t) {
+          const int k = t ? (col >> 2) & 3 : col & 3;
+          for (int m = 0; m < 2; ++m) {
+            int s = 0;
+            for (int kk = 0; kk < 64; ++kk) s += twice[A4[m][row][kk]] * twice[B4[t][m][kk][col]];
+            d[t] += m ? s << k : s;
+          }
+        }
+        quarters += (d[0] & 3) != 0 || (d[1] & 3) != 0;
+        top_field = d[0] > top_field ? d[0] : top_field;
+        top_field = d[1] > top_field ? d[1] : top_field;
+        const long long n = (1ll << 23) + (1024 - 4 * nh[col]) * 2048ll + (1024 - 4 * nl[col]) + 2048ll * d[0] + d[1];
+        top = n > top ? n : top;
+        uint32_t got;
+        memcpy(&got, &qo[l * 16 + i], 4);
+        if (got != (0x4b000000u | (uint32_t)(n - (1 << 23))) && bad_chain2++ < 4)
+          printf("chain4 q: row %d col %d: bits %08x, host N %lld (4 D hi %d lo %d)\n", row, col, got, n, d[0], d[1]);
+      }
+    if (top >= 1 << 24) { printf("chain4 q: the host sum leaves [2^23, 2^24)\n"); return 2; }
+    printf("chain4 quarters (bias + 2^11 (4 hi) + 4 lo, k = 0 .. 3): %d of 1024 differ (largest 4 D: %d, results off the integers: %d)\n",
+           bad_chain2, top_field, quarters);
+  }
+
   // --- 3. the rate
   hipDeviceProp_t prop;
   CHECK(hipGetDeviceProperties(&prop, 0));
@@ -331,5 +416,5 @@ int main() {
     if (pair_rate<3>("two chains of two, zero C", dout, prop.multiProcessorCount, waves)) return 2;
     if (pair_rate<4>("one chain of four, bias C", dout, prop.multiProcessorCount, waves)) return 2;
   }
-  return (bad[0] || bad[1] || bad_perm || bad_chain) ? 1 : 0;
+  return (bad[0] || bad[1] || bad_perm || bad_chain || bad_chain2) ? 1 : 0;
 }
