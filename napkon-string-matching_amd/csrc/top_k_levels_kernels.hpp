@@ -3,6 +3,7 @@
 #pragma once
 #include "indel_score.hpp"
 #include "indel_wide.hpp"
+#include "set_measure.hpp"
 #include "top_k_lists.hpp"
 
 namespace nsm {
@@ -162,15 +163,12 @@ __global__ __launch_bounds__(kWave) void indel_levels_top_k_kernel(
 struct TopLevJacParams {
   int32_t n_left, n_right, k, lev_stride_l, lev_stride_r, cat_mode;
   double threshold;
+  int32_t measure = NSM_MEASURE_UNION;  // read by RuntimeMeasure alone
 };
 
-// Upper bound of |A n B| / |A u B| for sets of a and b ids that share at most `inter` (inter <= min(a, b)).
-__device__ __forceinline__ double lev_top_jac(int a, int b, int inter) {
-  const int uni = a + b - inter;
-  return uni ? static_cast<double>(inter) / static_cast<double>(uni) : 0.0;
-}
-
-template <int W, bool PRUNE, class Sink = TopLists<false>>
+// M: the measure (set_measure.hpp: part, later); the default is the Jaccard quotient lev_top_jac, the nsm_jaccard_*
+// entries' instantiations.
+template <int W, bool PRUNE, class Sink = TopLists<false>, class M = JaccardMeasure>
 __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
     const int32_t* __restrict__ lids, const int32_t* __restrict__ lcnt, const int32_t* __restrict__ lnlev,
     const uint8_t* __restrict__ lplen, const uint64_t* __restrict__ lcat, const uint32_t* __restrict__ lfilt,
@@ -186,6 +184,7 @@ __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
   const double thr = p.threshold;
   const bool use_cat = p.cat_mode != NSM_CAT_NONE;
   const bool use_sig = PRUNE && lfilt && rfilt;
+  const M meas(p.measure);
 
   const int ll = lnlev[row];
   const int nl = lcnt[row];
@@ -218,11 +217,10 @@ __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
       const double eff = L.eff(0, thr);
       st[0] += valid ? 1u : 0u;
       const int b1 = cand ? rpl[min(min(1, lr - 1), p.lev_stride_r - 1)] : 0;
-      const int m = max(a1, b1);
-      // step 1 <= inter1 / m, every later step <= min(1, inter / m) (its sets contain the step-1 sets)
+      // step 1 <= its score with inter1 in common, every later step <= the measure's `later` (Jaccard: min(1, inter / max(a1,
+      // b1)): its sets contain the step-1 sets)
       auto bound = [&](int inter1, int inter) {
-        const double later = m ? fmin(1.0, static_cast<double>(inter) / static_cast<double>(m)) : 1.0;
-        return 0.5 * lev_top_jac(a1, b1, inter1) + lev_top_tail(S) * later + 1e-6;
+        return 0.5 * meas.part(a1, b1, inter1) + lev_top_tail(S) * meas.later(a1, b1, inter) + 1e-6;
       };
       if (PRUNE && cand) cand = bound(min(a1, b1), min(nl, nr)) >= eff;
       st[1] += cand ? 1u : 0u;
@@ -281,8 +279,7 @@ __global__ __launch_bounds__(kWave) void jaccard_levels_top_k_kernel(
               inter += __popc(~(y | x) & 0x80808080u);
             }
           }
-          const int uni = pl + pr - inter;
-          const double part = uni ? static_cast<double>(inter) / static_cast<double>(uni) : 0.0;
+          const double part = meas.part(pl, pr, inter);
           factor *= 0.5;
           score += part * factor;
           if (PRUNE && s < S && score + factor + 1e-9 < eff) {  // the rest (< factor) cannot lift it

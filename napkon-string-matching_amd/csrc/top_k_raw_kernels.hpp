@@ -3,15 +3,12 @@
 #pragma once
 #include "indel_score.hpp"
 #include "indel_wide.hpp"
+#include "set_measure.hpp"
 #include "top_k_lists.hpp"
 
 namespace nsm {
 
 constexpr int kTopG = 8;         // left rows per wavefront
-
-__device__ __forceinline__ double topk_jaccard_score(int a, int b, int inter) {  // the RAW Jaccard grid's quotient
-  return static_cast<double>(inter) / static_cast<double>(a + b - inter);
-}
 
 // Least LCS whose score reaches `eff` (la, lb >= 1), or min(la, lb) + 1 when none does.  The start
 // ceil(eff (la + lb) / 2) - 1 is below the answer (the rounding of the score is far smaller than one LCS step), the walk
@@ -25,15 +22,7 @@ __device__ __forceinline__ int indel_need(int la, int lb, double eff) {
   return need;
 }
 
-// The same for the intersection of a set of a ids and one of b ids (a + b >= 1).
-__device__ __forceinline__ int jaccard_need(int a, int b, double eff) {
-  if (eff <= 0.0) return 0;
-  const int top = min(a, b);
-  int need = static_cast<int>(floor(eff * static_cast<double>(a + b) / (1.0 + eff))) - 1;
-  need = max(0, min(need, top + 1));
-  while (need <= top && topk_jaccard_score(a, b, need) < eff) ++need;
-  return need;
-}
+// (The same for the intersection of two id sets: jaccard_need and the measures' need, set_measure.hpp.)
 
 // The class walk: classes are indexed by their size z = 0 .. top (length / set size); starting at z0 -- the group's first
 // row's -- the walk goes to whichever neighbour, up (hi) or down (lo), has the larger bound for z0, and drops a direction
@@ -199,10 +188,12 @@ __global__ __launch_bounds__(kWave) void indel_top_k_kernel(
 // ---------------------------------------------------------------------------------------------------------------- Jaccard
 struct TopJacParams {
   int32_t n_left, n_right, k;
+  int32_t measure = NSM_MEASURE_UNION;  // read by RuntimeMeasure alone
   double threshold;
 };
 
-template <int W, bool PRUNE, bool GROUPED, class Sink = TopLists<GROUPED>>  // (GROUPED, rgroup, glist, sx: as in the Indel kernel)
+// M: the measure (set_measure.hpp); the default is the Jaccard quotient, the nsm_jaccard_* entries' instantiations.
+template <int W, bool PRUNE, bool GROUPED, class Sink = TopLists<GROUPED>, class M = JaccardMeasure>  // (GROUPED, rgroup, glist, sx: as in the Indel kernel)
 __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
     const int32_t* __restrict__ lids, const int32_t* __restrict__ lcnt, const uint64_t* __restrict__ lsig,
     const uint64_t* __restrict__ lsig2, const int32_t* __restrict__ lorig, const int32_t* __restrict__ rids,
@@ -217,6 +208,7 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
   const int rows = min(G, p.n_left - row0);
   const double thr = p.threshold;
   const bool two_sigs = PRUNE && lsig2 && rsig2;
+  const M meas(p.measure);
 
   const int na_v = lane < rows ? lcnt[row0 + lane] : 0;
   const int io_v = lane < rows ? lorig[row0 + lane] : 0;
@@ -234,11 +226,8 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
   Sink L = Sink::open(list, glist, p.k, row0, lane, sx);
   unsigned long long st[4] = {0, 0, 0, 0};
 
-  // upper bound with a set of b ids: min / max -- 0 when exactly one side is empty; two empty sets never score
-  auto bound = [&](int g, int b) {
-    const int a = na(g);
-    return a + b == 0 ? -__builtin_inf() : topk_jaccard_score(a, b, min(a, b));
-  };
+  // upper bound with a set of b ids (Jaccard: min / max -- 0 when exactly one side is empty); an undefined pair never scores
+  auto bound = [&](int g, int b) { return meas.bound(na(g), b); };
   auto alive = [&](int from, int to) {
     if (from > to) return false;
     if (!PRUNE) return true;
@@ -246,7 +235,7 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       int b = min(max(na(g), from), to);
-      if (b == 0 && na(g) == 0 && to >= 1) b = 1;  // (an empty row scores 0 against any non-empty set)
+      if (b == 0 && na(g) == 0 && to >= 1) b = 1;  // (an empty row's own class is undefined; class 1 is its best)
       any = any || (g < rows && bound(g, b) >= L.eff(g, thr));
     }
     return any;
@@ -257,8 +246,7 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
   while (true) {
     const bool up = alive(w.hi, W), down = alive(0, w.lo);
     if (!up && !down) break;
-    // bound of class hi for a0: a0 / hi; of class lo: lo / a0
-    const int b = (up && (!down || static_cast<long long>(a0) * a0 >= static_cast<long long>(w.lo) * w.hi)) ? w.hi++ : w.lo--;
+    const int b = (up && (!down || meas.up_first(a0, w.lo, w.hi))) ? w.hi++ : w.lo--;  // the larger bound for a0 first
     const int s = rsize_start[W - b], e = rsize_start[W - b + 1];
     uint32_t active = 0;
     int need[G];
@@ -270,8 +258,8 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
 #pragma unroll
         for (int g = 0; g < G; ++g) {
           const double eff = L.eff(g, thr);
-          active |= (g < rows && na(g) + b > 0 && (!PRUNE || bound(g, b) >= eff)) ? (1u << g) : 0u;
-          need[g] = (PRUNE && na(g) + b > 0) ? jaccard_need(na(g), b, eff) : 0;
+          active |= (g < rows && meas.defined(na(g), b) && (!PRUNE || bound(g, b) >= eff)) ? (1u << g) : 0u;
+          need[g] = (PRUNE && meas.defined(na(g), b)) ? meas.need(na(g), b, eff) : 0;
         }
       }
       if (!active) break;
@@ -321,7 +309,7 @@ __global__ __launch_bounds__(kWave) void jaccard_top_k_kernel(
           }
         }
         st[3] += mine ? 1u : 0u;
-        const double sc = mine ? topk_jaccard_score(a, b, inter) : 0.0;
+        const double sc = mine ? meas.score(a, b, inter) : 0.0;
         L.offer_lanes(g, mine && sc >= thr && L.beats(g, sc, jo), sc, __builtin_amdgcn_readlane(io_v, g), jo,
                       L.group_of(rgroup, jo));
       }

@@ -22,6 +22,9 @@ ASSIGN_ROUNDS_ONLY, ASSIGN_STREAM_ONLY = 1, 2  # nsm_assign_hits (include/nsm_hi
 GROUP_CONTINUE = 1  # nsm_group_hits (include/nsm_hip_groups.h): `label` holds a forest, link the lists into it
 SPAN_NO_COMPACT = 1  # nsm_span_hits (include/nsm_hip_span.h): every round visits every edge (accepted; the only route)
 CAT_NONE, CAT_INTERSECT, CAT_INTERSECT_OR_BOTH_EMPTY = 0, 1, 2
+# include/nsm_hip_measures.h: the token-set measure of the nsm_set_* entries
+MEASURE_UNION, MEASURE_MEAN, MEASURE_SMALLER, MEASURE_LEFT = 0, 1, 2, 3
+MEASURES = {"union": MEASURE_UNION, "mean": MEASURE_MEAN, "smaller": MEASURE_SMALLER, "left": MEASURE_LEFT}
 
 c_i32p = ctypes.c_void_p  # device pointers travel as integers
 c_u64 = ctypes.c_uint64
@@ -147,6 +150,18 @@ GROUP_EXPORTS = ("nsm_group_hits",)
 
 # include/nsm_hip_span.h, likewise
 SPAN_EXPORTS = ("nsm_span_hits",)
+# include/nsm_hip_measures.h, likewise: every nsm_jaccard_* per-item entry with `measure` after `right`
+MEASURE_EXPORTS = (
+    "nsm_set_raw_top_k",
+    "nsm_set_raw_top_k_grouped",
+    "nsm_set_raw_profile",
+    "nsm_set_raw_floor_grid",
+    "nsm_set_raw_pairs",
+    "nsm_set_levels_top_k",
+    "nsm_set_levels_profile",
+    "nsm_set_levels_floor_grid",
+    "nsm_set_levels_pairs",
+)
 
 _lib = None
 
@@ -247,7 +262,20 @@ def load() -> ctypes.CDLL:
     group_args = {"nsm_group_hits": [P(NsmHitList), i32, i32, ctypes.c_double, u32, vp, vp, vp]}
     # lists (host), n_lists, nodes, min_score, flags, forest, forest_count, label, stats, stream
     span_args = {"nsm_span_hits": [P(NsmHitList), i32, i32, ctypes.c_double, u32, vp, vp, vp, vp, vp]}
-    for names, args in ((ASSIGN_EXPORTS, assign_args), (GROUP_EXPORTS, group_args), (SPAN_EXPORTS, span_args)):
+    sets = [P(NsmSetTable), P(NsmSetTable), i32]  # left, right, measure; then the tail of the nsm_jaccard_* counterpart
+    measure_args = {
+        "nsm_set_raw_top_k": sets + top_k_tail,
+        "nsm_set_raw_top_k_grouped": sets + [vp] + top_k_tail,
+        "nsm_set_raw_profile": sets + profile_tail,
+        "nsm_set_raw_floor_grid": sets + floor_tail,
+        "nsm_set_raw_pairs": sets + pairs_tail,
+        "nsm_set_levels_top_k": sets + levels_top_k_tail,
+        "nsm_set_levels_profile": sets + levels_profile_tail,
+        "nsm_set_levels_floor_grid": sets + levels_floor_tail,
+        "nsm_set_levels_pairs": sets + pairs_tail,
+    }
+    for names, args in ((ASSIGN_EXPORTS, assign_args), (GROUP_EXPORTS, group_args), (SPAN_EXPORTS, span_args),
+                        (MEASURE_EXPORTS, measure_args)):
         for name in names:
             try:
                 fn = getattr(lib, name)

@@ -36,6 +36,10 @@ Same names, call convention and error behaviour as the reference's
   merge forest (``grid.forest_of_hits``), spanned on the device -- ``cut(t)``, ``ladder(thresholds)``, ``merge_score(a, b)``;
   ``plugin.cluster_tree(items, threshold)`` is the self-join.
 
+Beside the reference's two functions the module holds three more token-set measures with the same faces --
+``intersection_vs_mean`` (Sorensen-Dice), ``intersection_vs_smaller`` (overlap coefficient) and ``intersection_vs_left``
+(containment of left in right): ``intersection_vs_union``'s class with another ``measure``.
+
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
 """
@@ -137,21 +141,45 @@ def _best(profile, split, n_left: int, n_right: int, margin: float, threshold: f
 
 
 class _IntersectionVsUnion:
+    """``len(A & B) / len(A | B)`` of the two token sets (Jaccard; score_functions.py:6-13).  The token-set measures below
+    are this class with another ``measure``: every method here hands ``self.measure`` to the ``grid.jaccard_*`` wrapper it
+    uses (``"union"`` keeps each wrapper's own route) and takes its ``ZeroDivisionError`` rule from ``divides_by_zero``."""
     __name__ = "intersection_vs_union"
     kind = "sets"
+    measure = "union"  # grid.check_measure: which quotient the device computes
 
     def __call__(self, left: Operand, right: Operand) -> float:
         hits = self.raw_grid([left], [right], float("-inf"))
         return float(hits.score[0])
 
-    @staticmethod
-    def raw_grid(left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+    def divides_by_zero(self, a, b) -> bool:
+        """Does the score of a left set ``a`` and a right set ``b`` (sets, or their sizes) divide by zero?"""
+        size = lambda x: x if isinstance(x, (int, np.integer)) else len(x)
+        return grid.measure_divides_by_zero(self.measure, size(a), size(b))
+
+    def _rows(self, left_items, right_items):
+        """Both sides as token lists.  A measure beside Jaccard checks here what it cannot score, before the device is asked
+        for: the whole grid's ``ZeroDivisionError`` (``grid.check_measure_grid``) and items beyond the fast kernels."""
+        l_rows = [list(set_operand(v)) for v in left_items]
+        r_rows = [list(set_operand(v)) for v in right_items]
+        if self.measure != "union":
+            grid.check_measure_grid(self.measure, any(not r for r in l_rows), len(l_rows), any(not r for r in r_rows), len(r_rows))
+            self._check_narrow(l_rows, r_rows)
+        return l_rows, r_rows
+
+    def _check_narrow(self, *sides) -> None:
+        from .. import wide
+
+        if self.measure != "union" and any(len(set(r)) > wide.FAST_TOKENS for rows in sides for r in rows):
+            raise NotImplementedError(f"{self.__name__}: an item of more than {wide.FAST_TOKENS} distinct tokens (measure "
+                                      f"{self.measure!r} has no general kernel)")
+
+    def raw_grid(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
                  prune: bool = True) -> grid.Hits:
         from .. import wide
 
+        l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
-        l_rows = [list(set_operand(v)) for v in left_items]
-        r_rows = [list(set_operand(v)) for v in right_items]
 
         def fast(li, ri):
             vocab = tables.Vocabulary()
@@ -159,7 +187,7 @@ class _IntersectionVsUnion:
             width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
             lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
             rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
-            return grid.jaccard_raw_grid(lt, rt, threshold, prune=prune)
+            return grid.jaccard_raw_grid(lt, rt, threshold, prune=prune, measure=self.measure)
 
         split = wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows])
         if split is None:
@@ -171,8 +199,7 @@ class _IntersectionVsUnion:
                                                        raw=True, device=dev)
         return wide.split_grid(split[0], split[1], fast, general)
 
-    @staticmethod
-    def top_k(left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
+    def top_k(self, left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
               prune: bool = True, groups=None) -> grid.Hits:
         """Per left item the first ``k`` records of ``raw_grid(left_items, right_items, threshold)`` (score descending,
         right index ascending), all of them in canonical order.  ``groups`` (hashables, one per right item): right items
@@ -182,9 +209,8 @@ class _IntersectionVsUnion:
 
         k = grid.check_k(k)
         gids = factorise_groups(groups, len(right_items))
+        l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
-        l_rows = [list(set_operand(v)) for v in left_items]
-        r_rows = [list(set_operand(v)) for v in right_items]
         if any(not r for r in l_rows) and any(not r for r in r_rows):
             raise ZeroDivisionError("division by zero")  # (:13)
 
@@ -196,7 +222,7 @@ class _IntersectionVsUnion:
             width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
             lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
             rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
-            return grid.jaccard_raw_top_k(lt, rt, k, threshold, prune=prune, groups=sub(ri))
+            return grid.jaccard_raw_top_k(lt, rt, k, threshold, prune=prune, groups=sub(ri), measure=self.measure)
 
         split = wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows])
         if split is None:
@@ -210,8 +236,7 @@ class _IntersectionVsUnion:
         return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
 
 
-    @staticmethod
-    def pairs(left_items: Sequence[Operand], right_items: Sequence[Operand], pairs, device=None) -> np.ndarray:
+    def pairs(self, left_items: Sequence[Operand], right_items: Sequence[Operand], pairs, device=None) -> np.ndarray:
         """The score of every listed pair: ``pairs`` is a sequence of ``(i, j)`` positions in the two item lists, or a
         P x 2 integer array; the result is ``[plugin(left_items[i], right_items[j]) for i, j in pairs]`` as a float64 array,
         in O(P) (``nsm_jaccard_raw_pairs``: tables of the listed items only, one launch).  A listed pair of two empty sets
@@ -223,8 +248,9 @@ class _IntersectionVsUnion:
         i, j = wide.check_pair_positions(pairs, len(left_items), len(right_items))
         l_rows = {int(k): list(set_operand(left_items[k])) for k in np.unique(i)}
         r_rows = {int(k): list(set_operand(right_items[k])) for k in np.unique(j)}
-        if any(not l_rows[int(a)] and not r_rows[int(b)] for a, b in zip(i, j)):
+        if any(self.divides_by_zero(set(l_rows[int(a)]), set(r_rows[int(b)])) for a, b in zip(i, j)):
             raise ZeroDivisionError("division by zero")  # (:13)
+        self._check_narrow(l_rows.values(), r_rows.values())
         if len(i) == 0:
             return np.zeros(0, dtype=np.float64)
         dev = device or _device()
@@ -235,7 +261,7 @@ class _IntersectionVsUnion:
             width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
             lt = tables.SetTable.from_padded(_padded_ids(ls, vocab, width), "left", dev, width=width, validate=False, index=False)
             rt = tables.SetTable.from_padded(_padded_ids(rs, vocab, width), "right", dev, width=width, validate=False, index=False)
-            return grid.jaccard_raw_pairs(lt, rt, pi, pj)
+            return grid.jaccard_raw_pairs(lt, rt, pi, pj, measure=self.measure)
 
         general = lambda li, ri: wide.jaccard_any_grid([[l_rows[int(k)]] for k in li], [[r_rows[int(k)]] for k in ri],
                                                        float("-inf"), raw=True, device=dev)
@@ -245,8 +271,7 @@ class _IntersectionVsUnion:
         split = (wide_l, wide_r) if wide_l.any() or wide_r.any() else None
         return wide.split_pairs(split, i, j, fast, general)
 
-    @staticmethod
-    def profile(left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,
+    def profile(self, left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,
                 prune: bool = True) -> grid.ThresholdProfile:
         """``grid.profile_of_hits(raw_grid(left_items, right_items, thresholds[0]), thresholds, ...)`` without the hits:
         per threshold the number of pairs scoring at least that, per item its best score (``-1.0``: none at
@@ -254,9 +279,8 @@ class _IntersectionVsUnion:
         from .. import wide
 
         t = grid.check_thresholds(thresholds)
+        l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
-        l_rows = [list(set_operand(v)) for v in left_items]
-        r_rows = [list(set_operand(v)) for v in right_items]
         if any(not r for r in l_rows) and any(not r for r in r_rows):
             raise ZeroDivisionError("division by zero")  # (:13)
 
@@ -266,7 +290,7 @@ class _IntersectionVsUnion:
             width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
             lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
             rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
-            return grid.jaccard_raw_profile(lt, rt, t, prune=prune)
+            return grid.jaccard_raw_profile(lt, rt, t, prune=prune, measure=self.measure)
 
         general = lambda li, ri: grid.profile_of_hits(
             wide.jaccard_any_grid([[l_rows[k_]] for k_ in li], [[r_rows[k_]] for k_ in ri], float(t[0]), raw=True, device=dev),
@@ -283,9 +307,8 @@ class _IntersectionVsUnion:
 
         margin = grid.check_margin(margin)
         grid.check_thresholds([threshold])
+        l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
-        l_rows = [list(set_operand(v)) for v in left_items]
-        r_rows = [list(set_operand(v)) for v in right_items]
         if any(not r for r in l_rows) and any(not r for r in r_rows):
             raise ZeroDivisionError("division by zero")  # (:13)
 
@@ -295,7 +318,7 @@ class _IntersectionVsUnion:
             width = tables.pick_width(max((len(set(r)) for r in ls), default=1), max((len(set(r)) for r in rs), default=1))
             lt = tables.SetTable.from_rows(ls, "left", dev, vocab, width=width)
             rt = tables.SetTable.from_rows(rs, "right", dev, vocab, width=width)
-            return grid.jaccard_raw_floor_grid(lt, rt, threshold, lf, rf, prune=prune)
+            return grid.jaccard_raw_floor_grid(lt, rt, threshold, lf, rf, prune=prune, measure=self.measure)
 
         general = lambda li, ri: wide.jaccard_any_grid([[l_rows[k_]] for k_ in li], [[r_rows[k_]] for k_ in ri], threshold,
                                                        raw=True, device=dev)
@@ -313,9 +336,8 @@ class _IntersectionVsUnion:
         from .. import wide
 
         grid.check_thresholds([threshold])
+        l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
-        l_rows = [list(set_operand(v)) for v in left_items]
-        r_rows = [list(set_operand(v)) for v in right_items]
         if not l_rows or not r_rows:
             return wide.merge([])
         if wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]) is not None:
@@ -325,7 +347,7 @@ class _IntersectionVsUnion:
         width = tables.pick_width(max((len(set(r)) for r in l_rows), default=1), max((len(set(r)) for r in r_rows), default=1))
         lt = tables.SetTable.from_rows(l_rows, "left", dev, vocab, width=width)
         rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
-        return grid.jaccard_raw_assign(lt, rt, threshold, prune=prune)
+        return grid.jaccard_raw_assign(lt, rt, threshold, prune=prune, measure=self.measure)
 
     def groups(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
                prune: bool = True, same: bool = False) -> grid.MatchGroups:
@@ -337,9 +359,8 @@ class _IntersectionVsUnion:
         from .. import wide
 
         grid.check_thresholds([threshold])
+        l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
-        l_rows = [list(set_operand(v)) for v in left_items]
-        r_rows = [list(set_operand(v)) for v in right_items]
         n_l, n_r = len(l_rows), len(r_rows)
         layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
         if not l_rows or not r_rows:
@@ -351,7 +372,7 @@ class _IntersectionVsUnion:
         width = tables.pick_width(max((len(set(r)) for r in l_rows), default=1), max((len(set(r)) for r in r_rows), default=1))
         lt = tables.SetTable.from_rows(l_rows, "left", dev, vocab, width=width)
         rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
-        return grid.jaccard_raw_groups(lt, rt, threshold, prune=prune, same=same)
+        return grid.jaccard_raw_groups(lt, rt, threshold, prune=prune, same=same, measure=self.measure)
 
     def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> List[np.ndarray]:
         """Near-duplicate clusters inside ONE list (dedupe): the self-join's groups of at least two items, each an
@@ -368,9 +389,8 @@ class _IntersectionVsUnion:
         from .. import wide
 
         grid.check_thresholds([threshold])
+        l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
-        l_rows = [list(set_operand(v)) for v in left_items]
-        r_rows = [list(set_operand(v)) for v in right_items]
         n_l, n_r = len(l_rows), len(r_rows)
         layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
         if not l_rows or not r_rows:
@@ -383,7 +403,7 @@ class _IntersectionVsUnion:
         width = tables.pick_width(max((len(set(r)) for r in l_rows), default=1), max((len(set(r)) for r in r_rows), default=1))
         lt = tables.SetTable.from_rows(l_rows, "left", dev, vocab, width=width)
         rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
-        return grid.jaccard_raw_forest(lt, rt, threshold, prune=prune, same=same)
+        return grid.jaccard_raw_forest(lt, rt, threshold, prune=prune, same=same, measure=self.measure)
 
     def cluster_tree(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> grid.MergeForest:
         """The single-linkage tree of ONE list: the self-join's merge forest (node k is ``items[k]``); ``cut(t).members(2)``
@@ -598,5 +618,30 @@ class _FuzzyMatch:
         return self.forest(items, items, threshold, device=device, prune=prune, same=True)
 
 
+class _IntersectionVsMean(_IntersectionVsUnion):
+    """``2 * len(A & B) / (len(A) + len(B))``: the Sorensen-Dice coefficient.  ``ZeroDivisionError`` when both sets are
+    empty."""
+    __name__ = "intersection_vs_mean"
+    measure = "mean"
+
+
+class _IntersectionVsSmaller(_IntersectionVsUnion):
+    """``len(A & B) / min(len(A), len(B))``: the overlap (Szymkiewicz-Simpson) coefficient -- 1.0 whenever one set holds the
+    other.  ``ZeroDivisionError`` when either set is empty."""
+    __name__ = "intersection_vs_smaller"
+    measure = "smaller"
+
+
+class _IntersectionVsLeft(_IntersectionVsUnion):
+    """``len(A & B) / len(A)``: the containment of the LEFT set in the right one (asymmetric) -- a short definition against
+    a long item that holds all its tokens scores 1.0.  ``ZeroDivisionError`` when the left set is empty."""
+    __name__ = "intersection_vs_left"
+    measure = "left"
+
+
 intersection_vs_union = _IntersectionVsUnion()
+intersection_vs_mean = _IntersectionVsMean()
+intersection_vs_smaller = _IntersectionVsSmaller()
+intersection_vs_left = _IntersectionVsLeft()
 fuzzy_match = _FuzzyMatch()
+PLUGINS = (intersection_vs_union, intersection_vs_mean, intersection_vs_smaller, intersection_vs_left, fuzzy_match)

@@ -128,16 +128,73 @@ def run_grid(launch: Callable[[HitBuffer, int], int], device, capacity: Optional
     raise _lib.NsmLibraryError(f"{what}: hit count changed between two identical launches")
 
 
+# ------------------------------------------------------------------------------- token-set measures
+def check_measure(measure) -> int:
+    """The code (``_lib.MEASURES``, include/nsm_hip_measures.h) of a measure name: "union" (Jaccard, the default of every
+    ``jaccard_*`` wrapper), "mean" (Dice), "smaller" (overlap), "left" (containment of left in right)."""
+    try:
+        return _lib.MEASURES[measure]
+    except (KeyError, TypeError):
+        raise ValueError(f"measure must be one of {tuple(_lib.MEASURES)}, not {measure!r}") from None
+
+
+def measure_divides_by_zero(measure: str, a: int, b: int) -> bool:
+    """Whether the measure's denominator is zero for a left set of ``a`` and a right set of ``b`` tokens."""
+    code = check_measure(measure)
+    if code == _lib.MEASURE_SMALLER:
+        return a == 0 or b == 0
+    if code == _lib.MEASURE_LEFT:
+        return a == 0
+    return a == 0 and b == 0
+
+
+def check_measure_grid(measure: str, left_empty: bool, n_left: int, right_empty: bool, n_right: int) -> None:
+    """The whole-grid ``ZeroDivisionError`` of a measure: ``left_empty`` / ``right_empty`` say whether that side holds an
+    empty set.  "union" / "mean": an empty set on both sides; "smaller": an empty set on either side while the other has
+    items; "left": an empty left set while the right side has items."""
+    code = check_measure(measure)
+    if code == _lib.MEASURE_SMALLER:
+        bad = (left_empty and n_right > 0) or (right_empty and n_left > 0)
+    elif code == _lib.MEASURE_LEFT:
+        bad = left_empty and n_right > 0
+    else:
+        bad = left_empty and right_empty
+    if bad:
+        raise ZeroDivisionError("division by zero")
+
+
+def _set_entry(entry: str, measure: str):
+    """(C entry, what it takes between the tables and the rest) of a ``nsm_jaccard_*`` per-item query under ``measure``:
+    the entry itself for "union", else its ``nsm_set_*`` counterpart with the measure code behind the tables."""
+    code = check_measure(measure)
+    if code == _lib.MEASURE_UNION:
+        return entry, ()
+    entry = entry.replace("nsm_jaccard_", "nsm_set_")
+    _lib.entry(entry)  # (NsmLibraryError for a library without the measures)
+    return entry, (code,)
+
+
+def _check_set_sides(left: SetTable, right: SetTable, measure: str) -> None:
+    """The preconditions of the RAW per-item Jaccard wrappers: the two paddings, then the measure's division by zero."""
+    if left.side != "left" or right.side != "right":
+        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
+    check_measure_grid(measure, left.has_empty, left.n, right.has_empty, right.n)
+
+
 # ------------------------------------------------------------------------------- RAW grids
 def jaccard_raw_grid(
     left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
-    index: Optional[bool] = None, defer: bool = False,
+    index: Optional[bool] = None, defer: bool = False, measure: str = "union",
 ) -> Hits:
     """``intersection_vs_union`` on one set per item, all N x M pairs, hits ``>= threshold``.
     ``index``: None = the library decides (candidates from the right table's global inverted index where its posting
     statistics say they are few, from a per-tile index at low thresholds, else the signature kernel over all pairs);
     True = force an index (the global one when the right table carries it), "tile" = force the per-tile index,
-    False = never an index."""
+    False = never an index.
+    ``measure``: another token-set measure (``check_measure``) -- its threshold grid is the floor grid without floors
+    (``nsm_set_raw_floor_grid``, the per-item sweep); ``index`` does not apply to it."""
+    if check_measure(measure) != _lib.MEASURE_UNION:
+        return jaccard_raw_floor_grid(left, right, threshold, prune=prune, capacity=capacity, defer=defer, measure=measure)
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
     if left.has_empty and right.has_empty:
@@ -265,15 +322,16 @@ def _top_k(launch: Callable, n_left: int, n_right: int, k: int, device, what: st
 
 
 def _raw_top_k(entry: str, left, right, device, k: int, threshold: float, prune: bool, stats: Optional[list], groups,
-               id_limit: int = 0) -> Hits:
+               id_limit: int = 0, head: tuple = ()) -> Hits:
     """A RAW top-k query through the C entry ``entry``, or with ``groups`` through ``entry + "_grouped"`` (the same
-    arguments with the group column in front of the threshold)."""
+    arguments with the group column in front of the threshold).  ``head``: what the entry takes right behind the tables
+    (``_set_entry``)."""
     what = entry if groups is None else entry + "_grouped"
     gcol = None if groups is None else _device_groups(groups, right.n, right.orig, device, what)
     fn = getattr(_lib.load(), what)
     ls, rs = left.struct(), right.struct()
     flags = _lib.FLAG_PRUNE if prune else 0
-    group_arg = () if gcol is None else (gcol.data_ptr(),)
+    group_arg = head if gcol is None else (*head, gcol.data_ptr())
     return _top_k(lambda out, cnt, st, kk, stream: fn(
         ls, rs, *group_arg, float(threshold), kk, flags, out.data_ptr(), cnt.data_ptr(), st.data_ptr(), stream),
         left.n, right.n, k, device, what, stats, id_limit)
@@ -292,18 +350,19 @@ def indel_raw_top_k(left: StrTable, right: StrTable, k: int, threshold: float, p
 
 
 def jaccard_raw_top_k(left: SetTable, right: SetTable, k: int, threshold: float, prune: bool = True,
-                      stats: Optional[list] = None, groups=None) -> Hits:
+                      stats: Optional[list] = None, groups=None, measure: str = "union") -> Hits:
     """``intersection_vs_union`` counterpart of ``indel_raw_top_k``; stats[2] counts the pairs past the signature bound,
-    stats[3] the exact merges.  ``groups`` as there (``nsm_jaccard_raw_top_k_grouped``)."""
+    stats[3] the exact merges.  ``groups`` as there (``nsm_jaccard_raw_top_k_grouped``).  ``measure``: another token-set
+    measure (``check_measure``: ``nsm_set_raw_top_k``)."""
     k = check_k(k)
+    entry, head = _set_entry("nsm_jaccard_raw_top_k", measure)
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
     if groups is not None and len(groups) != right.n:  # (a wrong length is reported before the division by zero)
-        raise ValueError(f"nsm_jaccard_raw_top_k_grouped: {len(groups)} group ids for {right.n} right items")
-    if left.has_empty and right.has_empty:
-        raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
+        raise ValueError(f"{entry}_grouped: {len(groups)} group ids for {right.n} right items")
+    check_measure_grid(measure, left.has_empty, left.n, right.has_empty, right.n)  # score_functions.py:13, as for the grid
     id_limit = max(left.id_limit, right.id_limit) if left.id_limit and right.id_limit else 0
-    return _raw_top_k("nsm_jaccard_raw_top_k", left, right, left.ids.device, k, threshold, prune, stats, groups, id_limit)
+    return _raw_top_k(entry, left, right, left.ids.device, k, threshold, prune, stats, groups, id_limit, head)
 
 
 # ------------------------------------------------------------------------------- levels top-k
@@ -347,7 +406,7 @@ def _id_count(orig: torch.Tensor, n: int, what: str) -> int:
 
 
 def _levels_top_k(entry: str, tables: tuple, left, right, device, k: int, threshold: float, category_mode: int, prune: bool,
-                  banned, stats: Optional[list]) -> Hits:
+                  banned, stats: Optional[list], head: tuple = ()) -> Hits:
     """A levels top-k query through the C entry ``entry``: ``tables`` in the entry's argument order, ``left`` / ``right``
     the two item tables among them (row counts, caller ids, the encoder's category predicate)."""
     fn = getattr(_lib.load(), entry)
@@ -358,7 +417,7 @@ def _levels_top_k(entry: str, tables: tuple, left, right, device, k: int, thresh
     bs, bj = banned_csr(banned, _id_count(left.orig, left.n, "banned") if banned is not None else 0, device)
     ptr = lambda t: 0 if t is None else t.data_ptr()
     return _top_k(lambda out, cnt, st, kk, stream: fn(
-        *structs, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
+        *structs, *head, float(threshold), kk, int(category_mode), flags, ptr(bs), ptr(bj), out.data_ptr(), cnt.data_ptr(),
         st.data_ptr(), stream), left.n, right.n, k, device, entry, stats)
 
 
@@ -376,16 +435,18 @@ def indel_levels_top_k(left: LevelItems, left_strings: StrTable, right: LevelIte
 
 
 def jaccard_levels_top_k(left: SetTable, right: SetTable, k: int, threshold: float, category_mode: int = _lib.CAT_NONE,
-                         prune: bool = True, banned=None, stats: Optional[list] = None) -> Hits:
+                         prune: bool = True, banned=None, stats: Optional[list] = None, measure: str = "union") -> Hits:
     """``intersection_vs_union`` counterpart of ``indel_levels_top_k`` (tables from ``SetTable.from_levels`` /
-    ``from_nested_arrays`` with ``partition=False``); stats[2] counts the pairs past the signature bound."""
+    ``from_nested_arrays`` with ``partition=False``); stats[2] counts the pairs past the signature bound.  ``measure``:
+    another token-set measure (``check_measure``: ``nsm_set_levels_top_k``)."""
     k = check_k(k)
+    entry, head = _set_entry("nsm_jaccard_levels_top_k", measure)
     if left.nlev is None or right.nlev is None:
         raise ValueError("levels top-k needs tables built with SetTable.from_levels")
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    return _levels_top_k("nsm_jaccard_levels_top_k", (left, right), left, right, left.ids.device, k, threshold,
-                         category_mode, prune, banned, stats)
+    return _levels_top_k(entry, (left, right), left, right, left.ids.device, k, threshold, category_mode, prune, banned, stats,
+                         head)
 
 
 # ------------------------------------------------------------------------------- threshold profiles
@@ -486,22 +547,21 @@ def indel_raw_profile(left: StrTable, right: StrTable, thresholds, prune: bool =
 
 
 def jaccard_raw_profile(left: SetTable, right: SetTable, thresholds, prune: bool = True,
-                        stats: Optional[list] = None) -> ThresholdProfile:
-    """``intersection_vs_union`` counterpart of ``indel_raw_profile``; preconditions as for ``jaccard_raw_top_k``."""
+                        stats: Optional[list] = None, measure: str = "union") -> ThresholdProfile:
+    """``intersection_vs_union`` counterpart of ``indel_raw_profile``; preconditions as for ``jaccard_raw_top_k``.
+    ``measure``: another token-set measure (``check_measure``: ``nsm_set_raw_profile``)."""
     t = check_thresholds(thresholds)
-    if left.side != "left" or right.side != "right":
-        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    if left.has_empty and right.has_empty:
-        raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
-    lib = _lib.load()
+    entry, head = _set_entry("nsm_jaccard_raw_profile", measure)
+    _check_set_sides(left, right, measure)  # score_functions.py:13, as for the grid
+    fn = getattr(_lib.load(), entry)
     ls, rs = left.struct(), right.struct()
     flags = _lib.FLAG_PRUNE if prune else 0
-    return _profile(lambda lad, n, pairs, lb, rb, st, stream: lib.nsm_jaccard_raw_profile(ls, rs, lad, n, flags, pairs, lb, rb, st, stream),
-                    t, left.orig, left.n, right.orig, right.n, left.ids.device, "nsm_jaccard_raw_profile", stats)
+    return _profile(lambda lad, n, pairs, lb, rb, st, stream: fn(ls, rs, *head, lad, n, flags, pairs, lb, rb, st, stream),
+                    t, left.orig, left.n, right.orig, right.n, left.ids.device, entry, stats)
 
 
 def _levels_profile(entry: str, tables: tuple, left, right, device, t: np.ndarray, category_mode: int, prune: bool, banned,
-                    stats: Optional[list]) -> ThresholdProfile:
+                    stats: Optional[list], head: tuple = ()) -> ThresholdProfile:
     fn = getattr(_lib.load(), entry)
     if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
         category_mode = left.category_mode
@@ -509,7 +569,7 @@ def _levels_profile(entry: str, tables: tuple, left, right, device, t: np.ndarra
     flags = _lib.FLAG_PRUNE if prune else 0
     bs, bj = banned_csr(banned, _id_count(left.orig, left.n, "banned") if banned is not None else 0, device)
     ptr = lambda x: 0 if x is None else x.data_ptr()
-    return _profile(lambda lad, n, pairs, lb, rb, st, stream: fn(*structs, lad, n, int(category_mode), flags, ptr(bs), ptr(bj),
+    return _profile(lambda lad, n, pairs, lb, rb, st, stream: fn(*structs, *head, lad, n, int(category_mode), flags, ptr(bs), ptr(bj),
                                                                  pairs, lb, rb, st, stream),
                     t, left.orig, left.n, right.orig, right.n, device, entry, stats)
 
@@ -525,15 +585,16 @@ def indel_levels_profile(left: LevelItems, left_strings: StrTable, right: LevelI
 
 
 def jaccard_levels_profile(left: SetTable, right: SetTable, thresholds, category_mode: int = _lib.CAT_NONE, prune: bool = True,
-                           banned=None, stats: Optional[list] = None) -> ThresholdProfile:
-    """``intersection_vs_union`` counterpart of ``indel_levels_profile`` (``jaccard_levels_top_k``'s preconditions)."""
+                           banned=None, stats: Optional[list] = None, measure: str = "union") -> ThresholdProfile:
+    """``intersection_vs_union`` counterpart of ``indel_levels_profile`` (``jaccard_levels_top_k``'s preconditions and
+    ``measure``: ``nsm_set_levels_profile``)."""
     t = check_thresholds(thresholds)
+    entry, head = _set_entry("nsm_jaccard_levels_profile", measure)
     if left.nlev is None or right.nlev is None:
         raise ValueError("levels profile needs tables built with SetTable.from_levels")
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    return _levels_profile("nsm_jaccard_levels_profile", (left, right), left, right, left.ids.device, t, category_mode, prune,
-                           banned, stats)
+    return _levels_profile(entry, (left, right), left, right, left.ids.device, t, category_mode, prune, banned, stats, head)
 
 
 # ------------------------------------------------------------------------------- floor grids and best matches
@@ -607,9 +668,10 @@ def _floor_column(floor, ids: int, device, what: str) -> Optional[torch.Tensor]:
 
 
 def _floor_grid(entry: str, structs: list, middle: tuple, left, right, device, threshold: float, left_floor, right_floor,
-                stats: Optional[list], capacity: Optional[int]) -> Hits:
-    """A floor grid through the C entry ``entry``: ``structs`` the tables in the entry's argument order, ``middle`` what it
-    takes between the floors and the hit buffer, ``left`` / ``right`` the two tables whose caller ids the floors go by."""
+                stats: Optional[list], capacity: Optional[int], defer: bool = False):
+    """A floor grid through the C entry ``entry``: ``structs`` the tables in the entry's argument order (and what it takes
+    right behind them), ``middle`` what it takes between the floors and the hit buffer, ``left`` / ``right`` the two tables
+    whose caller ids the floors go by.  ``defer``: as for ``run_grid``."""
     dev = _require_gpu(device)
     fn = getattr(_lib.load(), entry)
     ids_l, ids_r = _left_id_limit(left.orig, left.n), _left_id_limit(right.orig, right.n)
@@ -628,7 +690,7 @@ def _floor_grid(entry: str, structs: list, middle: tuple, left, right, device, t
                   buf.count.data_ptr(), st.data_ptr(), stream)
 
     # (every reported id is below the larger limit: the sort's key width; an empty side reports nothing)
-    hits = run_grid(launch, dev, capacity, entry, id_limit=max(ids_l, ids_r) if ids_l and ids_r else 0)
+    hits = run_grid(launch, dev, capacity, entry, id_limit=max(ids_l, ids_r) if ids_l and ids_r else 0, defer=defer)
     if stats is not None:
         stats[:] = [int(v) for v in st.tolist()]
     return hits
@@ -646,26 +708,27 @@ def indel_raw_floor_grid(left: StrTable, right: StrTable, threshold: float, left
 
 
 def jaccard_raw_floor_grid(left: SetTable, right: SetTable, threshold: float, left_floor=None, right_floor=None,
-                           prune: bool = True, stats: Optional[list] = None, capacity: Optional[int] = None) -> Hits:
-    """``intersection_vs_union`` counterpart of ``indel_raw_floor_grid``; preconditions as for ``jaccard_raw_top_k``."""
-    if left.side != "left" or right.side != "right":
-        raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    if left.has_empty and right.has_empty:
-        raise ZeroDivisionError("division by zero")  # score_functions.py:13, as for the grid
+                           prune: bool = True, stats: Optional[list] = None, capacity: Optional[int] = None,
+                           defer: bool = False, measure: str = "union") -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_raw_floor_grid``; preconditions as for ``jaccard_raw_top_k``.
+    ``measure``: another token-set measure (``check_measure``: ``nsm_set_raw_floor_grid``); ``defer`` as for the grids."""
+    entry, head = _set_entry("nsm_jaccard_raw_floor_grid", measure)
+    _check_set_sides(left, right, measure)  # score_functions.py:13, as for the grid
     flags = _lib.FLAG_PRUNE if prune else 0
-    return _floor_grid("nsm_jaccard_raw_floor_grid", [left.struct(), right.struct()], (flags,), left, right, left.ids.device,
-                       threshold, left_floor, right_floor, stats, capacity)
+    return _floor_grid(entry, [left.struct(), right.struct(), *head], (flags,), left, right, left.ids.device,
+                       threshold, left_floor, right_floor, stats, capacity, defer)
 
 
 def _levels_floor_grid(entry: str, tables: tuple, left, right, device, threshold: float, left_floor, right_floor,
-                       category_mode: int, prune: bool, banned, stats: Optional[list], capacity: Optional[int]) -> Hits:
+                       category_mode: int, prune: bool, banned, stats: Optional[list], capacity: Optional[int],
+                       head: tuple = (), defer: bool = False) -> Hits:
     if left.category_mode is not None:  # the encoder may have dropped the predicate (no categories given)
         category_mode = left.category_mode
     bs, bj = banned_csr(banned, _id_count(left.orig, left.n, "banned") if banned is not None else 0, device)
     ptr = lambda t: 0 if t is None else t.data_ptr()
     middle = (int(category_mode), _lib.FLAG_PRUNE if prune else 0, ptr(bs), ptr(bj))
-    return _floor_grid(entry, [t.struct() for t in tables], middle, left, right, device, threshold, left_floor, right_floor,
-                       stats, capacity)
+    return _floor_grid(entry, [*(t.struct() for t in tables), *head], middle, left, right, device, threshold, left_floor,
+                       right_floor, stats, capacity, defer)
 
 
 def indel_levels_floor_grid(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable,
@@ -681,14 +744,17 @@ def indel_levels_floor_grid(left: LevelItems, left_strings: StrTable, right: Lev
 
 def jaccard_levels_floor_grid(left: SetTable, right: SetTable, threshold: float, left_floor=None, right_floor=None,
                               category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
-                              stats: Optional[list] = None, capacity: Optional[int] = None) -> Hits:
-    """``intersection_vs_union`` counterpart of ``indel_levels_floor_grid`` (``jaccard_levels_top_k``'s preconditions)."""
+                              stats: Optional[list] = None, capacity: Optional[int] = None, defer: bool = False,
+                              measure: str = "union") -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_levels_floor_grid`` (``jaccard_levels_top_k``'s preconditions and
+    ``measure``: ``nsm_set_levels_floor_grid``; ``defer`` as for the grids)."""
+    entry, head = _set_entry("nsm_jaccard_levels_floor_grid", measure)
     if left.nlev is None or right.nlev is None:
         raise ValueError("levels floor grid needs tables built with SetTable.from_levels")
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    return _levels_floor_grid("nsm_jaccard_levels_floor_grid", (left, right), left, right, left.ids.device, threshold,
-                              left_floor, right_floor, category_mode, prune, banned, stats, capacity)
+    return _levels_floor_grid(entry, (left, right), left, right, left.ids.device, threshold, left_floor, right_floor,
+                              category_mode, prune, banned, stats, capacity, head, defer)
 
 
 def floors_of_profile(prof: ThresholdProfile, margin: float, mutual: bool):
@@ -723,10 +789,10 @@ def indel_raw_best(left: StrTable, right: StrTable, margin: float = 0.0, thresho
 
 
 def jaccard_raw_best(left: SetTable, right: SetTable, margin: float = 0.0, threshold: float = 0.0, mutual: bool = False,
-                     prune: bool = True, stats: Optional[list] = None) -> Hits:
-    """``intersection_vs_union`` counterpart of ``indel_raw_best``; preconditions as for ``jaccard_raw_top_k``."""
-    return _best(lambda t, st: jaccard_raw_profile(left, right, t, prune=prune, stats=st),
-                 lambda lf, rf, st: jaccard_raw_floor_grid(left, right, threshold, lf, rf, prune=prune, stats=st),
+                     prune: bool = True, stats: Optional[list] = None, measure: str = "union") -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_raw_best``; preconditions and ``measure`` as for ``jaccard_raw_top_k``."""
+    return _best(lambda t, st: jaccard_raw_profile(left, right, t, prune=prune, stats=st, measure=measure),
+                 lambda lf, rf, st: jaccard_raw_floor_grid(left, right, threshold, lf, rf, prune=prune, stats=st, measure=measure),
                  margin, threshold, mutual, stats)
 
 
@@ -743,11 +809,12 @@ def indel_levels_best(left: LevelItems, left_strings: StrTable, right: LevelItem
 
 def jaccard_levels_best(left: SetTable, right: SetTable, margin: float = 0.0, threshold: float = 0.0, mutual: bool = False,
                         category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
-                        stats: Optional[list] = None) -> Hits:
-    """``intersection_vs_union`` counterpart of ``indel_levels_best`` (``jaccard_levels_top_k``'s preconditions)."""
-    return _best(lambda t, st: jaccard_levels_profile(left, right, t, category_mode=category_mode, prune=prune, banned=banned, stats=st),
+                        stats: Optional[list] = None, measure: str = "union") -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_levels_best`` (``jaccard_levels_top_k``'s preconditions and ``measure``)."""
+    return _best(lambda t, st: jaccard_levels_profile(left, right, t, category_mode=category_mode, prune=prune, banned=banned,
+                                                      stats=st, measure=measure),
                  lambda lf, rf, st: jaccard_levels_floor_grid(left, right, threshold, lf, rf, category_mode=category_mode,
-                                                              prune=prune, banned=banned, stats=st),
+                                                              prune=prune, banned=banned, stats=st, measure=measure),
                  margin, threshold, mutual, stats)
 
 
@@ -805,7 +872,7 @@ def _row_map(orig: torch.Tensor, n: int, device) -> torch.Tensor:
     return rows[:ids] if ids else rows[:0]
 
 
-def _pairs(entry: str, tables: tuple, left, right, device, i, j) -> np.ndarray:
+def _pairs(entry: str, tables: tuple, left, right, device, i, j, head: tuple = ()) -> np.ndarray:
     """A pairs query through the C entry ``entry``: ``tables`` in the entry's argument order, ``left`` / ``right`` the two
     tables among them whose rows the caller ids name."""
     i, j = check_pair_ids(i, j)
@@ -822,7 +889,7 @@ def _pairs(entry: str, tables: tuple, left, right, device, i, j) -> np.ndarray:
     lmap, rmap = _row_map(left.orig, left.n, dev), _row_map(right.orig, right.n, dev)
     structs = [t.struct() for t in tables]
     ptr = lambda t: t.data_ptr() if t.numel() else 0
-    _lib.check(fn(*structs, ptr(lmap), int(lmap.numel()), ptr(rmap), int(rmap.numel()), records.data_ptr(), n,
+    _lib.check(fn(*structs, *head, ptr(lmap), int(lmap.numel()), ptr(rmap), int(rmap.numel()), records.data_ptr(), n,
                   torch.cuda.current_stream(dev).cuda_stream), entry)
     return records[:, 0].cpu().numpy()
 
@@ -835,13 +902,15 @@ def indel_raw_pairs(left: StrTable, right: StrTable, i, j) -> np.ndarray:
     return _pairs("nsm_indel_raw_pairs", (left, right), left, right, left.codes.device, i, j)
 
 
-def jaccard_raw_pairs(left: SetTable, right: SetTable, i, j) -> np.ndarray:
+def jaccard_raw_pairs(left: SetTable, right: SetTable, i, j, measure: str = "union") -> np.ndarray:
     """``intersection_vs_union`` counterpart of ``indel_raw_pairs``; a pair of two empty sets gets ``-1.0`` (the plugin
-    raises ``ZeroDivisionError`` for it)."""
+    raises ``ZeroDivisionError`` for it).  ``measure``: another token-set measure (``check_measure``:
+    ``nsm_set_raw_pairs``), ``-1.0`` wherever its denominator is zero."""
     i, j = check_pair_ids(i, j)
+    entry, head = _set_entry("nsm_jaccard_raw_pairs", measure)
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    return _pairs("nsm_jaccard_raw_pairs", (left, right), left, right, left.ids.device, i, j)
+    return _pairs(entry, (left, right), left, right, left.ids.device, i, j, head)
 
 
 def indel_levels_pairs(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, i, j) -> np.ndarray:
@@ -852,27 +921,37 @@ def indel_levels_pairs(left: LevelItems, left_strings: StrTable, right: LevelIte
     return _pairs("nsm_indel_levels_pairs", (left, left_strings, right, right_strings), left, right, left.first.device, i, j)
 
 
-def jaccard_levels_pairs(left: SetTable, right: SetTable, i, j) -> np.ndarray:
+def jaccard_levels_pairs(left: SetTable, right: SetTable, i, j, measure: str = "union") -> np.ndarray:
     """``intersection_vs_union`` counterpart of ``indel_levels_pairs`` (tables from ``SetTable.from_levels`` /
-    ``from_nested_arrays`` with ``partition=False``); ``-1.0`` also for a pair that compares two empty levels."""
+    ``from_nested_arrays`` with ``partition=False``); ``-1.0`` also for a pair that compares two empty levels.
+    ``measure``: another token-set measure (``nsm_set_levels_pairs``), ``-1.0`` for a pair with a step that divides by zero."""
     i, j = check_pair_ids(i, j)
+    entry, head = _set_entry("nsm_jaccard_levels_pairs", measure)
     if left.nlev is None or right.nlev is None:
         raise ValueError("levels pairs need tables built with SetTable.from_levels")
     if left.side != "left" or right.side != "right":
         raise ValueError("tables must be encoded with side='left' and side='right' (distinct padding)")
-    return _pairs("nsm_jaccard_levels_pairs", (left, right), left, right, left.ids.device, i, j)
+    return _pairs(entry, (left, right), left, right, left.ids.device, i, j, head)
 
 
 # ------------------------------------------------------------------------------- levels grids
 def jaccard_levels_grid(
     left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True,
-    capacity: Optional[int] = None, index: Optional[bool] = None, defer: bool = False,
+    capacity: Optional[int] = None, index: Optional[bool] = None, defer: bool = False, measure: str = "union", banned=None,
 ) -> Hits:
     """``compare_terms`` with ``intersection_vs_union`` over suffix-nested levels.
     ``index``: None = the library decides (candidates from the right table's global inverted index where its posting
     statistics say they are few, from a per-tile index at low thresholds, else the filter kernel over all pairs);
     True = force an index (the global one when the right table carries it), "tile" = force the per-tile index,
-    False = never an index."""
+    False = never an index.
+    ``measure``: another token-set measure (``check_measure``) -- its threshold grid is the floor grid without floors
+    (``nsm_set_levels_floor_grid``: tables encoded with ``partition=False``, and ``banned`` as ``jaccard_levels_top_k``
+    takes it; ``index`` does not apply)."""
+    if check_measure(measure) != _lib.MEASURE_UNION:
+        return jaccard_levels_floor_grid(left, right, threshold, category_mode=category_mode, prune=prune, banned=banned,
+                                         capacity=capacity, defer=defer, measure=measure)
+    if banned is not None:
+        raise ValueError("banned: the Jaccard threshold grid takes no blacklist (jaccard_levels_floor_grid does)")
     if left.nlev is None or right.nlev is None:
         raise ValueError("levels grid needs tables built with SetTable.from_levels")
     lib = _lib.load()
@@ -1132,9 +1211,9 @@ def indel_raw_assign(left: StrTable, right: StrTable, threshold: float, prune: b
 
 
 def jaccard_raw_assign(left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
-                       index: Optional[bool] = None, route=None, stats: Optional[list] = None) -> Hits:
-    """``intersection_vs_union`` counterpart of ``indel_raw_assign``."""
-    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True)
+                       index: Optional[bool] = None, route=None, stats: Optional[list] = None, measure: str = "union") -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_raw_assign`` (``measure`` as for ``jaccard_raw_grid``)."""
+    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True, measure=measure)
     return _assign_pending(pending, left, right, route, stats)
 
 
@@ -1150,10 +1229,10 @@ def indel_levels_assign(left: LevelItems, left_strings: StrTable, right: LevelIt
 
 def jaccard_levels_assign(left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE,
                           prune: bool = True, capacity: Optional[int] = None, index: Optional[bool] = None, route=None,
-                          stats: Optional[list] = None) -> Hits:
-    """``intersection_vs_union`` counterpart of ``indel_levels_assign``."""
+                          stats: Optional[list] = None, measure: str = "union", banned=None) -> Hits:
+    """``intersection_vs_union`` counterpart of ``indel_levels_assign`` (``measure``, ``banned`` as for ``jaccard_levels_grid``)."""
     pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
-                                  index=index, defer=True)
+                                  index=index, defer=True, measure=measure, banned=banned)
     return _assign_pending(pending, left, right, route, stats)
 
 
@@ -1328,9 +1407,9 @@ def indel_raw_groups(left: StrTable, right: StrTable, threshold: float, prune: b
 
 def jaccard_raw_groups(left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
                        index: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
-                       stats: Optional[list] = None) -> MatchGroups:
-    """``intersection_vs_union`` counterpart of ``indel_raw_groups``."""
-    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True)
+                       stats: Optional[list] = None, measure: str = "union") -> MatchGroups:
+    """``intersection_vs_union`` counterpart of ``indel_raw_groups`` (``measure`` as for ``jaccard_raw_grid``)."""
+    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True, measure=measure)
     return _groups_pending(pending, left, right, same, min_score, stats)
 
 
@@ -1346,10 +1425,11 @@ def indel_levels_groups(left: LevelItems, left_strings: StrTable, right: LevelIt
 
 def jaccard_levels_groups(left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE,
                           prune: bool = True, capacity: Optional[int] = None, index: Optional[bool] = None, same: bool = False,
-                          min_score: Optional[float] = None, stats: Optional[list] = None) -> MatchGroups:
-    """``intersection_vs_union`` counterpart of ``indel_levels_groups``."""
+                          min_score: Optional[float] = None, stats: Optional[list] = None, measure: str = "union",
+                          banned=None) -> MatchGroups:
+    """``intersection_vs_union`` counterpart of ``indel_levels_groups`` (``measure``, ``banned`` as for ``jaccard_levels_grid``)."""
     pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
-                                  index=index, defer=True)
+                                  index=index, defer=True, measure=measure, banned=banned)
     return _groups_pending(pending, left, right, same, min_score, stats)
 
 
@@ -1594,9 +1674,9 @@ def indel_raw_forest(left: StrTable, right: StrTable, threshold: float, prune: b
 
 def jaccard_raw_forest(left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
                        index: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
-                       stats: Optional[list] = None) -> MergeForest:
-    """``intersection_vs_union`` counterpart of ``indel_raw_forest``."""
-    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True)
+                       stats: Optional[list] = None, measure: str = "union") -> MergeForest:
+    """``intersection_vs_union`` counterpart of ``indel_raw_forest`` (``measure`` as for ``jaccard_raw_grid``)."""
+    pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True, measure=measure)
     return _forest_pending(pending, left, right, threshold, same, min_score, stats)
 
 
@@ -1612,8 +1692,9 @@ def indel_levels_forest(left: LevelItems, left_strings: StrTable, right: LevelIt
 
 def jaccard_levels_forest(left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE,
                           prune: bool = True, capacity: Optional[int] = None, index: Optional[bool] = None, same: bool = False,
-                          min_score: Optional[float] = None, stats: Optional[list] = None) -> MergeForest:
-    """``intersection_vs_union`` counterpart of ``indel_levels_forest``."""
+                          min_score: Optional[float] = None, stats: Optional[list] = None, measure: str = "union",
+                          banned=None) -> MergeForest:
+    """``intersection_vs_union`` counterpart of ``indel_levels_forest`` (``measure``, ``banned`` as for ``jaccard_levels_grid``)."""
     pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
-                                  index=index, defer=True)
+                                  index=index, defer=True, measure=measure, banned=banned)
     return _forest_pending(pending, left, right, threshold, same, min_score, stats)

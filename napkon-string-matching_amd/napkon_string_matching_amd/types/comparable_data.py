@@ -18,6 +18,7 @@ they are resolved on the host, in pair order, against the same blacklist / categ
 """
 from __future__ import annotations
 
+import itertools
 import json
 import logging
 from contextlib import contextmanager
@@ -328,8 +329,8 @@ class ComparableData:
         if plugin.kind == "sets":
             sets = lambda levels: [list(score_functions.set_operand(lv)) for lv in levels]
             sl, sr = sets(left), sets(right)
-            if _divides_by_zero(sl, _empty_levels(sl), sr, _empty_levels(sr)):
-                raise ZeroDivisionError("division by zero")  # an empty-vs-empty level is visited
+            if _divides_by_zero(sl, _empty_levels(sl), sr, _empty_levels(sr), plugin.divides_by_zero):
+                raise ZeroDivisionError("division by zero")  # a step the plugin divides by zero at is visited
         hits = _levels_grid(plugin, [list(left)], [list(right)], float("-inf"), None, None)
         return float(hits.score[0])
 
@@ -517,8 +518,8 @@ class ComparableData:
                 score[p] = 0.0
             elif len(a) == 0 or len(b) == 0:
                 raise IndexError("list index out of range")
-            elif is_sets and empty[("l", int(pi[p]))] and empty[("r", int(pj[p]))] and \
-                    _divides_by_zero(a, empty[("l", int(pi[p]))], b, empty[("r", int(pj[p]))]):
+            elif is_sets and (empty[("l", int(pi[p]))] or empty[("r", int(pj[p]))]) and \
+                    _divides_by_zero(a, empty[("l", int(pi[p]))], b, empty[("r", int(pj[p]))], pre.plugin.divides_by_zero):
                 raise ZeroDivisionError("division by zero")
             else:
                 todo.append(p)
@@ -614,6 +615,8 @@ class ComparableData:
                 raise IndexError("single positional indexer is out-of-bounds")  # df.iloc[0] at :465
             cl, cr = list(lf[category_column]), list(rf[category_column])
             cats = _Categories(cl, cr, cl[first[0]], cr[first[1]])
+            if per_item is None and getattr(plugin, "measure", "union") != "union":
+                per_item = f"score_func {score_func}"  # (its grid is a per-item sweep: floors_levels.hip without floors)
             if per_item is not None and not cats.on_device:
                 raise NotImplementedError(f"{per_item} with more than 64 distinct category labels (the predicate must run on "
                                           "the device, where each item keeps its list)")
@@ -631,7 +634,8 @@ class ComparableData:
         nlev_r = np.array([len(v) for v in levels_r], dtype=np.int64)
         extra_hits: List[Tuple[int, int]] = []  # zero-level x zero-level pairs score 0
         _raise_first_pair_error(
-            plugin.kind == "sets", levels_l, levels_r, nlev_l, nlev_r, n_r, survives, extra_hits
+            plugin.kind == "sets", levels_l, levels_r, nlev_l, nlev_r, n_r, survives, extra_hits,
+            getattr(plugin, "divides_by_zero", None)
         )
 
         # ---- device grid over the items that have at least one level
@@ -829,10 +833,11 @@ def remove_existing_mappings(
 def _resolve_plugin(score_func):
     if isinstance(score_func, str):
         return getattr(score_functions, score_func)
-    if score_func in (score_functions.intersection_vs_union, score_functions.fuzzy_match):
+    if any(score_func is plugin for plugin in score_functions.PLUGINS):
         return score_func
     raise NotImplementedError(
-        "only this package's score functions (intersection_vs_union, fuzzy_match) have a device implementation"
+        "only this package's score functions (" + ", ".join(p.__name__ for p in score_functions.PLUGINS) +
+        ") have a device implementation"
     )
 
 
@@ -912,13 +917,18 @@ def _empty_levels(levels: Sequence[Sequence]) -> frozenset:
     return frozenset(k for k, lv in enumerate(levels) if len(lv) == 0 and (k >= 1 or n == 1))
 
 
-def _divides_by_zero(levels_l, empty_l: frozenset, levels_r, empty_r: frozenset) -> bool:
-    """Does ``compare_terms`` reach a step at which BOTH level sets are empty (score_functions.py:13)?"""
+def _divides_by_zero(levels_l, empty_l: frozenset, levels_r, empty_r: frozenset, predicate=None) -> bool:
+    """Does ``compare_terms`` reach a step at which the plugin divides by zero?  ``predicate(a, b)``: the plugin's
+    ``divides_by_zero`` on the sizes of the step's two sets -- every rule only asks which of them are empty, so 0 / 1 stand
+    in for the sizes; None: BOTH level sets empty (score_functions.py:13)."""
     n_l, n_r = len(levels_l), len(levels_r)
-    return any(min(s, n_l - 1) in empty_l and min(s, n_r - 1) in empty_r for s in range(1, max(n_l, n_r) + 1))
+    if predicate is None:
+        return any(min(s, n_l - 1) in empty_l and min(s, n_r - 1) in empty_r for s in range(1, max(n_l, n_r) + 1))
+    return any(predicate(int(min(s, n_l - 1) not in empty_l), int(min(s, n_r - 1) not in empty_r))
+               for s in range(1, max(n_l, n_r) + 1))
 
 
-def _raise_first_pair_error(is_sets, levels_l, levels_r, nlev_l, nlev_r, n_r, survives, extra_hits) -> None:
+def _raise_first_pair_error(is_sets, levels_l, levels_r, nlev_l, nlev_r, n_r, survives, extra_hits, predicate=None) -> None:
     zero_l, zero_r = np.flatnonzero(nlev_l == 0), np.flatnonzero(nlev_r == 0)
     candidates: List[Tuple[int, int, type]] = []
     for i in zero_l:
@@ -936,10 +946,16 @@ def _raise_first_pair_error(is_sets, levels_l, levels_r, nlev_l, nlev_r, n_r, su
         emp_r = [_empty_levels(v) for v in levels_r]
         sus_l = [i for i, v in enumerate(emp_l) if v]
         sus_r = [j for j, v in enumerate(emp_r) if v]
-        for i in sus_l:
-            for j in sus_r:
-                if _divides_by_zero(levels_l[i], emp_l[i], levels_r[j], emp_r[j]):
-                    candidates.append((i, j, ZeroDivisionError))
+        one_side = predicate is not None and (predicate(0, 1) or predicate(1, 0))  # (one empty set is enough to divide by zero)
+        some = lambda n: [k for k in range(len(n)) if n[k] > 0]
+        pairs = ((i, j) for i in sus_l for j in sus_r)
+        if one_side:  # every pair with a suspect on either side, each once
+            in_l = set(sus_l)
+            pairs = itertools.chain(((i, j) for i in sus_l for j in some(nlev_r)),
+                                    ((i, j) for j in sus_r for i in some(nlev_l) if i not in in_l))
+        for i, j in pairs:
+            if _divides_by_zero(levels_l[i], emp_l[i], levels_r[j], emp_r[j], predicate):
+                candidates.append((i, j, ZeroDivisionError))
     best = None
     for i, j, exc in candidates:
         if survives(i, j):
@@ -960,13 +976,14 @@ def _may_be_wide_sets(*sides) -> bool:
 
 
 def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev, defer=False, top_k=None,
-                         banned=None, profile=None, floors=None):
+                         banned=None, profile=None, floors=None, measure="union"):
     """The suffix-nested fast layout of both sides + ``nsm_jaccard_levels_grid``; raises ``tables.IrregularLevels`` when an
     item does not fit it.  ``top_k``: ``nsm_jaccard_levels_top_k`` instead, without the ``banned`` pairs (tables without a
     category partition and without an inverted index).  ``profile`` (a ladder of thresholds): ``nsm_jaccard_levels_profile``
     on the same tables.  ``floors`` ((left, right) arrays by position, the right one or None):
-    ``nsm_jaccard_levels_floor_grid`` on the same tables."""
-    per_item = top_k is not None or profile is not None or floors is not None
+    ``nsm_jaccard_levels_floor_grid`` on the same tables.  ``measure``: the plugin's; beside "union" every query is a
+    per-item sweep (``nsm_set_levels_*``), the plain grid the floor grid without floors."""
+    per_item = top_k is not None or profile is not None or floors is not None or measure != "union"
     part = False if per_item else tables.partition_allowed(cat_mode, cat_l, cat_r)
     index = False if per_item else None
     memo = ComparableData._item_memo
@@ -997,11 +1014,14 @@ def _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, ca
     if len(vocab) >= 1 << 25:
         raise NotImplementedError("vocabulary of 2^25 or more distinct tokens")
     if profile is not None:
-        return grid.jaccard_levels_profile(lt, rt, profile, category_mode=cat_mode, banned=banned)
+        return grid.jaccard_levels_profile(lt, rt, profile, category_mode=cat_mode, banned=banned, measure=measure)
     if floors is not None:
-        return grid.jaccard_levels_floor_grid(lt, rt, threshold, floors[0], floors[1], category_mode=cat_mode, banned=banned)
+        return grid.jaccard_levels_floor_grid(lt, rt, threshold, floors[0], floors[1], category_mode=cat_mode, banned=banned,
+                                              measure=measure)
     if top_k is not None:
-        return grid.jaccard_levels_top_k(lt, rt, top_k, threshold, category_mode=cat_mode, banned=banned)
+        return grid.jaccard_levels_top_k(lt, rt, top_k, threshold, category_mode=cat_mode, banned=banned, measure=measure)
+    if measure != "union":
+        return grid.jaccard_levels_grid(lt, rt, threshold, category_mode=cat_mode, defer=defer, measure=measure, banned=banned)
     # the library picks the inverted-index kernel from the threshold alone (it cannot see the vocabulary); the host
     # can: with a large vocabulary few pairs share an id and the index wins at every threshold (3 x 100k^2 items of
     # ~8 ids: 20k words 2.1 vs 2.2 ms at 0.7 and 4.2 vs 22 ms at 0.1; 2^17 words 1.0 vs 2.3 ms and 1.8 vs 20.9 ms)
@@ -1068,14 +1088,17 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
                 cut(cat_r, ri), cat_mode, device=dev)
             return split_grid(split, fast, general)
 
+        measure = plugin.measure
         split = wide.wide_set_items([as_set_levels(it) for it in levels_l], [as_set_levels(it) for it in levels_r]) \
             if _may_be_wide_sets(levels_l, levels_r) else None
         if split is not None:
+            _need_general(plugin, f"an item of more than {wide.FAST_TOKENS} distinct tokens or {wide.FAST_LEVELS} levels")
             return split_route(split)
         try:
             return _fast_jaccard_levels(levels_l, levels_r, as_set_levels, threshold, cat_l, cat_r, cat_mode, dev,
-                                        defer and top_k is None and floors is None, top_k, banned, profile, floors)
+                                        defer and top_k is None and floors is None, top_k, banned, profile, floors, measure)
         except tables.IrregularLevels:
+            _need_general(plugin, "an item whose levels are not suffix-nested")
             # the reference scores whatever its tokenizer yields per level (:283-299): find the items the nested layout
             # cannot hold and route only them
             split = wide.wide_set_items([as_set_levels(it) for it in levels_l], [as_set_levels(it) for it in levels_r],
@@ -1114,6 +1137,13 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
     return split_grid(split, fast, general)
 
 
+def _need_general(plugin, what: str) -> None:
+    """The general (any-operand) kernels score Jaccard alone: another measure refuses what only they can take, before any
+    launch."""
+    if getattr(plugin, "measure", "union") != "union":
+        raise NotImplementedError(f"{plugin.__name__}: {what} (measure {plugin.measure!r} has no general kernel)")
+
+
 # =============================================================================== listed pairs
 _NO_LEVELS: list = []  # stands in for the items no listed pair names
 
@@ -1144,13 +1174,16 @@ def _levels_pairs(plugin, levels_l, levels_r, pi: np.ndarray, pj: np.ndarray) ->
                                       max((len(set(it[-1])) for it in b if it), default=1))
             lt = tables.SetTable.from_levels(a, "left", dev, vocab, width=width, partition=False, index=False)
             rt = tables.SetTable.from_levels(b, "right", dev, vocab, width=width, partition=False, index=False)
-            return grid.jaccard_levels_pairs(lt, rt, qi, qj)
+            return grid.jaccard_levels_pairs(lt, rt, qi, qj, measure=plugin.measure)
 
         general = lambda li, ri: wide.jaccard_any_grid([sl[k] for k in li], [sr[k] for k in ri], float("-inf"), device=dev)
         split = wide.wide_set_items(sl, sr)
+        if split is not None:
+            _need_general(plugin, f"an item of more than {wide.FAST_TOKENS} distinct tokens or {wide.FAST_LEVELS} levels")
         try:
             return wide.split_pairs(split, pi, pj, fast, general)
         except tables.IrregularLevels:  # levels that are not suffix-nested: only those items leave the fast path
+            _need_general(plugin, "an item whose levels are not suffix-nested")
             split = wide.wide_set_items(sl, sr, nesting=True)
             if split is None:
                 raise
