@@ -57,12 +57,14 @@ def row_gap(records):
 
 def probe_floors(records, s, floor, n_left, n_right):
     """The floors of one probe case: ``floor`` for the left items whose best score is ``s``, every other item its own
-    best (an item without a record: 0.0); on either side one NaN and one -inf floor, put on items that have records."""
+    best (an item without a record: 0.0); on either side one NaN and one -inf floor, put on items that have records (on the
+    left side: that are not at the probe, if there are any)."""
     lb, rb = bests(records)
     left = [floor if lb.get(i) == s else lb.get(i, 0.0) for i in range(n_left)]
     right = [rb.get(j, 0.0) for j in range(n_right)]
     li, rj = [i for i in sorted(lb) if lb[i] != s], sorted(rb)  # (the items at the probe keep their floor)
-    left[li[len(li) // 3]], left[li[2 * len(li) // 3]] = math.nan, -math.inf
+    if li:  # (under the overlap measure every left item of a RAW probe grid has the best score 1.0)
+        left[li[len(li) // 3]], left[li[2 * len(li) // 3]] = math.nan, -math.inf
     right[rj[len(rj) // 3]], right[rj[2 * len(rj) // 3]] = math.nan, -math.inf
     return left, right
 

@@ -15,6 +15,7 @@ import pytest
 from support import probe_tables
 from support import best_matches as bm
 from support import threshold_probes as tp
+from support.probe_checks import ban_unique_bests as _ban_unique_bests, check_small as _check_small, same as _same
 
 pytestmark = pytest.mark.gpu
 PRUNE = {"prune": True, "no_prune": False}
@@ -25,13 +26,6 @@ def dev():
     import torch
 
     return torch.device("cuda:0")
-
-
-def _same(got, want, what):
-    """Records and doubles equal, bit for bit (scores are never NaN or -0.0)."""
-    assert len(got) == len(want), f"{what}: {len(got)} records, expected {len(want)}"
-    assert np.array_equal(got.i, want.i) and np.array_equal(got.j, want.j), f"{what}: pairs differ"
-    assert np.array_equal(got.score.view(np.int64), want.score.view(np.int64)), f"{what}: scores differ"
 
 
 def _calls(g, dev):
@@ -80,15 +74,6 @@ def test_floor_grids_on_probe_grids(dev, name, route):
     # neither: the threshold grid
     for thr in (probes[0], probes[len(probes) // 2], math.nextafter(probes[-1], 2.0)):
         _same(floors(thr, None, None, PRUNE[route]), bm.to_hits(tp.expectation(records, thr)), f"{name} / {route} no floors at {thr!r}")
-
-
-def _ban_unique_bests(records):
-    """The best pair of every third left item, where it is the item's only pair at that score: banning it moves the best."""
-    rows = {}
-    for s, i, j in records:  # (score descending: a row's first record is its best)
-        rows.setdefault(i, []).append((s, j))
-    banned = {(i, r[0][1]) for i, r in rows.items() if i % 3 == 0 and r[0][0] > 0.0 and (len(r) == 1 or r[1][0] < r[0][0])}
-    return banned, {i: r[0][0] for i, r in rows.items()}
 
 
 @pytest.mark.parametrize("name", tp.EVERY)
@@ -144,28 +129,6 @@ def test_pruning_is_monotone(dev, name):
 # ------------------------------------------------------------------------------------------------------ small shapes
 def _small_strings(rng, n):
     return ["".join(rng.choice("abcd") for _ in range(rng.choice((0, 1, 3, 9, 20)))) for _ in range(n)]
-
-
-def _floor_cases(records, n, m):
-    """Floors of a small grid: every item's own best; left floors one ulp above it (admits nothing for the item); a mix."""
-    lb, rb = bm.bests(records)
-    own_l, own_r = [lb.get(i, 0.0) for i in range(n)], [rb.get(j, 0.0) for j in range(m)]
-    above = [math.nextafter(x, 2.0) if i % 2 else x for i, x in enumerate(own_l)]
-    mixed = [math.nan if j % 5 == 1 else -math.inf if j % 5 == 2 else x for j, x in enumerate(own_r)]
-    return [(own_l, None), (None, own_r), (own_l, own_r), (above, mixed), (None, None)]
-
-
-def _check_small(records, n, m, floor_grid, best, what):
-    from napkon_string_matching_amd import grid
-
-    hits = bm.to_hits(records)
-    for prune in (True, False):
-        for lf, rf in _floor_cases(records, n, m):
-            arr = lambda f: None if f is None else np.array(f, dtype=np.float64)
-            _same(floor_grid(0.0, arr(lf), arr(rf), prune), bm.to_hits(bm.floors_plain(records, lf, rf)), f"{what} prune={prune}")
-        for margin, mutual in ((0.0, False), (0.0, True), (0.25, False), (0.25, True), (2.0, True)):
-            _same(best(margin, 0.0, mutual, prune), grid.best_of_hits(hits, margin, mutual, n, m),
-                  f"{what} margin {margin} mutual {mutual} prune={prune}")
 
 
 @pytest.mark.parametrize("stride", [64, 128])

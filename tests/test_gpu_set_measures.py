@@ -5,6 +5,7 @@ The yardstick is the pure-Python definition in tests/support/set_measures.py (fo
 ``compare_terms`` / ``gen_comparable`` with that definition registered as score_func).  Records are compared as canonical
 ``(score, i, j)`` tuples, the scores as doubles bit for bit (``==`` on Python floats: every score here is finite).  The
 inputs are checked in tests/test_cpu_set_measures.py: every threshold has a pair exactly on it and one below it.
+The pruning bounds of the measures at exact thresholds and floors, at every width: tests/test_gpu_measure_probes.py.
 """
 import math
 

@@ -16,13 +16,12 @@ below it, and none of them one ulp above.
 At most 40 probes x 3 thresholds per route, every tight-family score and every ulp twin among them.  The per-tile index of
 the RAW Jaccard grid exists for widths 16 and 32 only, so width 64 has no "index_tile" route.
 """
-import math
-
 import numpy as np
 import pytest
 
 from support import threshold_probes as tp
 from support import probe_tables
+from support.probe_checks import check as _check, check_top_k as _check_top_k
 
 pytestmark = pytest.mark.gpu
 
@@ -32,52 +31,6 @@ def dev():
     import torch
 
     return torch.device("cuda:0")
-
-
-_AT = {}
-
-
-def _pairs_at(g):
-    """score -> the pairs that score exactly that."""
-    if g.name not in _AT:
-        at = {}
-        for s, i, j in tp.all_scores(g):
-            at.setdefault(s, set()).add((i, j))
-        _AT[g.name] = at
-    return _AT[g.name]
-
-
-def _check(g, route, run):
-    """``run(thr)`` -> the kernel's (score, i, j) list."""
-    all_hits = tp.all_scores(g)
-    scores = tp.probes_of(g)
-    seen = {}
-    for thr in tp.thresholds_around(scores):
-        want = tp.expectation(all_hits, thr)
-        got = seen[thr] = run(thr)
-        assert got == want, f"{g.name} / {route} at threshold {thr!r}: {probe_tables.first_difference(got, want)}"
-    at = _pairs_at(g)
-    for s in scores:  # (implied by the equalities above; spelled out, since it is what these thresholds are for)
-        here, below, above = ({(i, j) for _, i, j in seen[t]} for t in (s, math.nextafter(s, 0.0), math.nextafter(s, 2.0)))
-        assert at[s] and at[s] <= here and at[s] <= below and not at[s] & above, \
-            f"{g.name} / {route}: pairs scoring exactly {s!r}: {sorted(at[s] - here)[:4]} lost at it, " \
-            f"{sorted(at[s] - below)[:4]} lost one ulp below, {sorted(at[s] & above)[:4]} kept one ulp above"
-
-
-def _check_top_k(g, route, run, groups=None):
-    """``run(k, thr)`` -> the kernel's list.  The expectation: the oracle's list cut at the threshold, per left item the
-    first k in (score descending, j ascending) -- of the groups' representatives when ``groups`` is given."""
-    all_hits = tp.all_scores(g)
-    ranks = tp.RowRanks(all_hits, None if groups is None else groups.tolist())
-    thresholds = tp.thresholds_around(tp.probes_of(g))
-    for k in (1, 3, 64):
-        # a threshold on the score of some row's k-th record: floor and threshold coincide, the tie goes to the lower j
-        tie = ranks.kth_tie(k)
-        assert tie is not None or k == 64  # (with categories a row may hold fewer than 64 records)
-        for thr in sorted(set(thresholds) | set(tp.thresholds_around([] if tie is None else [tie]))):
-            want = ranks.cut(thr, k)
-            got = run(k, thr)
-            assert got == want, f"{g.name} / {route} k={k} at threshold {thr!r}: {probe_tables.first_difference(got, want)}"
 
 
 # --------------------------------------------------------------------------------------------------------- RAW Indel
