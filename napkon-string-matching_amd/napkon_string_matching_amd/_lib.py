@@ -25,6 +25,9 @@ CAT_NONE, CAT_INTERSECT, CAT_INTERSECT_OR_BOTH_EMPTY = 0, 1, 2
 # include/nsm_hip_measures.h: the token-set measure of the nsm_set_* entries
 MEASURE_UNION, MEASURE_MEAN, MEASURE_SMALLER, MEASURE_LEFT = 0, 1, 2, 3
 MEASURES = {"union": MEASURE_UNION, "mean": MEASURE_MEAN, "smaller": MEASURE_SMALLER, "left": MEASURE_LEFT}
+# include/nsm_hip_edit.h: the string metric of the nsm_edit_* entries
+METRIC_INDEL, METRIC_EDIT, METRIC_EDIT_WITHIN = 0, 1, 2
+METRICS = {"indel": METRIC_INDEL, "edit": METRIC_EDIT, "edit_within": METRIC_EDIT_WITHIN}
 
 c_i32p = ctypes.c_void_p  # device pointers travel as integers
 c_u64 = ctypes.c_uint64
@@ -163,6 +166,19 @@ MEASURE_EXPORTS = (
     "nsm_set_levels_pairs",
 )
 
+# include/nsm_hip_edit.h, likewise: every nsm_indel_* per-item entry with `metric` after the tables
+EDIT_EXPORTS = (
+    "nsm_edit_raw_top_k",
+    "nsm_edit_raw_top_k_grouped",
+    "nsm_edit_raw_profile",
+    "nsm_edit_raw_floor_grid",
+    "nsm_edit_raw_pairs",
+    "nsm_edit_levels_top_k",
+    "nsm_edit_levels_profile",
+    "nsm_edit_levels_floor_grid",
+    "nsm_edit_levels_pairs",
+)
+
 _lib = None
 
 
@@ -274,8 +290,21 @@ def load() -> ctypes.CDLL:
         "nsm_set_levels_floor_grid": sets + levels_floor_tail,
         "nsm_set_levels_pairs": sets + pairs_tail,
     }
+    strs = [P(NsmStrTable), P(NsmStrTable), i32]  # left, right, metric; then the tail of the nsm_indel_* counterpart
+    levs = [P(NsmLevelItems), P(NsmStrTable), P(NsmLevelItems), P(NsmStrTable), i32]
+    edit_args = {
+        "nsm_edit_raw_top_k": strs + top_k_tail,
+        "nsm_edit_raw_top_k_grouped": strs + [vp] + top_k_tail,
+        "nsm_edit_raw_profile": strs + profile_tail,
+        "nsm_edit_raw_floor_grid": strs + floor_tail,
+        "nsm_edit_raw_pairs": strs + pairs_tail,
+        "nsm_edit_levels_top_k": levs + levels_top_k_tail,
+        "nsm_edit_levels_profile": levs + levels_profile_tail,
+        "nsm_edit_levels_floor_grid": levs + levels_floor_tail,
+        "nsm_edit_levels_pairs": levs + pairs_tail,
+    }
     for names, args in ((ASSIGN_EXPORTS, assign_args), (GROUP_EXPORTS, group_args), (SPAN_EXPORTS, span_args),
-                        (MEASURE_EXPORTS, measure_args)):
+                        (MEASURE_EXPORTS, measure_args), (EDIT_EXPORTS, edit_args)):
         for name in names:
             try:
                 fn = getattr(lib, name)

@@ -40,6 +40,10 @@ Beside the reference's two functions the module holds three more token-set measu
 ``intersection_vs_mean`` (Sorensen-Dice), ``intersection_vs_smaller`` (overlap coefficient) and ``intersection_vs_left``
 (containment of left in right): ``intersection_vs_union``'s class with another ``measure``.
 
+On the string side ``levenshtein_match`` (normalised Levenshtein similarity) and ``levenshtein_within`` (best approximate
+occurrence of the left string inside the right one) stand beside ``fuzzy_match`` in the same way: ``fuzzy_match``'s class
+with another ``metric``.
+
 ``default_process`` / ``join_sorted`` are per-item string preparation and stay on the host; the
 reference re-does them for every pair (score_functions.py:24-25 inside the hot loop).
 """
@@ -412,26 +416,41 @@ class _IntersectionVsUnion:
 
 
 class _FuzzyMatch:
+    """The Indel ratio ``2 LCS / (la + lb)`` of the two prepared strings (QRatio / 100; score_functions.py:20-27).  The
+    Levenshtein score functions below are this class with another ``metric``: every method here hands ``self.metric`` to
+    the ``grid.indel_*`` wrapper it uses (``"indel"`` keeps each wrapper's own route)."""
     __name__ = "fuzzy_match"
     kind = "strings"
+    metric = "indel"  # grid.check_metric: which score the device computes
 
     def __call__(self, left: Operand, right: Operand) -> float:
         hits = self.raw_grid([left], [right], float("-inf"))
         return float(hits.score[0])
 
-    @staticmethod
-    def raw_grid(left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
+    def _split(self, items_l, items_r):
+        """``wide.wide_string_items``: which items lie beyond the fast kernels (None: none).  The general kernels are
+        Indel-only, so another metric raises here, before the device is asked."""
+        from .. import wide
+
+        split = wide.wide_string_items(items_l, items_r)
+        if split is not None and self.metric != "indel":
+            raise NotImplementedError(f"{self.__name__}: a string beyond the fast kernels (more than {wide.FAST_LEN} code "
+                                      f"units, or more than 255 distinct code units in the grid; metric {self.metric!r} has "
+                                      "no general kernel)")
+        return split
+
+    def raw_grid(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
                  prune: bool = True) -> grid.Hits:
         from .. import wide
 
-        dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
+        dev = device or _device()
 
         def fast(li, ri):
             lt, rt = tables.encode_strings([l_ops[k] for k in li], [r_ops[k] for k in ri], dev)
-            return grid.indel_raw_grid(lt, rt, threshold, prune=prune)
+            return grid.indel_raw_grid(lt, rt, threshold, prune=prune, metric=self.metric)
 
-        split = wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops])
         if split is None:
             return fast(range(len(l_ops)), range(len(r_ops)))
         # strings of more than 512 code units / more than 255 distinct code units (rapidfuzz has no such limit, :27)
@@ -439,8 +458,7 @@ class _FuzzyMatch:
                                                      device=dev)
         return wide.split_grid(split[0], split[1], fast, general)
 
-    @staticmethod
-    def top_k(left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
+    def top_k(self, left_items: Sequence[Operand], right_items: Sequence[Operand], k: int, threshold: float = 0.0, device=None,
               prune: bool = True, groups=None) -> grid.Hits:
         """Per left item the first ``k`` records of ``raw_grid(left_items, right_items, threshold)`` (score descending,
         right index ascending), all of them in canonical order.  ``groups`` (hashables, one per right item): right items
@@ -450,15 +468,15 @@ class _FuzzyMatch:
 
         k = grid.check_k(k)
         gids = factorise_groups(groups, len(right_items))
-        dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
+        dev = device or _device()
         sub = lambda ri: None if gids is None else gids[np.asarray(ri, dtype=np.int64)]
 
         def fast(li, ri):
             lt, rt = tables.encode_strings([l_ops[k_] for k_ in li], [r_ops[k_] for k_ in ri], dev)
-            return grid.indel_raw_top_k(lt, rt, k, threshold, prune=prune, groups=sub(ri))
+            return grid.indel_raw_top_k(lt, rt, k, threshold, prune=prune, groups=sub(ri), metric=self.metric)
 
-        split = wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops])
         if split is None:
             return fast(range(len(l_ops)), range(len(r_ops)))
         # strings beyond the fast kernels: the general kernel at `threshold`; the parts are disjoint in j for every i, so
@@ -469,8 +487,7 @@ class _FuzzyMatch:
         return grid.select_top_k(wide.split_grid(split[0], split[1], fast, general), k, gids)
 
 
-    @staticmethod
-    def pairs(left_items: Sequence[Operand], right_items: Sequence[Operand], pairs, device=None) -> np.ndarray:
+    def pairs(self, left_items: Sequence[Operand], right_items: Sequence[Operand], pairs, device=None) -> np.ndarray:
         """The score of every listed pair: ``pairs`` is a sequence of ``(i, j)`` positions in the two item lists, or a
         P x 2 integer array; the result is ``[plugin(left_items[i], right_items[j]) for i, j in pairs]`` as a float64 array,
         in O(P) -- rapidfuzz's ``process.cpdist`` (``nsm_indel_raw_pairs``: tables of the listed items only, one launch).
@@ -482,22 +499,21 @@ class _FuzzyMatch:
         i, j = wide.check_pair_positions(pairs, len(left_items), len(right_items))
         if len(i) == 0:
             return np.zeros(0, dtype=np.float64)
-        dev = device or _device()
         l_ops = {int(k): fuzzy_operand(left_items[k]) for k in np.unique(i)}
         r_ops = {int(k): fuzzy_operand(right_items[k]) for k in np.unique(j)}
+        n_l, n_r = len(left_items), len(right_items)
+        split = self._split([[l_ops.get(k, "")] for k in range(n_l)], [[r_ops.get(k, "")] for k in range(n_r)])  # (before the device)
+        dev = device or _device()
 
         def fast(li, ri, pi, pj):
             lt, rt = tables.encode_strings([l_ops[int(k)] for k in li], [r_ops[int(k)] for k in ri], dev)
-            return grid.indel_raw_pairs(lt, rt, pi, pj)
+            return grid.indel_raw_pairs(lt, rt, pi, pj, metric=self.metric)
 
         general = lambda li, ri: wide.indel_any_grid([[l_ops[int(k)]] for k in li], [[r_ops[int(k)]] for k in ri], float("-inf"),
                                                      raw=True, device=dev)
-        n_l, n_r = len(left_items), len(right_items)
-        split = wide.wide_string_items([[l_ops.get(k, "")] for k in range(n_l)], [[r_ops.get(k, "")] for k in range(n_r)])
         return wide.split_pairs(split, i, j, fast, general)
 
-    @staticmethod
-    def profile(left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,
+    def profile(self, left_items: Sequence[Operand], right_items: Sequence[Operand], thresholds, device=None,
                 prune: bool = True) -> grid.ThresholdProfile:
         """``grid.profile_of_hits(raw_grid(left_items, right_items, thresholds[0]), thresholds, ...)`` without the hits:
         per threshold the number of pairs scoring at least that, per item its best score (``-1.0``: none at
@@ -506,17 +522,18 @@ class _FuzzyMatch:
         from .. import wide
 
         t = grid.check_thresholds(thresholds)
-        dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
+        dev = device or _device()
 
         def fast(li, ri):
             lt, rt = tables.encode_strings([l_ops[k_] for k_ in li], [r_ops[k_] for k_ in ri], dev)
-            return grid.indel_raw_profile(lt, rt, t, prune=prune)
+            return grid.indel_raw_profile(lt, rt, t, prune=prune, metric=self.metric)
 
         general = lambda li, ri: grid.profile_of_hits(
             wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], float(t[0]), raw=True, device=dev),
             t, len(li), len(ri))
-        return wide.split_profile(wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]), len(l_ops), len(r_ops),
+        return wide.split_profile(split, len(l_ops), len(r_ops),
                                   t, fast, general)
 
     def best(self, left_items: Sequence[Operand], right_items: Sequence[Operand], margin: float = 0.0, threshold: float = 0.0,
@@ -529,17 +546,18 @@ class _FuzzyMatch:
 
         margin = grid.check_margin(margin)
         grid.check_thresholds([threshold])
-        dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
+        dev = device or _device()
 
         def fast(li, ri, lf, rf):
             lt, rt = tables.encode_strings([l_ops[k_] for k_ in li], [r_ops[k_] for k_ in ri], dev)
-            return grid.indel_raw_floor_grid(lt, rt, threshold, lf, rf, prune=prune)
+            return grid.indel_raw_floor_grid(lt, rt, threshold, lf, rf, prune=prune, metric=self.metric)
 
         general = lambda li, ri: wide.indel_any_grid([[l_ops[k_]] for k_ in li], [[r_ops[k_]] for k_ in ri], threshold, raw=True,
                                                      device=dev)
         return _best(lambda t: self.profile(left_items, right_items, t, device=dev, prune=prune),
-                     wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]), len(l_ops), len(r_ops), margin,
+                     split, len(l_ops), len(r_ops), margin,
                      threshold, mutual, fast, general)
 
     def assign(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
@@ -552,15 +570,16 @@ class _FuzzyMatch:
         from .. import wide
 
         grid.check_thresholds([threshold])
-        dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
+        dev = device or _device()
         if not l_ops or not r_ops:
             return wide.merge([])
-        if wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]) is not None:
+        if split is not None:
             return grid.assign_hits(self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune), len(l_ops),
                                     len(r_ops), device=dev)
         lt, rt = tables.encode_strings(l_ops, r_ops, dev)
-        return grid.indel_raw_assign(lt, rt, threshold, prune=prune)
+        return grid.indel_raw_assign(lt, rt, threshold, prune=prune, metric=self.metric)
 
     def groups(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
                prune: bool = True, same: bool = False) -> grid.MatchGroups:
@@ -572,17 +591,18 @@ class _FuzzyMatch:
         from .. import wide
 
         grid.check_thresholds([threshold])
-        dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
+        dev = device or _device()
         n_l, n_r = len(l_ops), len(r_ops)
         layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
         if not l_ops or not r_ops:
             return grid.MatchGroups(np.arange(sum(layout[1]), dtype=np.int32), *layout)
-        if wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]) is not None:
+        if split is not None:
             hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
             return grid.MatchGroups(grid.group_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float("-inf"), device=dev), *layout)
         lt, rt = tables.encode_strings(l_ops, r_ops, dev)
-        return grid.indel_raw_groups(lt, rt, threshold, prune=prune, same=same)
+        return grid.indel_raw_groups(lt, rt, threshold, prune=prune, same=same, metric=self.metric)
 
     def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> List[np.ndarray]:
         """Near-duplicate clusters inside ONE list (rapidfuzz users' dedupe): the self-join's groups of at least two items,
@@ -599,18 +619,19 @@ class _FuzzyMatch:
         from .. import wide
 
         grid.check_thresholds([threshold])
-        dev = device or _device()
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
+        split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
+        dev = device or _device()
         n_l, n_r = len(l_ops), len(r_ops)
         layout = ((0,), (max(n_l, n_r),)) if same else ((0, n_l), (n_l, n_r))
         if not l_ops or not r_ops:
             return grid.forest_of_hits([], sum(layout[1]), float(threshold), *layout)
-        if wide.wide_string_items([[s] for s in l_ops], [[s] for s in r_ops]) is not None:
+        if split is not None:
             hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
             return grid.span_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float(threshold), device=dev, bases=layout[0],
                                   cohort_sizes=layout[1])
         lt, rt = tables.encode_strings(l_ops, r_ops, dev)
-        return grid.indel_raw_forest(lt, rt, threshold, prune=prune, same=same)
+        return grid.indel_raw_forest(lt, rt, threshold, prune=prune, same=same, metric=self.metric)
 
     def cluster_tree(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> grid.MergeForest:
         """The single-linkage tree of ONE list: the self-join's merge forest (node k is ``items[k]``); ``cut(t).members(2)``
@@ -639,9 +660,27 @@ class _IntersectionVsLeft(_IntersectionVsUnion):
     measure = "left"
 
 
+class _LevenshteinMatch(_FuzzyMatch):
+    """``1 - d(a, b) / max(la, lb)`` of the two prepared strings, d the unit-cost Levenshtein distance: the normalised
+    Levenshtein similarity.  0.0 when either prepared string is empty, as ``fuzzy_match``."""
+    __name__ = "levenshtein_match"
+    metric = "edit"
+
+
+class _LevenshteinWithin(_FuzzyMatch):
+    """``1 - w(a, b) / la`` with w the least Levenshtein distance of the LEFT prepared string to any substring of the right
+    one (asymmetric): a short definition that occurs verbatim in a long item scores 1.0 -- the string counterpart of
+    ``intersection_vs_left``.  0.0 when either prepared string is empty."""
+    __name__ = "levenshtein_within"
+    metric = "edit_within"
+
+
 intersection_vs_union = _IntersectionVsUnion()
 intersection_vs_mean = _IntersectionVsMean()
 intersection_vs_smaller = _IntersectionVsSmaller()
 intersection_vs_left = _IntersectionVsLeft()
 fuzzy_match = _FuzzyMatch()
-PLUGINS = (intersection_vs_union, intersection_vs_mean, intersection_vs_smaller, intersection_vs_left, fuzzy_match)
+levenshtein_match = _LevenshteinMatch()
+levenshtein_within = _LevenshteinWithin()
+PLUGINS = (intersection_vs_union, intersection_vs_mean, intersection_vs_smaller, intersection_vs_left, fuzzy_match,
+           levenshtein_match, levenshtein_within)

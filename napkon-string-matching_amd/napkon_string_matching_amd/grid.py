@@ -181,6 +181,32 @@ def _check_set_sides(left: SetTable, right: SetTable, measure: str) -> None:
     check_measure_grid(measure, left.has_empty, left.n, right.has_empty, right.n)
 
 
+# ------------------------------------------------------------------------------- string metrics
+def check_metric(metric) -> int:
+    """The code (``_lib.METRICS``, include/nsm_hip_edit.h) of a string metric name: "indel" (the Indel ratio of
+    ``fuzzy_match``, the default of every ``indel_*`` wrapper), "edit" (normalised Levenshtein similarity) and
+    "edit_within" (the best approximate occurrence of the left string inside the right one)."""
+    try:
+        return _lib.METRICS[metric]
+    except (KeyError, TypeError):
+        raise ValueError(f"metric must be one of {tuple(_lib.METRICS)}, not {metric!r}") from None
+
+
+def _edit_entry(entry: str, metric: str):
+    """(C entry, what it takes between the tables and the rest) of a ``nsm_indel_*`` per-item query under ``metric``: the
+    entry itself for "indel", else its ``nsm_edit_*`` counterpart with the metric code behind the tables.  A query the
+    library has no ``nsm_edit_*`` entry for is a ``NotImplementedError``, before the device is asked."""
+    code = check_metric(metric)
+    if code == _lib.METRIC_INDEL:
+        return entry, ()
+    entry = entry.replace("nsm_indel_", "nsm_edit_")
+    if entry not in _lib.EDIT_EXPORTS:
+        raise NotImplementedError(f"{entry}: metric {metric!r} has no kernel for this query (the threshold-grid and general "
+                                  "kernels are Indel-only)")
+    _lib.entry(entry)  # (NsmLibraryError for a library without the metrics)
+    return entry, (code,)
+
+
 # ------------------------------------------------------------------------------- RAW grids
 def jaccard_raw_grid(
     left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
@@ -218,7 +244,7 @@ def jaccard_raw_grid(
 
 def indel_raw_grid(
     left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
-    two_stage: bool = True, pack: Optional[bool] = None, defer: bool = False, one_group: bool = False,
+    two_stage: bool = True, pack: Optional[bool] = None, defer: bool = False, one_group: bool = False, metric: str = "indel",
 ) -> Hits:
     """``fuzzy_match`` (QRatio/100 = Indel ratio after default_process) on one string per item.
     ``two_stage=False``: the 32-bucket histogram test for every pair even when both tables carry the ``hist16``
@@ -226,7 +252,11 @@ def indel_raw_grid(
     ``pack``: None = the library decides whether the two-stage scan codes its left operand words once per call (a
     pre-pass into a buffer the library keeps per stream, where the grid is large enough); True = force it, False = never (same hits).
     ``one_group``: where the call packs, the persistent form of the scan (waves that pull work items from a list) as ONE workgroup
-    (tests; same hits)."""
+    (tests; same hits).
+    ``metric``: another string metric (``check_metric``) -- its threshold grid is the floor grid without floors
+    (``nsm_edit_raw_floor_grid``, the per-item sweep); ``two_stage``, ``pack`` and ``one_group`` do not apply to it."""
+    if check_metric(metric) != _lib.METRIC_INDEL:
+        return indel_raw_floor_grid(left, right, threshold, prune=prune, capacity=capacity, defer=defer, metric=metric)
     lib = _lib.load()
     ls, rs = left.struct(), right.struct()
     flags = ((_lib.FLAG_PRUNE if prune else 0) | (0 if two_stage else _lib.FLAG_ONE_STAGE)
@@ -338,15 +368,17 @@ def _raw_top_k(entry: str, left, right, device, k: int, threshold: float, prune:
 
 
 def indel_raw_top_k(left: StrTable, right: StrTable, k: int, threshold: float, prune: bool = True,
-                    stats: Optional[list] = None, groups=None) -> Hits:
+                    stats: Optional[list] = None, groups=None, metric: str = "indel") -> Hits:
     """For every left item the first ``min(k, #hits of its row)`` records of ``indel_raw_grid(left, right, threshold)``
     in the order (score descending, j ascending), all of them in canonical order.  ``stats``: a list that receives
     [pairs in visited classes, pairs past the length bound, pairs past the histogram bound, exact LCS evaluations].
     ``groups``: an int32 device tensor or integer array with one group id per right caller index -- then a left item gets
     the best record of every group (its representative) and of those the first ``k``: ``select_top_k(hits, k, groups)`` of
-    the threshold grid's hits, computed by ``nsm_indel_raw_top_k_grouped`` with lists of one record per group."""
+    the threshold grid's hits, computed by ``nsm_indel_raw_top_k_grouped`` with lists of one record per group.
+    ``metric``: another string metric (``check_metric``: ``nsm_edit_raw_top_k``); stats[3] then counts the exact distances."""
     k = check_k(k)
-    return _raw_top_k("nsm_indel_raw_top_k", left, right, left.codes.device, k, threshold, prune, stats, groups)
+    entry, head = _edit_entry("nsm_indel_raw_top_k", metric)
+    return _raw_top_k(entry, left, right, left.codes.device, k, threshold, prune, stats, groups, head=head)
 
 
 def jaccard_raw_top_k(left: SetTable, right: SetTable, k: int, threshold: float, prune: bool = True,
@@ -423,15 +455,17 @@ def _levels_top_k(entry: str, tables: tuple, left, right, device, k: int, thresh
 
 def indel_levels_top_k(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, k: int,
                        threshold: float, category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
-                       stats: Optional[list] = None) -> Hits:
+                       stats: Optional[list] = None, metric: str = "indel") -> Hits:
     """For every left item the first ``min(k, #hits of its row)`` records of ``indel_levels_grid(...)`` without the
     ``banned`` pairs, in the order (score descending, j ascending), all of them in canonical order.  ``banned``: None or
     (left ids, right ids) of pairs that never take a slot, in caller ids.  Tables must be encoded with
     ``partition=False``.  ``stats``: a list that receives [pairs visited, pairs past the category predicate and the
-    length bound, pairs past the histogram bound, pairs that got an exact level score]."""
+    length bound, pairs past the histogram bound, pairs that got an exact level score].  ``metric``: another string metric
+    (``check_metric``: ``nsm_edit_levels_top_k``)."""
     k = check_k(k)
-    return _levels_top_k("nsm_indel_levels_top_k", (left, left_strings, right, right_strings), left, right, left.first.device,
-                         k, threshold, category_mode, prune, banned, stats)
+    entry, head = _edit_entry("nsm_indel_levels_top_k", metric)
+    return _levels_top_k(entry, (left, left_strings, right, right_strings), left, right, left.first.device,
+                         k, threshold, category_mode, prune, banned, stats, head)
 
 
 def jaccard_levels_top_k(left: SetTable, right: SetTable, k: int, threshold: float, category_mode: int = _lib.CAT_NONE,
@@ -535,15 +569,17 @@ def _profile(launch: Callable, t: np.ndarray, left_orig: torch.Tensor, n_left: i
 
 
 def indel_raw_profile(left: StrTable, right: StrTable, thresholds, prune: bool = True,
-                      stats: Optional[list] = None) -> ThresholdProfile:
+                      stats: Optional[list] = None, metric: str = "indel") -> ThresholdProfile:
     """``profile_of_hits(indel_raw_grid(left, right, thresholds[0]), thresholds, ...)`` without the hits, in one sweep of
-    ``nsm_indel_raw_profile`` (the top-k kernel with a tally in place of its lists).  ``stats`` as for ``indel_raw_top_k``."""
+    ``nsm_indel_raw_profile`` (the top-k kernel with a tally in place of its lists).  ``stats`` as for ``indel_raw_top_k``.
+    ``metric``: another string metric (``check_metric``: ``nsm_edit_raw_profile``)."""
     t = check_thresholds(thresholds)
-    lib = _lib.load()
+    entry, head = _edit_entry("nsm_indel_raw_profile", metric)
+    fn = getattr(_lib.load(), entry)
     ls, rs = left.struct(), right.struct()
     flags = _lib.FLAG_PRUNE if prune else 0
-    return _profile(lambda lad, n, pairs, lb, rb, st, stream: lib.nsm_indel_raw_profile(ls, rs, lad, n, flags, pairs, lb, rb, st, stream),
-                    t, left.orig, left.n, right.orig, right.n, left.codes.device, "nsm_indel_raw_profile", stats)
+    return _profile(lambda lad, n, pairs, lb, rb, st, stream: fn(ls, rs, *head, lad, n, flags, pairs, lb, rb, st, stream),
+                    t, left.orig, left.n, right.orig, right.n, left.codes.device, entry, stats)
 
 
 def jaccard_raw_profile(left: SetTable, right: SetTable, thresholds, prune: bool = True,
@@ -576,12 +612,13 @@ def _levels_profile(entry: str, tables: tuple, left, right, device, t: np.ndarra
 
 def indel_levels_profile(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, thresholds,
                          category_mode: int = _lib.CAT_NONE, prune: bool = True, banned=None,
-                         stats: Optional[list] = None) -> ThresholdProfile:
+                         stats: Optional[list] = None, metric: str = "indel") -> ThresholdProfile:
     """The profile of ``indel_levels_grid(...)`` without the ``banned`` pairs (``indel_levels_top_k``'s arguments and
-    preconditions: tables encoded with ``partition=False``)."""
+    preconditions: tables encoded with ``partition=False``; ``metric``: ``nsm_edit_levels_profile``)."""
     t = check_thresholds(thresholds)
-    return _levels_profile("nsm_indel_levels_profile", (left, left_strings, right, right_strings), left, right,
-                           left.first.device, t, category_mode, prune, banned, stats)
+    entry, head = _edit_entry("nsm_indel_levels_profile", metric)
+    return _levels_profile(entry, (left, left_strings, right, right_strings), left, right,
+                           left.first.device, t, category_mode, prune, banned, stats, head)
 
 
 def jaccard_levels_profile(left: SetTable, right: SetTable, thresholds, category_mode: int = _lib.CAT_NONE, prune: bool = True,
@@ -697,14 +734,17 @@ def _floor_grid(entry: str, structs: list, middle: tuple, left, right, device, t
 
 
 def indel_raw_floor_grid(left: StrTable, right: StrTable, threshold: float, left_floor=None, right_floor=None,
-                         prune: bool = True, stats: Optional[list] = None, capacity: Optional[int] = None) -> Hits:
+                         prune: bool = True, stats: Optional[list] = None, capacity: Optional[int] = None,
+                         defer: bool = False, metric: str = "indel") -> Hits:
     """``filter_by_floors(indel_raw_grid(left, right, threshold), left_floor, right_floor)`` in one sweep of
     ``nsm_indel_raw_floor_grid`` (the top-k kernel with a gate in place of its lists): a threshold grid whose threshold is
     per item.  Floors: numpy float64 arrays or float64 tensors indexed by caller id, or None.  ``stats`` as for
-    ``indel_raw_top_k``."""
+    ``indel_raw_top_k``.  ``metric``: another string metric (``check_metric``: ``nsm_edit_raw_floor_grid``); ``defer`` as
+    for the grids."""
+    entry, head = _edit_entry("nsm_indel_raw_floor_grid", metric)
     flags = _lib.FLAG_PRUNE if prune else 0
-    return _floor_grid("nsm_indel_raw_floor_grid", [left.struct(), right.struct()], (flags,), left, right, left.codes.device,
-                       threshold, left_floor, right_floor, stats, capacity)
+    return _floor_grid(entry, [left.struct(), right.struct(), *head], (flags,), left, right, left.codes.device,
+                       threshold, left_floor, right_floor, stats, capacity, defer)
 
 
 def jaccard_raw_floor_grid(left: SetTable, right: SetTable, threshold: float, left_floor=None, right_floor=None,
@@ -734,12 +774,14 @@ def _levels_floor_grid(entry: str, tables: tuple, left, right, device, threshold
 def indel_levels_floor_grid(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable,
                             threshold: float, left_floor=None, right_floor=None, category_mode: int = _lib.CAT_NONE,
                             prune: bool = True, banned=None, stats: Optional[list] = None,
-                            capacity: Optional[int] = None) -> Hits:
+                            capacity: Optional[int] = None, defer: bool = False, metric: str = "indel") -> Hits:
     """``filter_by_floors`` of ``indel_levels_grid(...)`` without the ``banned`` pairs, in one sweep of
     ``nsm_indel_levels_floor_grid`` (``indel_levels_top_k``'s arguments and preconditions: tables encoded with
-    ``partition=False``)."""
-    return _levels_floor_grid("nsm_indel_levels_floor_grid", (left, left_strings, right, right_strings), left, right,
-                              left.first.device, threshold, left_floor, right_floor, category_mode, prune, banned, stats, capacity)
+    ``partition=False``; ``metric``: ``nsm_edit_levels_floor_grid``; ``defer`` as for the grids)."""
+    entry, head = _edit_entry("nsm_indel_levels_floor_grid", metric)
+    return _levels_floor_grid(entry, (left, left_strings, right, right_strings), left, right,
+                              left.first.device, threshold, left_floor, right_floor, category_mode, prune, banned, stats, capacity,
+                              head, defer)
 
 
 def jaccard_levels_floor_grid(left: SetTable, right: SetTable, threshold: float, left_floor=None, right_floor=None,
@@ -779,12 +821,13 @@ def _best(profile: Callable, floor_grid: Callable, margin: float, threshold: flo
 
 
 def indel_raw_best(left: StrTable, right: StrTable, margin: float = 0.0, threshold: float = 0.0, mutual: bool = False,
-                   prune: bool = True, stats: Optional[list] = None) -> Hits:
+                   prune: bool = True, stats: Optional[list] = None, metric: str = "indel") -> Hits:
     """``best_of_hits(indel_raw_grid(left, right, threshold), margin, mutual)`` without the grid's hits: every left item's
     best match with everything within ``margin`` of it (``margin=0``: all its ties), with ``mutual`` only the pairs that
-    are also within ``margin`` of the right item's best.  A profile sweep at ``[threshold]``, then a floor grid."""
-    return _best(lambda t, st: indel_raw_profile(left, right, t, prune=prune, stats=st),
-                 lambda lf, rf, st: indel_raw_floor_grid(left, right, threshold, lf, rf, prune=prune, stats=st),
+    are also within ``margin`` of the right item's best.  A profile sweep at ``[threshold]``, then a floor grid.
+    ``metric`` as for ``indel_raw_top_k``."""
+    return _best(lambda t, st: indel_raw_profile(left, right, t, prune=prune, stats=st, metric=metric),
+                 lambda lf, rf, st: indel_raw_floor_grid(left, right, threshold, lf, rf, prune=prune, stats=st, metric=metric),
                  margin, threshold, mutual, stats)
 
 
@@ -798,12 +841,14 @@ def jaccard_raw_best(left: SetTable, right: SetTable, margin: float = 0.0, thres
 
 def indel_levels_best(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable,
                       margin: float = 0.0, threshold: float = 0.0, mutual: bool = False, category_mode: int = _lib.CAT_NONE,
-                      prune: bool = True, banned=None, stats: Optional[list] = None) -> Hits:
-    """Best matches of ``indel_levels_grid(...)`` without the ``banned`` pairs (``indel_levels_top_k``'s preconditions)."""
+                      prune: bool = True, banned=None, stats: Optional[list] = None, metric: str = "indel") -> Hits:
+    """Best matches of ``indel_levels_grid(...)`` without the ``banned`` pairs (``indel_levels_top_k``'s preconditions and
+    ``metric``)."""
     tabs = (left, left_strings, right, right_strings)
-    return _best(lambda t, st: indel_levels_profile(*tabs, t, category_mode=category_mode, prune=prune, banned=banned, stats=st),
+    return _best(lambda t, st: indel_levels_profile(*tabs, t, category_mode=category_mode, prune=prune, banned=banned, stats=st,
+                                                    metric=metric),
                  lambda lf, rf, st: indel_levels_floor_grid(*tabs, threshold, lf, rf, category_mode=category_mode, prune=prune,
-                                                            banned=banned, stats=st),
+                                                            banned=banned, stats=st, metric=metric),
                  margin, threshold, mutual, stats)
 
 
@@ -894,12 +939,14 @@ def _pairs(entry: str, tables: tuple, left, right, device, i, j, head: tuple = (
     return records[:, 0].cpu().numpy()
 
 
-def indel_raw_pairs(left: StrTable, right: StrTable, i, j) -> np.ndarray:
+def indel_raw_pairs(left: StrTable, right: StrTable, i, j, metric: str = "indel") -> np.ndarray:
     """The ``fuzzy_match`` score of every listed pair: ``i`` / ``j`` are integer arrays of equal length holding caller ids
     (the tables' ``orig`` values).  Returns float64 scores in the caller's order -- ``lookup_pairs(indel_raw_grid(left,
-    right, -inf), i, j)`` bit for bit, ``-1.0`` for an id the table does not hold -- in O(P), by ``nsm_indel_raw_pairs``."""
+    right, -inf), i, j)`` bit for bit, ``-1.0`` for an id the table does not hold -- in O(P), by ``nsm_indel_raw_pairs``.
+    ``metric``: another string metric (``check_metric``: ``nsm_edit_raw_pairs``)."""
     i, j = check_pair_ids(i, j)
-    return _pairs("nsm_indel_raw_pairs", (left, right), left, right, left.codes.device, i, j)
+    entry, head = _edit_entry("nsm_indel_raw_pairs", metric)
+    return _pairs(entry, (left, right), left, right, left.codes.device, i, j, head)
 
 
 def jaccard_raw_pairs(left: SetTable, right: SetTable, i, j, measure: str = "union") -> np.ndarray:
@@ -913,12 +960,14 @@ def jaccard_raw_pairs(left: SetTable, right: SetTable, i, j, measure: str = "uni
     return _pairs(entry, (left, right), left, right, left.ids.device, i, j, head)
 
 
-def indel_levels_pairs(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, i, j) -> np.ndarray:
+def indel_levels_pairs(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, i, j,
+                       metric: str = "indel") -> np.ndarray:
     """The ``compare_terms`` x ``fuzzy_match`` score of every listed pair of items, as ``indel_levels_grid`` computes it --
     without category predicate or blacklist.  ``-1.0`` also for a pair with an item without levels.  Tables must be encoded
-    with ``partition=False``."""
+    with ``partition=False``.  ``metric``: another string metric (``check_metric``: ``nsm_edit_levels_pairs``)."""
     i, j = check_pair_ids(i, j)
-    return _pairs("nsm_indel_levels_pairs", (left, left_strings, right, right_strings), left, right, left.first.device, i, j)
+    entry, head = _edit_entry("nsm_indel_levels_pairs", metric)
+    return _pairs(entry, (left, left_strings, right, right_strings), left, right, left.first.device, i, j, head)
 
 
 def jaccard_levels_pairs(left: SetTable, right: SetTable, i, j, measure: str = "union") -> np.ndarray:
@@ -1045,14 +1094,22 @@ def indel_levels_grid(
     left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, threshold: float,
     category_mode: int = _lib.CAT_NONE, prune: bool = True, capacity: Optional[int] = None, wave_wide: bool = False,
     park: bool = False, workspace: Optional[int] = None, return_overflow: Optional[list] = None, defer: bool = False,
-    probe: Optional[bool] = None, route: Optional[list] = None,
+    probe: Optional[bool] = None, route: Optional[list] = None, metric: str = "indel", banned=None,
 ) -> Hits:
     """``compare_terms`` with ``fuzzy_match`` over per-level strings.  ``wave_wide`` selects the kernel
     without block-cooperative parking, ``park`` the round-2 kernel for multi-word strings (same hits; A/B runs
     and tests).  ``workspace``: bytes of split-path scratch to hand to the library (None = what it asks for, 0 = none:
     the single-kernel path); ``return_overflow``: a list that receives the workspace's overflow word (tests).
     ``probe``: measure the survival rate of step 1 on a sample first and route by it (None = for large grids of one-word
-    strings; ``route`` receives what was decided)."""
+    strings; ``route`` receives what was decided).
+    ``metric``: another string metric (``check_metric``) -- its threshold grid is the floor grid without floors
+    (``nsm_edit_levels_floor_grid``: tables encoded with ``partition=False``, and ``banned`` as ``indel_levels_top_k``
+    takes it; the kernel switches, the workspace and the probe do not apply)."""
+    if check_metric(metric) != _lib.METRIC_INDEL:
+        return indel_levels_floor_grid(left, left_strings, right, right_strings, threshold, category_mode=category_mode,
+                                       prune=prune, banned=banned, capacity=capacity, defer=defer, metric=metric)
+    if banned is not None:
+        raise ValueError("banned: the Indel threshold grid takes no blacklist (indel_levels_floor_grid does)")
     lib = _lib.load()
     li, ls, ri, rs = left.struct(), left_strings.struct(), right.struct(), right_strings.struct()
     flags = (_lib.FLAG_PRUNE if prune else 0) | (_lib.FLAG_WAVE_WIDE if wave_wide else 0) | (_lib.FLAG_PARK if park else 0)
@@ -1203,10 +1260,12 @@ def _assign_pending(pending: PendingHits, left, right, route, stats: Optional[li
 
 
 def indel_raw_assign(left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
-                     two_stage: bool = True, pack: Optional[bool] = None, route=None, stats: Optional[list] = None) -> Hits:
+                     two_stage: bool = True, pack: Optional[bool] = None, route=None, stats: Optional[list] = None,
+                     metric: str = "indel") -> Hits:
     """``assign_of_hits(indel_raw_grid(left, right, threshold, ...))``: the grid's hits stay in their device buffer, are
     ordered and assigned there, and only the assignment (at most min(N, M) records) crosses to the host."""
-    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True)
+    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True,
+                             metric=metric)
     return _assign_pending(pending, left, right, route, stats)
 
 
@@ -1396,12 +1455,13 @@ def _groups_pending(pending: PendingHits, left, right, same: bool, min_score, st
 
 def indel_raw_groups(left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
                      two_stage: bool = True, pack: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
-                     stats: Optional[list] = None) -> MatchGroups:
+                     stats: Optional[list] = None, metric: str = "indel") -> MatchGroups:
     """``groups_of_hits([(indel_raw_grid(left, right, threshold, ...), 0, right's base)], ...)``: the grid's hits stay in
     their device buffer, unsorted, are linked there, and only the labels cross to the host.  ``same``: both tables
     describe the same items (a self-join), numbered in ONE node space -- near-duplicate clusters.  ``min_score``: only
     records scoring at least that link (None: every hit of the grid)."""
-    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True)
+    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True,
+                             metric=metric)
     return _groups_pending(pending, left, right, same, min_score, stats)
 
 
@@ -1663,12 +1723,13 @@ def _forest_pending(pending: PendingHits, left, right, threshold: float, same: b
 
 def indel_raw_forest(left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
                      two_stage: bool = True, pack: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
-                     stats: Optional[list] = None) -> MergeForest:
+                     stats: Optional[list] = None, metric: str = "indel") -> MergeForest:
     """``forest_of_hits([(indel_raw_grid(left, right, threshold, ...), 0, right's base)], ...)``: the grid's hits stay in
     their device buffer, are spanned there, and only the forest (fewer records than there are items) crosses to the host.
     ``same``: both tables describe the same items (a self-join), numbered in ONE node space.  ``min_score``: only records
     scoring at least that are edges (None: every hit of the grid; the forest then knows every threshold the grid does)."""
-    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True)
+    pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True,
+                             metric=metric)
     return _forest_pending(pending, left, right, threshold, same, min_score, stats)
 
 

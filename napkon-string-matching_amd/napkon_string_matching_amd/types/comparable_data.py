@@ -615,7 +615,7 @@ class ComparableData:
                 raise IndexError("single positional indexer is out-of-bounds")  # df.iloc[0] at :465
             cl, cr = list(lf[category_column]), list(rf[category_column])
             cats = _Categories(cl, cr, cl[first[0]], cr[first[1]])
-            if per_item is None and getattr(plugin, "measure", "union") != "union":
+            if per_item is None and (getattr(plugin, "measure", "union") != "union" or getattr(plugin, "metric", "indel") != "indel"):
                 per_item = f"score_func {score_func}"  # (its grid is a per-item sweep: floors_levels.hip without floors)
             if per_item is not None and not cats.on_device:
                 raise NotImplementedError(f"{per_item} with more than 64 distinct category labels (the predicate must run on "
@@ -1110,27 +1110,37 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
         "fuzzy", items, lambda it: [score_functions.fuzzy_operand(lv) for lv in it])
     ops_l, ops_r = prep(levels_l), prep(levels_r)
 
+    metric = getattr(plugin, "metric", "indel")  # (beside "indel" every query is a per-item sweep: tables without a category partition)
+
     def fast(li, ri, defer=False):
         if profile is not None:
             a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
                                                      partition=False)
-            return grid.indel_levels_profile(a, b, c, d, profile, category_mode=cat_mode, banned=_restrict_banned(banned, li, ri))
+            return grid.indel_levels_profile(a, b, c, d, profile, category_mode=cat_mode, banned=_restrict_banned(banned, li, ri),
+                                             metric=metric)
         if floors is not None:
             a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
                                                      partition=False)
             return grid.indel_levels_floor_grid(a, b, c, d, threshold, *cut_floors(li, ri), category_mode=cat_mode,
-                                                banned=_restrict_banned(banned, li, ri))
+                                                banned=_restrict_banned(banned, li, ri), metric=metric)
+        if top_k is None and metric != "indel":
+            a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
+                                                     partition=False)
+            return grid.indel_levels_grid(a, b, c, d, threshold, category_mode=cat_mode, defer=defer, metric=metric,
+                                          banned=_restrict_banned(banned, li, ri))
         if top_k is None:
             a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode)
             return grid.indel_levels_grid(a, b, c, d, threshold, category_mode=cat_mode, defer=defer)
         a, b, c, d = tables.encode_level_strings(sub(ops_l, li), sub(ops_r, ri), dev, cut(cat_l, li), cut(cat_r, ri), cat_mode,
                                                  partition=False)
         return grid.indel_levels_top_k(a, b, c, d, top_k, threshold, category_mode=cat_mode,
-                                       banned=_restrict_banned(banned, li, ri))
+                                       banned=_restrict_banned(banned, li, ri), metric=metric)
 
     split = wide.wide_string_items(ops_l, ops_r)
     if split is None:
         return fast(None, None, defer)
+    _need_general(plugin, f"a level string of more than {wide.FAST_LEN} code units, more than {wide.FAST_ALPHABET} distinct code "
+                          f"units in the grid, or an item of more than {wide.FAST_LEVELS} levels")
     # level strings of more than 512 code units / a grid of more than 255 distinct code units (wide.py)
     general = lambda li, ri: wide.indel_any_grid(sub(ops_l, li), sub(ops_r, ri), threshold, cut(cat_l, li), cut(cat_r, ri),
                                                  cat_mode, device=dev)
@@ -1138,10 +1148,12 @@ def _levels_grid(plugin, levels_l, levels_r, threshold, cat_l, cat_r, cat_mode=_
 
 
 def _need_general(plugin, what: str) -> None:
-    """The general (any-operand) kernels score Jaccard alone: another measure refuses what only they can take, before any
-    launch."""
+    """The general (any-operand) kernels score Jaccard and the Indel ratio alone: another measure or string metric refuses
+    what only they can take, before any launch."""
     if getattr(plugin, "measure", "union") != "union":
         raise NotImplementedError(f"{plugin.__name__}: {what} (measure {plugin.measure!r} has no general kernel)")
+    if getattr(plugin, "metric", "indel") != "indel":
+        raise NotImplementedError(f"{plugin.__name__}: {what} (metric {plugin.metric!r} has no general kernel)")
 
 
 # =============================================================================== listed pairs
@@ -1193,10 +1205,14 @@ def _levels_pairs(plugin, levels_l, levels_r, pi: np.ndarray, pj: np.ndarray) ->
 
     def fast(li, ri, qi, qj):
         a, b, c, d = tables.encode_level_strings([ops_l[k] for k in li], [ops_r[k] for k in ri], dev, partition=False)
-        return grid.indel_levels_pairs(a, b, c, d, qi, qj)
+        return grid.indel_levels_pairs(a, b, c, d, qi, qj, metric=getattr(plugin, "metric", "indel"))
 
     general = lambda li, ri: wide.indel_any_grid([ops_l[k] for k in li], [ops_r[k] for k in ri], float("-inf"), device=dev)
-    return wide.split_pairs(wide.wide_string_items(ops_l, ops_r), pi, pj, fast, general)
+    split = wide.wide_string_items(ops_l, ops_r)
+    if split is not None:
+        _need_general(plugin, f"a level string of more than {wide.FAST_LEN} code units, more than {wide.FAST_ALPHABET} distinct "
+                              f"code units among the listed items, or an item of more than {wide.FAST_LEVELS} levels")
+    return wide.split_pairs(split, pi, pj, fast, general)
 
 
 # =============================================================================== per-item top-k
