@@ -179,6 +179,9 @@ EDIT_EXPORTS = (
     "nsm_edit_levels_pairs",
 )
 
+# include/nsm_hip_support.h, likewise
+SUPPORT_EXPORTS = ("nsm_support_hits",)
+
 _lib = None
 
 
@@ -278,6 +281,8 @@ def load() -> ctypes.CDLL:
     group_args = {"nsm_group_hits": [P(NsmHitList), i32, i32, ctypes.c_double, u32, vp, vp, vp]}
     # lists (host), n_lists, nodes, min_score, flags, forest, forest_count, label, stats, stream
     span_args = {"nsm_span_hits": [P(NsmHitList), i32, i32, ctypes.c_double, u32, vp, vp, vp, vp, vp]}
+    # lists (host), n_lists, nodes, min_score, min_support, support (host array of device pointers), stats, stream
+    support_args = {"nsm_support_hits": [P(NsmHitList), i32, i32, ctypes.c_double, i32, P(ctypes.c_void_p), vp, vp]}
     sets = [P(NsmSetTable), P(NsmSetTable), i32]  # left, right, measure; then the tail of the nsm_jaccard_* counterpart
     measure_args = {
         "nsm_set_raw_top_k": sets + top_k_tail,
@@ -304,7 +309,7 @@ def load() -> ctypes.CDLL:
         "nsm_edit_levels_pairs": levs + pairs_tail,
     }
     for names, args in ((ASSIGN_EXPORTS, assign_args), (GROUP_EXPORTS, group_args), (SPAN_EXPORTS, span_args),
-                        (MEASURE_EXPORTS, measure_args), (EDIT_EXPORTS, edit_args)):
+                        (MEASURE_EXPORTS, measure_args), (EDIT_EXPORTS, edit_args), (SUPPORT_EXPORTS, support_args)):
         for name in names:
             try:
                 fn = getattr(lib, name)

@@ -354,15 +354,18 @@ class _IntersectionVsUnion:
         return grid.jaccard_raw_assign(lt, rt, threshold, prune=prune, measure=self.measure)
 
     def groups(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
-               prune: bool = True, same: bool = False) -> grid.MatchGroups:
+               prune: bool = True, same: bool = False, min_support=0) -> grid.MatchGroups:
         """``grid.groups_of_hits`` of ``raw_grid(left_items, right_items, threshold)``: the items of both lists grouped by
         the pairs scoring ``>= threshold``, closed transitively (left item k is node k, right item k node N + k; with
         ``same`` both lists are the same items in one node space).  The hits are linked on the device, unsorted, and only
         the labels come back; where wide items send part of the grid through the general kernels the merged host list goes
-        through ``grid.group_hits``."""
+        through ``grid.group_hits``.  ``min_support > 0``: only the pairs of the ``(min_support + 2)``-truss link (every
+        linking pair has that many common neighbours among the linking pairs; ``grid.group_hits`` has the definition), so
+        chains fall apart -- for ``same=True``: two separate lists are a bipartite graph without common neighbours."""
         from .. import wide
 
         grid.check_thresholds([threshold])
+        min_support = grid.check_min_support(min_support)
         l_rows, r_rows = self._rows(left_items, right_items)
         dev = device or _device()
         n_l, n_r = len(l_rows), len(r_rows)
@@ -371,17 +374,21 @@ class _IntersectionVsUnion:
             return grid.MatchGroups(np.arange(sum(layout[1]), dtype=np.int32), *layout)
         if wide.wide_set_items([[r] for r in l_rows], [[r] for r in r_rows]) is not None:
             hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
-            return grid.MatchGroups(grid.group_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float("-inf"), device=dev), *layout)
+            return grid.MatchGroups(grid.group_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float("-inf"), device=dev,
+                                                    min_support=min_support), *layout)
         vocab = tables.Vocabulary()
         width = tables.pick_width(max((len(set(r)) for r in l_rows), default=1), max((len(set(r)) for r in r_rows), default=1))
         lt = tables.SetTable.from_rows(l_rows, "left", dev, vocab, width=width)
         rt = tables.SetTable.from_rows(r_rows, "right", dev, vocab, width=width)
-        return grid.jaccard_raw_groups(lt, rt, threshold, prune=prune, same=same, measure=self.measure)
+        return grid.jaccard_raw_groups(lt, rt, threshold, prune=prune, same=same, measure=self.measure, min_support=min_support)
 
-    def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> List[np.ndarray]:
+    def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True,
+                 min_support=0) -> List[np.ndarray]:
         """Near-duplicate clusters inside ONE list (dedupe): the self-join's groups of at least two items, each an
-        ascending array of positions in ``items``, ordered by their smallest member."""
-        return [members[0] for members in self.groups(items, items, threshold, device=device, prune=prune, same=True).members(2)]
+        ascending array of positions in ``items``, ordered by their smallest member.  ``min_support``: as for ``groups`` -- with 1 a chain of
+        near-duplicates no longer swallows the list, every linking pair needs a third item close to both."""
+        groups = self.groups(items, items, threshold, device=device, prune=prune, same=True, min_support=min_support)
+        return [members[0] for members in groups.members(2)]
 
     def forest(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
                prune: bool = True, same: bool = False) -> grid.MergeForest:
@@ -582,15 +589,18 @@ class _FuzzyMatch:
         return grid.indel_raw_assign(lt, rt, threshold, prune=prune, metric=self.metric)
 
     def groups(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
-               prune: bool = True, same: bool = False) -> grid.MatchGroups:
+               prune: bool = True, same: bool = False, min_support=0) -> grid.MatchGroups:
         """``grid.groups_of_hits`` of ``raw_grid(left_items, right_items, threshold)``: the items of both lists grouped by
         the pairs scoring ``>= threshold``, closed transitively (left item k is node k, right item k node N + k; with
         ``same`` both lists are the same items in one node space).  The hits are linked on the device, unsorted, and only
         the labels come back; where wide items send part of the grid through the general kernels the merged host list goes
-        through ``grid.group_hits``."""
+        through ``grid.group_hits``.  ``min_support > 0``: only the pairs of the ``(min_support + 2)``-truss link (every
+        linking pair has that many common neighbours among the linking pairs; ``grid.group_hits`` has the definition), so
+        chains fall apart -- for ``same=True``: two separate lists are a bipartite graph without common neighbours."""
         from .. import wide
 
         grid.check_thresholds([threshold])
+        min_support = grid.check_min_support(min_support)
         l_ops, r_ops = [fuzzy_operand(v) for v in left_items], [fuzzy_operand(v) for v in right_items]
         split = self._split([[s] for s in l_ops], [[s] for s in r_ops])  # (before the device is asked for)
         dev = device or _device()
@@ -600,14 +610,18 @@ class _FuzzyMatch:
             return grid.MatchGroups(np.arange(sum(layout[1]), dtype=np.int32), *layout)
         if split is not None:
             hits = self.raw_grid(left_items, right_items, threshold, device=dev, prune=prune)
-            return grid.MatchGroups(grid.group_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float("-inf"), device=dev), *layout)
+            return grid.MatchGroups(grid.group_hits([(hits, 0, layout[0][-1])], sum(layout[1]), float("-inf"), device=dev,
+                                                    min_support=min_support), *layout)
         lt, rt = tables.encode_strings(l_ops, r_ops, dev)
-        return grid.indel_raw_groups(lt, rt, threshold, prune=prune, same=same, metric=self.metric)
+        return grid.indel_raw_groups(lt, rt, threshold, prune=prune, same=same, metric=self.metric, min_support=min_support)
 
-    def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True) -> List[np.ndarray]:
+    def clusters(self, items: Sequence[Operand], threshold: float, device=None, prune: bool = True,
+                 min_support=0) -> List[np.ndarray]:
         """Near-duplicate clusters inside ONE list (rapidfuzz users' dedupe): the self-join's groups of at least two items,
-        each an ascending array of positions in ``items``, ordered by their smallest member."""
-        return [members[0] for members in self.groups(items, items, threshold, device=device, prune=prune, same=True).members(2)]
+        each an ascending array of positions in ``items``, ordered by their smallest member.  ``min_support``: as for ``groups`` -- with 1 a chain of
+        near-duplicates no longer swallows the list, every linking pair needs a third item close to both."""
+        groups = self.groups(items, items, threshold, device=device, prune=prune, same=True, min_support=min_support)
+        return [members[0] for members in groups.members(2)]
 
     def forest(self, left_items: Sequence[Operand], right_items: Sequence[Operand], threshold: float, device=None,
                prune: bool = True, same: bool = False) -> grid.MergeForest:

@@ -8,6 +8,7 @@ here, before the launch, from per-item properties; the kernels never see such a 
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Callable, Optional
 
@@ -1387,24 +1388,28 @@ def group_lists_device(entries, nodes: int, min_score: float, dev, start=None, s
     return label.cpu().numpy()
 
 
-def group_hits(lists, nodes: int, min_score: float = 0.0, start=None, device=None, stats: Optional[list] = None) -> np.ndarray:
+def group_hits(lists, nodes: int, min_score: float = 0.0, start=None, device=None, stats: Optional[list] = None,
+               min_support=0) -> np.ndarray:
     """``groups_of_hits(lists, nodes, min_score, start)`` on the device for host hit lists: upload (in any order), one
     ``nsm_group_hits`` call over all lists, one D2H copy of ``nodes`` words.  Ids must be ``>= 0`` and every record must
-    stay inside the nodes (``ValueError``).  ``stats`` receives [records with score >= min_score, hooks made]."""
+    stay inside the nodes (``ValueError``).  ``stats`` receives [records with score >= min_score, hooks made].
+
+    ``min_support > 0``: the groups are the connected components of the ``(min_support + 2)``-truss of the records
+    ``>= min_score`` -- ``groups_of_hits`` over the records whose ``truss_of_hits`` word is ``>= 0`` -- so a chain
+    a-b, b-c without a-c no longer makes one group, and a larger ``min_support`` refines the groups.  ``nsm_support_hits``
+    runs on the device lists, the alive records are compacted there and linked by ``nsm_group_hits`` as always.  Meant for
+    self-joins, overlapping node ranges and three or more cohorts: two disjoint cohorts are a bipartite graph, where every
+    support is 0 and every group dissolves."""
+    min_support = check_min_support(min_support)
     dev = _require_gpu("cuda" if device is None else device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     nodes = int(nodes)
     if nodes < 0:
         raise ValueError("group_hits: nodes must be >= 0")
-    entries, keep = [], []
-    for hits, left_base, right_base in lists:
-        _list_nodes(hits, left_base, right_base, nodes, "group_hits")
-        recs = _records_to_device(hits, dev)
-        keep.append(recs)
-        # (any id that stays inside the nodes is a node: the id counts reach to the end of the node space)
-        entries.append((recs.data_ptr() if recs is not None else 0, len(hits), int(left_base), nodes - int(left_base),
-                        int(right_base), nodes - int(right_base)))
+    entries, keep = _upload_lists(lists, nodes, dev, "group_hits")
+    if min_support:
+        entries, keep = _truss_entries(entries, keep, nodes, min_score, min_support, dev)
     return group_lists_device(entries, nodes, min_score, dev, start, stats)
 
 
@@ -1439,7 +1444,9 @@ class MatchGroups:
         return out
 
 
-def _groups_pending(pending: PendingHits, left, right, same: bool, min_score, stats: Optional[list]) -> MatchGroups:
+def _groups_pending(pending: PendingHits, left, right, same: bool, min_score, stats: Optional[list],
+                    min_support=0) -> MatchGroups:
+    min_support = check_min_support(min_support)
     # (nsm_group_hits indexes the labels by caller id)
     ids_l, ids_r = _id_count(left.orig, left.n, "groups"), _id_count(right.orig, right.n, "groups")
     if same:  # one node space: left item k and right item k are the same node
@@ -1448,49 +1455,195 @@ def _groups_pending(pending: PendingHits, left, right, same: bool, min_score, st
         nodes, bases, sizes = ids_l + ids_r, (0, ids_l), (ids_l, ids_r)
     floor = float("-inf") if min_score is None else float(min_score)
     # the buffer goes in UNSORTED: components need no order
-    label = group_lists_device([(pending.buf.records.data_ptr(), pending.n, 0, ids_l, bases[-1], ids_r)], nodes, floor,
-                               pending.buf.records.device, None, stats)
+    entries, dev = [(pending.buf.records.data_ptr(), pending.n, 0, ids_l, bases[-1], ids_r)], pending.buf.records.device
+    if min_support:  # only the records of the (min_support + 2)-truss link (group_hits has the meaning)
+        entries, _keep = _truss_entries(entries, [pending.buf.records], nodes, floor, min_support, dev)
+    label = group_lists_device(entries, nodes, floor, dev, None, stats)
     return MatchGroups(label, bases, sizes)
 
 
 def indel_raw_groups(left: StrTable, right: StrTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
                      two_stage: bool = True, pack: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
-                     stats: Optional[list] = None, metric: str = "indel") -> MatchGroups:
+                     stats: Optional[list] = None, metric: str = "indel", min_support=0) -> MatchGroups:
     """``groups_of_hits([(indel_raw_grid(left, right, threshold, ...), 0, right's base)], ...)``: the grid's hits stay in
     their device buffer, unsorted, are linked there, and only the labels cross to the host.  ``same``: both tables
     describe the same items (a self-join), numbered in ONE node space -- near-duplicate clusters.  ``min_score``: only
-    records scoring at least that link (None: every hit of the grid)."""
+    records scoring at least that link (None: every hit of the grid).  ``min_support > 0``: only the records of the
+    ``(min_support + 2)``-truss link (``group_hits`` has the meaning; for ``same=True`` -- two disjoint cohorts are
+    bipartite and dissolve): ``nsm_support_hits`` on the buffer, the alive records compacted on the device."""
+    check_min_support(min_support)  # (before any device work)
     pending = indel_raw_grid(left, right, threshold, prune=prune, capacity=capacity, two_stage=two_stage, pack=pack, defer=True,
                              metric=metric)
-    return _groups_pending(pending, left, right, same, min_score, stats)
+    return _groups_pending(pending, left, right, same, min_score, stats, min_support)
 
 
 def jaccard_raw_groups(left: SetTable, right: SetTable, threshold: float, prune: bool = True, capacity: Optional[int] = None,
                        index: Optional[bool] = None, same: bool = False, min_score: Optional[float] = None,
-                       stats: Optional[list] = None, measure: str = "union") -> MatchGroups:
+                       stats: Optional[list] = None, measure: str = "union", min_support=0) -> MatchGroups:
     """``intersection_vs_union`` counterpart of ``indel_raw_groups`` (``measure`` as for ``jaccard_raw_grid``)."""
+    check_min_support(min_support)  # (before any device work)
     pending = jaccard_raw_grid(left, right, threshold, prune=prune, capacity=capacity, index=index, defer=True, measure=measure)
-    return _groups_pending(pending, left, right, same, min_score, stats)
+    return _groups_pending(pending, left, right, same, min_score, stats, min_support)
 
 
 def indel_levels_groups(left: LevelItems, left_strings: StrTable, right: LevelItems, right_strings: StrTable, threshold: float,
                         category_mode: int = _lib.CAT_NONE, prune: bool = True, capacity: Optional[int] = None, same: bool = False,
-                        min_score: Optional[float] = None, stats: Optional[list] = None, **grid_options) -> MatchGroups:
+                        min_score: Optional[float] = None, stats: Optional[list] = None, min_support=0, **grid_options) -> MatchGroups:
     """``groups_of_hits`` of ``indel_levels_grid(...)``'s hits without them leaving the device (``grid_options``: the grid's
     other keywords)."""
+    check_min_support(min_support)  # (before any device work)
     pending = indel_levels_grid(left, left_strings, right, right_strings, threshold, category_mode=category_mode, prune=prune,
                                 capacity=capacity, defer=True, **grid_options)
-    return _groups_pending(pending, left, right, same, min_score, stats)
+    return _groups_pending(pending, left, right, same, min_score, stats, min_support)
 
 
 def jaccard_levels_groups(left: SetTable, right: SetTable, threshold: float, category_mode: int = _lib.CAT_NONE,
                           prune: bool = True, capacity: Optional[int] = None, index: Optional[bool] = None, same: bool = False,
                           min_score: Optional[float] = None, stats: Optional[list] = None, measure: str = "union",
-                          banned=None) -> MatchGroups:
+                          banned=None, min_support=0) -> MatchGroups:
     """``intersection_vs_union`` counterpart of ``indel_levels_groups`` (``measure``, ``banned`` as for ``jaccard_levels_grid``)."""
+    check_min_support(min_support)  # (before any device work)
     pending = jaccard_levels_grid(left, right, threshold, category_mode=category_mode, prune=prune, capacity=capacity,
                                   index=index, defer=True, measure=measure, banned=banned)
-    return _groups_pending(pending, left, right, same, min_score, stats)
+    return _groups_pending(pending, left, right, same, min_score, stats, min_support)
+
+
+# ------------------------------------------------------------------------------- edge support and truss groups
+def check_min_support(min_support) -> int:
+    """``min_support`` as an int: an integer ``>= 0`` (``ValueError`` otherwise -- 1.5 and "1" are not integers)."""
+    if isinstance(min_support, (bool, np.bool_)) or not isinstance(min_support, (int, np.integer)):
+        raise ValueError(f"min_support must be an integer >= 0, not {min_support!r}")
+    if int(min_support) < 0 or int(min_support) > 0x7FFFFFFF:
+        raise ValueError(f"min_support must be an integer >= 0, not {min_support!r}")
+    return int(min_support)
+
+
+def _edge_keys(lists, nodes: int, min_score: float, what: str):
+    """Per list the key ``min(u, v) * nodes + max(u, v)`` of every record (int64) and which records are edge records."""
+    out = []
+    for hits, left_base, right_base in lists:
+        u, v = _list_nodes(hits, left_base, right_base, nodes, what)
+        edge = (np.asarray(hits.score, dtype=np.float64) >= min_score) & (u != v)  # (a NaN compares false)
+        out.append((np.minimum(u, v) * max(nodes, 1) + np.maximum(u, v), edge))
+    return out
+
+
+def truss_of_hits(lists, nodes: int, min_support, min_score: float = 0.0):
+    """The definition of edge support and of the truss.  ``lists = [(Hits, left_base, right_base), ...]`` in the node space
+    of ``groups_of_hits``.  Record ``(score, i, j)`` is an EDGE RECORD iff ``score >= min_score`` (a NaN never is) and
+    ``u = left_base + i != v = right_base + j``; ``E`` is the set of unordered pairs ``{u, v}`` of all edge records of all
+    lists together (duplicates and the two orientations of a self-join collapse), ``N(u) = {w : {u, w} in E}``.
+
+    Peeling is synchronous: a round counts every alive edge's support ``|N(u) & N(v)|`` among the alive edges, then removes
+    ALL alive edges with support ``< min_support`` at once; it stops after the first round that removes nothing.  Returns
+    ``([int32 array per list], rounds)``: per record its edge's support in the final graph (``>= min_support``), ``-2`` for
+    an edge record whose edge was removed, ``-1`` for any other record; ``rounds`` counts the counting passes, the last one
+    included.  What is left is the ``(min_support + 2)``-truss (``networkx.k_truss(G, min_support + 2)``): the fixpoint is
+    unique, so the order of removal -- and of records and lists -- does not matter.  Python sets on the host."""
+    nodes, min_support = int(nodes), check_min_support(min_support)
+    if nodes < 0:
+        raise ValueError("truss_of_hits: nodes must be >= 0")
+    keyed = _edge_keys(lists, nodes, min_score, "truss_of_hits")
+    edges = np.unique(np.concatenate([key[edge] for key, edge in keyed])) if keyed else np.zeros(0, dtype=np.int64)
+    ends = [(int(k) // max(nodes, 1), int(k) % max(nodes, 1)) for k in edges.tolist()]
+    alive = np.ones(len(ends), dtype=bool)
+    support = np.zeros(len(ends), dtype=np.int32)
+    rounds = 0
+    while True:
+        rounds += 1
+        near = {}
+        for e, (a, b) in enumerate(ends):
+            if alive[e]:
+                near.setdefault(a, set()).add(b)
+                near.setdefault(b, set()).add(a)
+        for e, (a, b) in enumerate(ends):
+            support[e] = len(near[a] & near[b]) if alive[e] else 0
+        drop = alive & (support < min_support)
+        if not drop.any():
+            break
+        alive &= ~drop
+    words = []
+    for key, edge in keyed:
+        out = np.full(len(key), -1, dtype=np.int32)
+        at = np.searchsorted(edges, key[edge])
+        out[edge] = np.where(alive[at], support[at], -2)
+        words.append(out)
+    return words, rounds
+
+
+def support_of_hits(lists, nodes: int, min_score: float = 0.0):
+    """Per list an int32 array aligned with its records: ``|N(u) & N(v)|``, the number of common neighbours of the record's
+    two ends, for an edge record and ``-1`` for any other (``truss_of_hits`` has the definitions; this is its
+    ``min_support = 0``).  Independent of record order, list order and duplicates."""
+    return truss_of_hits(lists, nodes, 0, min_score)[0]
+
+
+def support_lists_device(entries, nodes: int, min_score: float, min_support: int, dev, stats: Optional[list] = None):
+    """One ``nsm_support_hits`` call (include/nsm_hip_support.h) over device lists; the words stay on the device: per list
+    an int32 tensor aligned with its records (``truss_of_hits``).  ``entries`` as for ``group_lists_device``.  ``stats``
+    receives [edge records, distinct edges, distinct edges alive at the end, rounds, sum of the final supports]."""
+    min_support = check_min_support(min_support)
+    fn = _lib.entry("nsm_support_hits")
+    nodes = int(nodes)
+    words = [torch.empty(int(n), dtype=torch.int32, device=dev) for _ptr, n, *_rest in entries]
+    lists = (_lib.NsmHitList * max(1, len(entries)))()
+    out = (ctypes.c_void_p * max(1, len(entries)))()
+    for k, (slot, (ptr, n, left_base, left_ids, right_base, right_ids)) in enumerate(zip(lists, entries)):
+        slot.hits, slot.n = (ptr if n else None), int(n)
+        slot.left_base, slot.left_ids, slot.right_base, slot.right_ids = int(left_base), int(left_ids), int(right_base), int(right_ids)
+        out[k] = words[k].data_ptr() if n else None
+    st = torch.zeros(5, dtype=torch.int64, device=dev) if stats is not None else None
+    status = fn(lists, len(entries), nodes, float(min_score), min_support, out, st.data_ptr() if st is not None else None,
+                torch.cuda.current_stream(dev).cuda_stream)
+    if status == 10001:
+        raise ValueError("nsm_support_hits: " + _lib.load().nsm_last_error().decode("utf-8", "replace"))
+    _lib.check(status, "nsm_support_hits")
+    if stats is not None:
+        stats[:] = [int(v) for v in st.tolist()]
+    return words
+
+
+def _upload_lists(lists, nodes: int, dev, what: str):
+    """Host lists as device records and the entries ``group_lists_device`` / ``support_lists_device`` take."""
+    entries, keep = [], []
+    for hits, left_base, right_base in lists:
+        _list_nodes(hits, left_base, right_base, nodes, what)
+        recs = _records_to_device(hits, dev)
+        keep.append(recs)
+        # (any id that stays inside the nodes is a node: the id counts reach to the end of the node space)
+        entries.append((recs.data_ptr() if recs is not None else 0, len(hits), int(left_base), nodes - int(left_base),
+                        int(right_base), nodes - int(right_base)))
+    return entries, keep
+
+
+def support_hits(lists, nodes: int, min_score: float = 0.0, min_support=0, device=None, stats: Optional[list] = None):
+    """``truss_of_hits(lists, nodes, min_support, min_score)[0]`` on the device for host hit lists (``min_support = 0``:
+    ``support_of_hits``): upload (in any order), one ``nsm_support_hits`` call over all lists, one D2H copy of the words.
+    ``stats`` as for ``support_lists_device``; ``stats[3]`` is the definition's ``rounds`` wherever there is a record."""
+    min_support = check_min_support(min_support)
+    dev = _require_gpu("cuda" if device is None else device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    nodes = int(nodes)
+    if nodes < 0:
+        raise ValueError("support_hits: nodes must be >= 0")
+    entries, _keep = _upload_lists(lists, nodes, dev, "support_hits")
+    words = support_lists_device(entries, nodes, min_score, min_support, dev, stats)
+    return [w.cpu().numpy() for w in words]
+
+
+def _truss_entries(entries, records, nodes: int, min_score: float, min_support: int, dev):
+    """The entries of the records that survive the ``(min_support + 2)``-truss: ``nsm_support_hits`` on the device lists,
+    then the alive records (word ``>= 0``) compacted on the device.  ``records``: per list its ``[n, 2]`` float64 tensor
+    (None for an empty list).  Returns the new entries and the tensors they point into."""
+    words = support_lists_device(entries, nodes, min_score, min_support, dev)
+    out, keep = [], []
+    for (_ptr, n, left_base, left_ids, right_base, right_ids), recs, word in zip(entries, records, words):
+        alive = recs[: int(n)][word >= 0] if n else None
+        keep.append(alive)
+        count = 0 if alive is None else int(alive.shape[0])
+        out.append((alive.data_ptr() if count else 0, count, left_base, left_ids, right_base, right_ids))
+    return out, keep
 
 
 # ------------------------------------------------------------------------------- merge forests

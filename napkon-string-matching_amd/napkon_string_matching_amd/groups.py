@@ -107,13 +107,16 @@ def mapping_of_labels(label, cohorts: Sequence[str], identifiers: Sequence[Seque
 
 
 def mapping_of_results(results: ComparisonResults, min_score: Optional[float] = None, id_reference: Optional[Mapping] = None,
-                       device=None) -> Mapping:
+                       device=None, min_support=0) -> Mapping:
     """The ``Mapping`` of a run: every frame's rows scoring ``>= min_score`` (None: all rows) are edges between
-    identifiers, closed transitively over ALL frames in one ``grid.group_hits`` call."""
+    identifiers, closed transitively over ALL frames in one ``grid.group_hits`` call.  ``min_support > 0``: only the rows of
+    the ``(min_support + 2)``-truss link (``grid.group_hits``): with 1, ``hap:A ~ pop:B`` and ``pop:B ~ suep:C`` make an
+    entry only where ``hap:A ~ suep:C`` is a row too.  Needs three or more cohorts: two are a bipartite graph."""
+    min_support = grid.check_min_support(min_support)
     cohorts, identifiers, lists = lists_of_results(results)
     nodes = sum(len(ids) for ids in identifiers)
     floor = float("-inf") if min_score is None else float(min_score)
-    label = grid.group_hits(lists, nodes, floor, device=device)
+    label = grid.group_hits(lists, nodes, floor, device=device, min_support=min_support)
     return mapping_of_labels(label, cohorts, identifiers, id_reference)
 
 

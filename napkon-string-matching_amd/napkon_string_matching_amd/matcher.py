@@ -102,13 +102,15 @@ class Matcher:
             score_threshold=self.config[CONFIG_FIELD_MATCHING][CONFIG_VARIABLE_THRESHOLD],
         )
 
-    def match_groups(self, min_score: Optional[float] = None, id_reference: Optional[Mapping] = None) -> Mapping:
+    def match_groups(self, min_score: Optional[float] = None, id_reference: Optional[Mapping] = None, min_support=0) -> Mapping:
         """The run's results as a ``Mapping``: the rows of ALL cohort pairs scoring ``>= min_score`` (None: every row)
         closed transitively into entries ``{id: {cohort: [identifier, ...]}}`` (``groups.mapping_of_results``; linked on the
-        device).  ``id_reference``: a mapping whose entry ids are kept where its members are found again."""
+        device).  ``id_reference``: a mapping whose entry ids are kept where its members are found again.  ``min_support``:
+        only rows with that many common neighbours among the linking rows link (``groups.mapping_of_results``): with 1 an
+        entry needs its members matched pairwise through a third cohort, a chain a-b, b-c without a-c dissolves."""
         from .groups import mapping_of_results
 
-        return mapping_of_results(self.results, min_score=min_score, id_reference=id_reference)
+        return mapping_of_results(self.results, min_score=min_score, id_reference=id_reference, min_support=min_support)
 
     def match_forest(self, min_score: Optional[float] = None):
         """The run's results as a merge forest (``groups.forest_of_results``): ``match_groups`` at EVERY threshold
