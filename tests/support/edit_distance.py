@@ -62,6 +62,83 @@ def _dp_fast(a: str, b: str, is_within: bool) -> int:
     return best if is_within else int(prev[la])
 
 
+def _units(s) -> np.ndarray:
+    return np.frombuffer(s.encode("utf-32-le"), dtype=np.uint32).astype(np.int64) if isinstance(s, str) \
+        else np.asarray(s, dtype=np.int64).reshape(-1)
+
+
+def both_all(lefts, rights, chunk: int = 8):
+    """(d, w): int64 [len(lefts)][len(rights)] arrays of d(a, b) and w(a, b), each pair's two distances from ONE pass of
+    the two-row programme.  The rows of the distance and of the occurrence distance are stacked, a step along the texts
+    serves every b and ``chunk`` patterns at once (numpy), a b shorter than the longest simply stops taking part, and a
+    pattern shorter than its chunk's longest is padded with a unit that matches nothing (cell p of a row depends on the
+    cells up to p alone, so the pattern's own last cell is unharmed).  Strings: str or sequences of ints.  Checked
+    against ``_dp`` on the CPU."""
+    m = len(rights)
+    lens = np.array([len(b) for b in rights], dtype=np.int64)
+    order = np.argsort(-lens, kind="stable")  # longest first: the texts still taking part at step t are a prefix
+    longest = int(lens.max(initial=0))
+    text = np.full((m, longest), -1, dtype=np.int64)
+    for r, k in enumerate(order.tolist()):
+        text[r, : len(rights[k])] = _units(rights[k])
+    sorted_lens = lens[order]
+    taking_part = [int(np.searchsorted(-sorted_lens, -t, side="left")) for t in range(longest)]  # texts with len > t
+    steps = np.arange(longest + 1)[:, None, None]
+    d_all, w_all = np.empty((len(lefts), m), dtype=np.int64), np.empty((len(lefts), m), dtype=np.int64)
+    by_length = np.argsort([len(a) for a in lefts], kind="stable")
+    for c0 in range(0, len(lefts), chunk):
+        ids = by_length[c0: c0 + chunk]
+        las = np.array([len(lefts[k]) for k in ids], dtype=np.int64)
+        c, width = len(ids), int(las.max())
+        pattern = np.full((c, width), -2, dtype=np.int64)
+        for r, k in enumerate(ids.tolist()):
+            pattern[r, : las[r]] = _units(lefts[k])
+        rows = np.arange(c)
+        # rows shifted by their position, q[p] = row[p] - p (so q starts as zeros): the row's own dependency is then a plain
+        # running minimum, and q[p] = min(q_prev[p] + 1, q_prev[p - 1] + (a[p - 1] != b[t]) - 1)
+        q = np.zeros((2, c, m, width + 1), dtype=np.int16)
+        last = np.zeros((longest + 1, c, 2, m), dtype=np.int16)  # the pattern's last cell of either table after every step
+        for t in range(longest):
+            n = taking_part[t]
+            prev = q[:, :, :n]
+            cur = np.empty_like(prev)
+            cur[0, :, :, 0], cur[1, :, :, 0] = t + 1, 0
+            step = (pattern[:, None, :] != text[None, :n, t, None]).astype(np.int16) - 1
+            np.add(prev[..., 1:], 1, out=cur[..., 1:])
+            np.minimum(cur[..., 1:], prev[..., :-1] + step[None], out=cur[..., 1:])
+            np.minimum.accumulate(cur, axis=3, out=prev)
+            last[t + 1] = q[:, rows, :, las]
+        cells = last.astype(np.int64) + las[None, :, None, None]  # row[la] = q[la] + la; a finished text keeps its value
+        d_sorted = cells[sorted_lens[None, :], rows[:, None], 0, np.arange(m)[None, :]]
+        w_sorted = np.where(steps <= sorted_lens[None, None, :], cells[:, :, 1, :], las[None, :, None]).min(axis=0)
+        for r, k in enumerate(ids.tolist()):  # (step 0 of w: the empty occurrence)
+            d_all[k, order], w_all[k, order] = d_sorted[r], w_sorted[r]
+    return d_all, w_all
+
+
+def both_many(a, rights):
+    """(d(a, b), w(a, b)) of one pattern and every b of ``rights``, as lists: ``both_all`` of one pattern."""
+    d, w = both_all([a], rights)
+    return d[0].tolist(), w[0].tolist()
+
+
+def distance_table(lefts, texts, known=None) -> dict:
+    """``{(a, b): (d, w)}`` for every a of ``lefts`` and b of ``texts`` (hashable strings: str or tuples of code units),
+    added to ``known``: one ``both_all`` call.  The one place the yardsticks of the GPU files build their cache from."""
+    known = {} if known is None else known
+    lefts, texts = list(lefts), list(texts)
+    if lefts and texts:
+        d, w = both_all(lefts, texts)
+        for r, a in enumerate(lefts):
+            known.update({(a, b): dw for b, dw in zip(texts, zip(d[r].tolist(), w[r].tolist()))})
+    return known
+
+
+def plain_score(metric: str, la: int, lb: int, d: int, w: int) -> float:
+    """The definition on strings as they are (the C entries take prepared strings): ``score`` of the metric's own distance."""
+    return score(metric, la, lb, d if metric == "edit" else w)
+
+
 def prepared(value) -> str:
     """What both score functions feed to the distance for one operand: ``fuzzy_match``'s preparation."""
     return default_process(join_sorted(value) if isinstance(value, list) else value)
@@ -252,6 +329,83 @@ def saturated_corpus():
     right = ["a" * 280 + "k" * 20 + "b" * 100 + tail, "a" * 260 + "b" * 140 + tail, "a" * 512, "b" * 300 + "a" * 100 + tail,
              "a" * 300 + "b" * 100 + tail, "a" * 257, "k" * 256, "a" * 250 + "b" * 6, "b" * 256 + "a" * 256]
     return left, right
+
+
+# ------------------------------------------------------------------------------------------------------- explicit floors
+FLOOR_CORPORA = ("raw_64", "raw_256", "levels", "levels_wide")
+FLOOR_SHIFTS = {"below": -1, "on": 0, "above": 1}  # the floor against the score it is taken from, in doubles
+ABOVE_ALL = 2  # this left item's floor lies one double above its best score in every case: it admits nothing
+
+
+def caller_id(k):
+    """Caller ids with gaps: item k reports 3 k + 2 (the floor arrays are indexed by them)."""
+    return 3 * k + 2
+
+
+def by_caller_id(floors):
+    """A floor per item as the array the entries index by caller id; an id that names no item holds a NaN."""
+    out = np.full(caller_id(len(floors) - 1) + 1, np.nan)
+    out[[caller_id(k) for k in range(len(floors))]] = floors
+    return out
+
+
+def ranked_floors(records, n_left: int, n_right: int, rank: int, shift: int):
+    """(left floors, right floors) by item: the item's ``rank``-th distinct score from the top (0: its best, 1: its second
+    best; an item with fewer distinct scores: its lowest), moved ``shift`` doubles (``FLOOR_SHIFTS``).  Left item
+    ``ABOVE_ALL`` gets one double above its best instead."""
+    def side(pos, n):
+        per = {}
+        for r in records:
+            per.setdefault(r[pos], set()).add(r[0])
+        picked = [sorted(per[k], reverse=True)[min(rank, len(per[k]) - 1)] for k in range(n)]
+        return [f if shift == 0 else math.nextafter(f, 2.0 if shift > 0 else -1.0) for f in picked], per
+
+    (left, per_left), (right, _) = side(1, n_left), side(2, n_right)
+    left[ABOVE_ALL] = math.nextafter(max(per_left[ABOVE_ALL]), 2.0)
+    return left, right
+
+
+def floor_cases(records, n_left: int, n_right: int, shift: int):
+    """(label, left floors by item or None, right floors by item or None): the floors on the items' best and second-best
+    scores, on the left side only, on the right side only, and on both."""
+    out = []
+    for rank in (0, 1):
+        left, right = ranked_floors(records, n_left, n_right, rank, shift)
+        out += [(f"rank {rank} left", left, None), (f"rank {rank} right", None, right), (f"rank {rank} both", left, right)]
+    return out
+
+
+def floors_plain(records, left, right):
+    """The definition of a floor grid on records by item: ``score >= floor`` of both its items (None: no floor)."""
+    return [r for r in records if (left is None or r[0] >= left[r[1]]) and (right is None or r[0] >= right[r[2]])]
+
+
+_CORPUS = {}
+
+
+def floor_corpus(kind: str):
+    """(left, right) of a ``FLOOR_CORPORA`` name: ``raw_corpus`` at strides 64 and 256, the two ``levels_corpus``."""
+    if kind not in _CORPUS:
+        _CORPUS[kind] = raw_corpus(int(kind[4:])) if kind.startswith("raw_") else levels_corpus(kind == "levels_wide")
+    return _CORPUS[kind]
+
+
+def floor_corpus_records(kind: str, metric: str):
+    """Every pair's record of a floor corpus, canonical order, from ``distance_table`` (one pass gives d and w); the CPU
+    tests compare it with ``raw_hits`` / ``levels_hits``, which the GPU tests use."""
+    if (kind, metric) not in _CORPUS:
+        left, right = floor_corpus(kind)
+        known = _CORPUS.setdefault((kind, "d and w"), {})
+        if not known:
+            flat = lambda side: sorted({s for it in side for s in ([it] if isinstance(it, str) else it)})
+            distance_table(flat(left), flat(right), known)
+        f =lambda a, b: plain_score(metric, len(a), len(b), *known[a, b])
+        if kind.startswith("raw_"):
+            hits = [(f(a, b), i, j) for i, a in enumerate(left) for j, b in enumerate(right)]
+            _CORPUS[kind, metric] = sorted(hits, key=lambda h: (-h[0], h[1], h[2]))
+        else:
+            _CORPUS[kind, metric] = levels_hits(metric, left, right, f=f)
+    return _CORPUS[kind, metric]
 
 
 # --------------------------------------------------------------------------------------------------------- levels corpora

@@ -11,6 +11,10 @@ plain Python alone) and tests/test_gpu_value_ranges.py (every entry against the 
   their word count.
 * Part C -- a per-row restatement of what include/nsm_hip.h says ``nsm_build_set_table`` / ``nsm_build_str_table`` produce:
   loops over plain ints, nothing from ``tables.py``.
+* Part D -- the strings of Part B over alphabets on either side of a multiple of 64 symbols, for the Levenshtein sweeps
+  (tests/test_gpu_edit_ranges.py): their match masks are laid out by ``pm_stride``, the alphabet and its pad code rounded up
+  to a multiple of 64, and at stride 512 they pass the 64 KB of LDS a kernel gets without asking.  The yardstick there is
+  the two-row programme of tests/support/edit_distance.py, not the oracle.
 
 The grids are ``tp.ProbeGrid`` objects, so ``tp.all_scores`` / ``tp.expectation`` / ``tp.RowRanks`` serve them as they
 serve the threshold probes.  Every generator is deterministic: its own ``random.Random(seed)``.
@@ -256,7 +260,7 @@ def grid(name: str) -> tp.ProbeGrid:
         elif base.startswith("value_raw_str_"):
             g = raw_strings(int(parts[3]), int(parts[4]))
         elif base.startswith("value_levels_str_"):
-            g = levels_strings(int(parts[3]))
+            g = levels_strings(int(parts[3])) if len(parts) == 4 else levels_strings(int(parts[3]), int(parts[4]), *EDIT_LEVELS_ITEMS)
         else:
             raise KeyError(name)
         assert g.name == name, (g.name, name)
@@ -282,6 +286,10 @@ RUNS = (1, 63, 64, 65, 127, 128, 129, 254, 255, 256, 257, 300, 511, 512)
 BLOCKS = ((200, 200), (255, 1), (256, 256), (100, 412))  # the shared bucket passes 255 although neither symbol does
 # (alphabet, a, b, c, d): b shares a's 32-bucket (b = a + 32 = a mod 32); c has its own; d shares a's 16-bucket only
 SYMBOLS = {40: (3, 35, 4, 19), 255: (254, 222, 253, 238)}
+# the alphabets on either side of a multiple of 64 symbols + the pad code (Part D): a = alphabet - 1 is the highest legal
+# code (the pad code is ``alphabet``), b = a - 32 shares a's 32-bucket, c = a - 1, d = a - 16
+SEAM_ALPHABETS = (63, 64, 127, 128, 191, 192)
+SYMBOLS.update({n: (n - 1, n - 33, n - 2, n - 17) for n in SEAM_ALPHABETS})
 STR_LEFT, STR_RIGHT = 32, 72  # two right tiles
 
 
@@ -385,30 +393,33 @@ def _one_of_each_removed(s: Sequence[int]) -> List[int]:
     return out
 
 
-def levels_strings(stride: int) -> tp.ProbeGrid:
+def levels_strings(stride: int, alphabet: int = 40, n_left: int = 24, n_right: int = 70) -> tp.ProbeGrid:
     """24 x 70 items of 1 .. 3 levels, every level a string of the pool of ``stride`` (alphabet 40).  A third of the right
     items are left items, some with one level exchanged.  Twelve left items of depth 3 carry a string with a saturated
     bucket as their step-1 level; each has two right partners that differ from it in that level alone, by one unit per
-    symbol -- near-copies (score about 0.87) whose step-1 histograms are far apart once a count wraps."""
-    rng = random.Random(3500 + stride)
-    pool = [s for s in string_pool(stride, 40).values() if s]  # (an empty level string is fine, but scores 0 everywhere)
+    symbol -- near-copies (score about 0.87) whose step-1 histograms are far apart once a count wraps.  ``alphabet``,
+    ``n_left``, ``n_right``: the same over another alphabet's symbols and with fewer items (half as many saturated ones as
+    left items); the grid's name then ends in the alphabet."""
+    rng = random.Random(3500 + stride + (0 if alphabet == 40 else alphabet))
+    pool = [s for s in string_pool(stride, alphabet).values() if s]  # (an empty level string is fine, but scores 0 everywhere)
     pool_e = pool + [[]]
     item = lambda: [list(rng.choice(pool_e if rng.random() < 0.1 else pool)) for _ in range(rng.randint(1, 3))]
-    left = [item() for _ in range(24)]
-    right = [item() for _ in range(70)]
-    for k in range(0, 70, 3):
-        src = [list(lv) for lv in left[rng.randrange(24)]]
+    left = [item() for _ in range(n_left)]
+    right = [item() for _ in range(n_right)]
+    for k in range(0, n_right, 3):
+        src = [list(lv) for lv in left[rng.randrange(n_left)]]
         if k % 2:
             src[rng.randrange(len(src))] = list(rng.choice(pool))
         right[k] = src
     full = sorted((s for s in pool if saturated(s)), key=lambda s: (max(bucket_counts(s)) % 256, len(s)))
-    for k in range(12):
+    for k in range(n_left // 2):
         x = full[k % len(full)]
         y = _one_of_each_removed(x)
         left[2 * k] = [list(rng.choice(pool)), list(x), list(rng.choice(pool))]
         right[5 * k + 1] = [list(rng.choice(pool)), list(y), list(left[2 * k][2])]
         right[5 * k + 2] = [list(y), list(y), list(left[2 * k][2])]
-    return tp.ProbeGrid(f"value_levels_str_{stride}", "indel", False, left, right, size=stride)
+    name = f"value_levels_str_{stride}" + ("" if alphabet == 40 else f"_{alphabet}")
+    return tp.ProbeGrid(name, "indel", False, left, right, size=stride)
 
 
 def levels_wrap_witnesses(g: tp.ProbeGrid, all_hits: Sequence[tuple]) -> List[Tuple[int, int, float]]:
@@ -433,9 +444,128 @@ RAW_STRINGS = ["value_raw_str_64_40", "value_raw_str_128_40", "value_raw_str_256
 RAW_SATURATED = ["value_raw_sat_256_40", "value_raw_sat_512_40"]
 LEVELS_STRINGS = ["value_levels_str_256", "value_levels_str_512"]
 
+# =========================================================================================================== Part D
+# The Levenshtein sweeps (csrc/edit_raw.hip, edit_levels.hip) keep one match mask per symbol in LDS: ``pm_stride`` symbols,
+# the alphabet and its pad code rounded up to a multiple of 64.  The RAW sweep holds the masks of ``TOP_G`` left rows at
+# once, 8 bytes per symbol and 64 code units of the stride: from 64 KB on the launcher has to raise the kernel's limit.
+TOP_G = 8  # csrc: kTopG, the left rows of one block of the RAW per-item sweeps
+EDIT_CUT = (19, 40)  # rows of the grids at strides 256 and 512: three groups of TOP_G with a ragged last one
+EDIT_LEVELS_ITEMS = (12, 40)
+EDIT_LENGTH_SEAMS = (0, 1, 255, 256, 257, 511, 512)
+
+
+def pm_stride(alphabet: int) -> int:
+    return ((alphabet + 1) + 63) // 64 * 64
+
+
+def edit_lds_bytes(stride: int, alphabet: int) -> int:
+    """Dynamic LDS of the RAW sweep: TOP_G rows x pm_stride symbols x (stride / 64) words of 8 bytes."""
+    return TOP_G * pm_stride(alphabet) * (stride // 64) * 8
+
+
+def _spread(rows: Sequence, limit: int, wanted_lengths: Sequence[int]) -> List:
+    """At most ``limit`` of ``rows``: the first row of every wanted length, then the others evenly spread, input order."""
+    first = []
+    for n in wanted_lengths:
+        hit = [k for k, r in enumerate(rows) if len(r) == n and k not in first]
+        first += hit[:1]
+    rest = [k for k in range(len(rows)) if k not in first]
+    need = max(0, min(limit, len(rows)) - len(first))
+    picked = first + [rest[(q * len(rest)) // need] for q in range(need)]
+    return [rows[k] for k in sorted(picked)]
+
+
+def edit_raw_strings(stride: int, alphabet: int) -> tp.ProbeGrid:
+    """``raw_strings`` for the Levenshtein sweeps.  Strides 64 and 128: the grid as it is (32 x 72).  Strides 256 and 512: at
+    most 19 x 40 of its rows (the DP yardstick is quadratic in the length) -- on both sides the empty string, the lengths
+    1, 255, 256, 257, 511, 512 and the runs of stride / 2 and stride units, the other rows evenly spread."""
+    g = raw_strings(stride, alphabet)
+    left, right = g.left, g.right
+    if stride >= 256:
+        wanted = [n for n in EDIT_LENGTH_SEAMS + (stride // 2, stride) if n <= stride]
+        left, right = _spread(left, EDIT_CUT[0], wanted), _spread(right, EDIT_CUT[1], wanted)
+    return tp.ProbeGrid(f"value_edit_str_{stride}_{alphabet}", "indel", True, left, right, size=stride)
+
+
+EDIT_RAW = [f"value_edit_str_64_{a}" for a in SEAM_ALPHABETS] + \
+    ["value_edit_str_128_255", "value_edit_str_256_255", "value_edit_str_512_128", "value_edit_str_512_255"]
+EDIT_RAW_W8 = EDIT_RAW[-2:]  # the two whose match masks need more than 64 KB
+EDIT_LEVELS = ["value_levels_str_256_255", "value_levels_str_512_255"]
+EDIT_METRICS = ("edit", "edit_within")
+
+# query x prune x metric -> the instantiation of edit_top_k_kernel<W, PRUNE, HIST, GROUPED, Sink> that csrc/edit_raw.hip
+# launches for it (W = stride / 64).  The threshold grid is the floor grid without floors; ``best`` is a profile and a floor
+# grid.  The histogram filter runs under NSM_FLAG_PRUNE and NSM_METRIC_EDIT alone (``edit_hist``).
+EDIT_SINKS = {"top_k": "TopLists<false>", "top_k_grouped": "TopLists<true>", "profile": "ScoreTally", "floor_grid": "FloorGate"}
+
+
+def edit_instantiation(query: str, prune: bool, metric: str, words: int = 8) -> Tuple[int, bool, bool, str]:
+    return words, prune, prune and metric == "edit", EDIT_SINKS[query]
+
+
+EDIT_LAUNCHES = {(q, prune, m): edit_instantiation(q, prune, m) for q in EDIT_SINKS for prune in (True, False) for m in EDIT_METRICS}
+# test of tests/test_gpu_edit_ranges.py -> the sinks it runs, each pruned and unpruned under either metric
+EDIT_QUERIES = {"threshold_grid": ("floor_grid",), "top_k": ("top_k", "top_k_grouped"), "profile_and_best": ("profile", "floor_grid"),
+                "floor_grid": ("floor_grid",)}
+
+_EDIT_DW: Dict[str, dict] = {}
+_EDIT_ALL: Dict[tuple, list] = {}
+
+
+def edit_grid(name: str) -> tp.ProbeGrid:
+    if name not in _BUILT:
+        parts = name.split("_")
+        _BUILT[name] = edit_raw_strings(int(parts[3]), int(parts[4])) if name.startswith("value_edit_str_") else grid(name)
+    return _BUILT[name]
+
+
+def edit_categories(g: tp.ProbeGrid, mode: int):
+    """(left masks, right masks) of a levels grid for the category modes of Part D; none at mode 0."""
+    from support import edit_distance as ed
+
+    return ed.levels_categories(len(g.left), len(g.right)) if mode else (None, None)
+
+
+def edit_records(g: tp.ProbeGrid, metric: str, mode: int = 0) -> list:
+    """Every pair's record under a Levenshtein metric from the definitions (tests/support/edit_distance.py): d and w of
+    two strings from ONE pass of the two-row programme (``ed.distance_table``, cached per grid: both metrics share it), RAW
+    ``ed.score`` of them, levels ``compare_terms`` with that as score_func over the pairs the category masks admit.
+    Canonical order; cached; never modified."""
+    from oracle.compare import compare_terms
+    from support import edit_distance as ed
+
+    if (g.name, metric, mode) not in _EDIT_ALL:
+        known = _EDIT_DW.setdefault(g.name, {})
+        if not known:
+            flat = lambda side: sorted({tuple(s) for it in side for s in ([it] if g.raw else it)})
+            ed.distance_table(flat(g.left), flat(g.right), known)
+        f = lambda a, b: ed.plain_score(metric, len(a), len(b), *known[tuple(a), tuple(b)])
+        cl, cr = edit_categories(g, mode)
+        hits = [((f(x, y) if g.raw else compare_terms(x, y, f)), i, j) for i, x in enumerate(g.left) for j, y in enumerate(g.right)
+                if not mode or ed.category_match(int(cl[i]), int(cr[j]), mode)]
+        _EDIT_ALL[g.name, metric, mode] = sorted(hits, key=lambda h: (-h[0], h[1], h[2]))
+    return _EDIT_ALL[g.name, metric, mode]
+
+
+def edit_thresholds(all_hits: Sequence[tuple]) -> Tuple[float, ...]:
+    """The thresholds of a Part D grid, each with a pair exactly on it: 0.5 and 1.0 (a run of m units against one of 2 m:
+    0.5 under "edit", 1.0 and 0.5 in the two orientations under "edit_within") and the distinct score two thirds of the way
+    up.  A levels grid (no score reaches 1.0) has its distinct scores one third and two thirds of the way up."""
+    distinct = sorted({h[0] for h in all_hits})
+    mid = distinct[2 * len(distinct) // 3]
+    return (0.5, mid, 1.0) if distinct[-1] == 1.0 else (distinct[len(distinct) // 3], mid)
+
+
+def around(bases: Sequence[float]) -> List[float]:
+    """Every base with its two neighbouring doubles."""
+    import math
+
+    return sorted({t for b in bases for t in (math.nextafter(b, -1.0), b, math.nextafter(b, 2.0))})
+
 
 def alphabet_of(g: tp.ProbeGrid) -> int:
-    return int(g.name.rsplit("_", 1)[1]) if g.raw else 40
+    parts = g.name.partition("-")[0].split("_")
+    return int(parts[4]) if len(parts) > 4 else 40
 
 
 def codes_of(rows: Sequence[Sequence[int]], stride: int, fill: int = 0):

@@ -394,3 +394,46 @@ def test_gpu_levels_inputs_hold_every_threshold(metric, wide):
         scores = [h[0] for h in kept]
         for t in ed.levels_thresholds(kept):
             assert t in scores and min(scores) < t < max(scores), (mode, t)
+
+
+# ------------------------------------------------------------------------------------------------------ explicit floors
+def test_floor_corpus_records_are_the_definitions():
+    """``floor_corpus_records`` (d and w of a pair from one stacked pass) gives the records of ``raw_hits`` / ``levels_hits``,
+    the yardsticks of the GPU file."""
+    for metric in ed.METRICS:
+        assert ed.floor_corpus_records("raw_64", metric) == ed.raw_hits(metric, *ed.floor_corpus("raw_64"))
+        assert ed.floor_corpus_records("levels", metric) == ed.levels_hits(metric, *ed.floor_corpus("levels"))
+    assert ed.by_caller_id([0.5, 0.25])[[2, 5]].tolist() == [0.5, 0.25] and len(ed.by_caller_id([0.5, 0.25])) == 6
+
+
+@pytest.mark.parametrize("kind", ed.FLOOR_CORPORA)
+@pytest.mark.parametrize("metric", ed.METRICS)
+def test_gpu_floor_inputs_sit_on_scores(metric, kind):
+    """The explicit floors of tests/test_gpu_edit_distance.py: every floor of an "on" case has a pair of its item exactly
+    on it, which the next double up excludes and the next double down keeps; left item ``ABOVE_ALL`` has no record in any
+    case; the second-best floors differ from the best ones; the three shifts give different record lists."""
+    left, right = ed.floor_corpus(kind)
+    records = ed.floor_corpus_records(kind, metric)
+    n, m = len(left), len(right)
+    assert len(records) == n * m
+    kept = {}
+    for shift_name, shift in ed.FLOOR_SHIFTS.items():
+        for label, lf, rf in ed.floor_cases(records, n, m, shift):
+            want = kept[shift_name, label] = ed.floors_plain(records, lf, rf)
+            nothing = shift > 0 and label.startswith("rank 0")  # (every floor one double above its item's best score)
+            assert len(want) < len(records) and (len(want) == 0) == nothing, (shift_name, label)
+            assert lf is None or not any(r[1] == ed.ABOVE_ALL for r in want)
+    for label, lf, rf in ed.floor_cases(records, n, m, 0):
+        for pos, floors in ((1, lf), (2, rf)):
+            for item, floor in enumerate(floors or []):
+                if pos == 1 and item == ed.ABOVE_ALL:
+                    assert floor > max(r[0] for r in records if r[1] == item)
+                    continue
+                on = [r for r in records if r[pos] == item and r[0] == floor]
+                assert on and all(r[0] < math.nextafter(floor, 2.0) for r in on), (label, pos, item)
+        # a record on the floors of both its items is in the "on" and "below" lists and not in the "above" list
+        edge = [r for r in kept["on", label] if (lf is not None and r[0] == lf[r[1]]) or (rf is not None and r[0] == rf[r[2]])]
+        assert edge and set(edge) <= set(kept["below", label]) and not set(edge) & set(kept["above", label])
+        assert len(kept["above", label]) < len(kept["on", label]) <= len(kept["below", label])
+    best, second = ed.ranked_floors(records, n, m, 0, 0), ed.ranked_floors(records, n, m, 1, 0)
+    assert sum(a > b for a, b in zip(best[0], second[0])) > n // 2 and sum(a > b for a, b in zip(best[1], second[1])) > m // 2

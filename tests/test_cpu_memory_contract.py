@@ -1,9 +1,10 @@
 """The guard-band arena of tests/support/arena.py on ``device="cpu"``, and the premises of
 tests/test_gpu_memory_contract.py from the oracle alone (no GPU).
 
-The GPU file only pins the extents of include/nsm_hip.h if (1) the arena reports a stray byte wherever it lands outside a
+The GPU file only pins the extents of include/nsm_hip*.h if (1) the arena reports a stray byte wherever it lands outside a
 region, and says where, and (2) its cases are worth running: more oracle hits than every "too small" capacity, caller ids
-with gaps, top-k rows of every fill.
+with gaps, top-k rows of every fill -- for the entries of nsm_hip.h by the oracle, for the nsm_set_* / nsm_edit_* entries
+under every measure and metric by the definitions.
 """
 import numpy as np
 import pytest
@@ -214,6 +215,118 @@ def test_pair_lists_hold_duplicates_and_ids_without_a_row(entry):
             assert any(not (0 <= i < len(g.left) and 0 <= j < len(g.right)) for i, j in pairs)  # ids outside the maps
             assert any(i in mc.UNMAPPED_LEFT or j in mc.UNMAPPED_RIGHT for i, j in pairs)       # ids whose row is -1
             assert sum(s >= 0 for s in scores) > n_pairs // 2 and any(s == -1.0 for s in scores)
+
+
+# ------------------------------------------------------------------------- premises of the additive headers' cases
+def test_codes_are_the_headers():
+    from napkon_string_matching_amd import _lib
+
+    assert {v: mc.CODE[v] for v in mc.MEASURES} == {v: c for v, c in _lib.MEASURES.items() if c} and len(mc.MEASURES) == 3
+    assert {v: mc.CODE[v] for v in mc.METRICS} == {v: c for v, c in _lib.METRICS.items() if c} and len(mc.METRICS) == 2
+    every = mc.additive(list(mc.FLOOR_GRIDS) + list(mc.TOP_K_GRIDS) + list(mc.PROFILE_GRIDS) + list(mc.PAIRS_GRIDS))
+    assert {e for e, _, _ in every} == set(_lib.MEASURE_EXPORTS) | set(_lib.EDIT_EXPORTS) and len({e for e, _, _ in every}) == 18
+    assert all(e.startswith("nsm_set_") == (v in mc.MEASURES) for e, _, v in every)
+
+
+def test_both_distances_in_one_pass_are_the_two_row_programme():
+    import random
+
+    from support import edit_distance as ed
+
+    rng = random.Random(7)
+    for alphabet in ("ab", "abcdefgh"):
+        for _ in range(12):
+            a = "".join(rng.choice(alphabet) for _ in range(rng.choice((0, 1, 5, 9, 17))))
+            rights = ["".join(rng.choice(alphabet) for _ in range(rng.randint(0, 21))) for _ in range(9)] + ["", a, a + a]
+            d, w = ed.both_many(a, rights)
+            assert d == [ed.distance(a, b) for b in rights] and w == [ed.within(a, b) for b in rights], (a, rights)
+    assert ed.both_many([1, 2, 3], [(1, 2, 3, 4), (), (9, 1, 2, 3, 9)]) == ([1, 3, 2], [0, 3, 0])  # (code units as ints)
+    # the yardstick of a levels grid is compare_terms with that definition: two pairs by hand from the two-row programme
+    g = tp.grid("levels_indel_one_word-cat2_lanes")
+    by_pair = {(i, j): s for s, i, j in mc.edit_scores(g, "edit_within")}
+    from oracle.compare import compare_terms
+
+    for (i, j) in list(by_pair)[:: max(1, len(by_pair) // 5)][:5]:
+        f = lambda a, b: ed.score("edit_within", len(a), len(b), ed.within(tp.text(a), tp.text(b)))
+        assert by_pair[i, j] == compare_terms(g.left[i], g.right[j], f)
+
+
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.FLOOR_GRIDS))
+def test_additive_floor_grids_overflow_every_small_capacity(entry, sibling, variant):
+    name = mc.FLOOR_GRIDS[sibling]
+    g = mc.view(name, variant)
+    thr, lf, rf, want = mc.floor_case(name, variant)
+    at_thr = tp.expectation(mc.scores(g, variant), thr)
+    assert max(mc.SMALL_CAPACITIES) + 1 < len(want) < len(at_thr) < g.pairs  # more than 65 hits, fewer than all pairs
+    assert len(set(want)) == len(want) and mc.capacities(len(want)) == sorted(set(mc.capacities(len(want))))
+    assert np.isnan(lf).any() and not any(i == mc.caller_id(3) for _, i, _ in want)  # (item 3: a NaN floor admits nothing)
+    assert len(lf) == mc.caller_id(len(g.left) - 1) + 1 and len(rf) == mc.caller_id(len(g.right) - 1) + 1
+    assert g.partition is False and (variant != "smaller" or not g.raw or all(g.right))
+
+
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.TOP_K_GRIDS))
+def test_additive_top_k_cases_have_rows_of_every_fill(entry, sibling, variant):
+    name = mc.grid_name(mc.TOP_K_GRIDS, sibling, variant)
+    g = mc.view(name, variant)
+    case = mc.top_k_case(name, variant)
+    assert case is not None, "no probe threshold leaves empty, short and long rows"
+    thr, allowed, banned = case
+    count = mc.row_counts(allowed, len(g.left))
+    assert 0 in count and any(0 < c < 3 for c in count) and any(c > 3 for c in count)
+    assert max(mc.TOP_K) > len(g.right) and (banned is not None) == (not g.raw)
+    at_thr = tp.expectation(mc.scores(g, variant), thr)
+    assert len(allowed) < g.pairs and (not banned or len(allowed) < len(at_thr))  # the blacklist removes hits
+    if variant == "smaller" and g.raw:  # why this variant has a grid of its own
+        for other in ("raw_jaccard_16", "raw_jaccard_32"):
+            assert mc.top_k_case(other, variant) is None
+
+
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.PROFILE_GRIDS))
+def test_additive_profile_cases_have_gaps(entry, sibling, variant):
+    name = mc.grid_name(mc.PROFILE_GRIDS, sibling, variant)
+    g = mc.view(name, variant)
+    ladder, pairs, left, right = mc.profile_case(name, variant)
+    assert len(ladder) == 3 and ladder == sorted(ladder) and g.pairs > pairs[0] > pairs[1] > pairs[2] > 0
+    for ids, n in ((left, len(g.left)), (right, len(g.right))):
+        assert sorted(ids) == [3 * k + 2 for k in range(n)] and any(v > 0 for v in ids.values())
+    assert any(v == -1.0 for v in left.values()) or any(v == -1.0 for v in right.values())  # items without a hit
+    assert pairs[0] == len(tp.expectation(mc.scores(g, variant), ladder[0]))
+
+
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.PAIRS_GRIDS))
+def test_additive_pair_lists_score_most_pairs(entry, sibling, variant):
+    g = tp.grid(mc.PAIRS_GRIDS[sibling])
+    for n_pairs in mc.PAIR_COUNTS[1:]:
+        pairs = mc.pair_list(g, n_pairs)
+        scores = mc.pair_scores(g, pairs, variant)
+        assert len(scores) == n_pairs and sum(s >= 0 for s in scores) > n_pairs // 2 and any(s == -1.0 for s in scores)
+        assert all(s == -1.0 for s, (i, j) in zip(scores, pairs) if i in mc.UNMAPPED_LEFT or not 0 <= j < len(g.right))
+    if variant == "smaller" and g.raw:  # an empty right row: the measure divides by zero, the entry writes -1.0
+        empty = [j for j, row in enumerate(g.right) if not row and j not in mc.UNMAPPED_RIGHT]
+        listed = {p for n in mc.PAIR_COUNTS for p in mc.pair_list(g, n)}
+        assert any(j in empty and 0 <= i < len(g.left) and i not in mc.UNMAPPED_LEFT for i, j in listed)
+
+
+def test_support_case_is_small_and_peels():
+    from napkon_string_matching_amd import grid
+    from support import edge_support as es
+
+    lists, nodes, min_score = mc.support_case()
+    sizes = [len(hits) for hits, _, _ in lists]
+    assert 0 in sizes and len(lists) == 5 and 150 < sum(sizes) <= 320
+    counting, one = grid.truss_of_hits(lists, nodes, 0, min_score)
+    peeled, rounds = grid.truss_of_hits(lists, nodes, 1, min_score)
+    assert one == 1 and rounds >= 2
+    flat = np.concatenate(peeled)
+    assert (flat == -1).any() and (flat == -2).any() and (flat >= 1).any() and (np.concatenate(counting) == 0).any()
+    records, distinct = es.edge_counts(lists, nodes, min_score)
+    assert distinct < records < sum(sizes)  # duplicates; records that are no edge
+    assert any(np.isnan(hits.score).any() for hits, _, _ in lists)
+    for side in ("i", "j", "negative"):
+        bad = mc.support_case_with_bad_id(lists, nodes, side)
+        hits, lb, rb = bad[-1]
+        out = (hits.i < 0) | (hits.i >= nodes - lb) | (hits.j < 0) | (hits.j >= nodes - rb)
+        assert out.sum() == 1 and hits.score[out][0] < min_score and mc.support_records(hits).shape == (len(hits), 2)
 
 
 def test_sort_records_are_distinct_and_tie_on_scores():

@@ -272,3 +272,98 @@ def test_models_on_rows_worked_by_hand():
     s = vr.str_table_model([[1] * 300 + [33] * 200 + [9] * 12, [2, 2, 7, 7] + [0] * 508], [500, 2], 40, True)
     assert s["len"].tolist() == [500, 2] and s["hist"][0, 1] == 255 and s["hist16"][0, 1] == 255 and s["hist"][1, 2] == 2
     assert s["codes"][1].tolist() == [2, 2] + [40] * 510 and s["len_start"][[0, 12, 13, 510, 511, 513]].tolist() == [0, 0, 1, 1, 2, 2]
+
+
+# ----------------------------------------------------------------------------------------------------------- Part D
+def test_edit_seam_alphabets_and_lds_arithmetic():
+    """``pm_stride`` at the seam alphabets, and the dynamic LDS of the RAW Levenshtein sweep restated from ``kTopG``,
+    ``pm_stride`` and the words of a row: exactly 64 KB at stride 256 over 255 symbols (the launcher asks only ABOVE it),
+    96 KB and 128 KB on the two stride-512 grids."""
+    import re
+    from pathlib import Path
+
+    assert [vr.pm_stride(a) for a in (40, 63, 64, 127, 128, 191, 192, 255)] == [64, 64, 128, 128, 192, 192, 256, 256]
+    for alphabet in vr.SEAM_ALPHABETS + (255,):
+        a, b, c, d = vr.SYMBOLS[alphabet]
+        assert (a, b, c, d) == (alphabet - 1, alphabet - 33, alphabet - 2, alphabet - 17) and min(a, b, c, d) >= 0
+        assert a & 31 == b & 31 and a & 31 != c & 31 and a & 15 == d & 15 and a & 31 != d & 31
+        assert alphabet < vr.pm_stride(alphabet)  # the pad code has a mask of its own
+        assert (a > 63) == (alphabet > 64)  # from 65 symbols on the highest code lies past the first 64 masks
+    # A tripwire, no proof: the two literal texts below are how the source spells kTopG and pm_stride today.  A reformat of
+    # the source trips it without harm (update the text here); it exists so that a CHANGE of either makes someone look at
+    # vr.TOP_G / vr.pm_stride, which restate them.
+    csrc = Path(__file__).resolve().parents[1] / "napkon-string-matching_amd" / "csrc"
+    assert int(re.search(r"kTopG\s*=\s*(\d+)", (csrc / "top_k_raw_kernels.hpp").read_text()).group(1)) == vr.TOP_G
+    assert "(left->alphabet + 1) + 63) / 64 * 64" in (csrc / "edit_raw.hip").read_text()
+    lds = {name: vr.edit_lds_bytes(vr.edit_grid(name).size, vr.alphabet_of(vr.edit_grid(name))) for name in vr.EDIT_RAW}
+    assert lds["value_edit_str_256_255"] == 64 * 1024 and lds["value_edit_str_512_128"] == 96 * 1024
+    assert lds["value_edit_str_512_255"] == 128 * 1024 and [n for n, v in lds.items() if v > 64 * 1024] == vr.EDIT_RAW_W8
+    assert sorted({vr.pm_stride(vr.alphabet_of(vr.edit_grid(n))) for n in vr.EDIT_RAW}) == [64, 128, 192, 256]
+
+
+def test_edit_launch_table_has_twelve_instantiations():
+    """query x prune x metric -> instantiation: sixteen launches, twelve distinct kernels (an unpruned sweep is the same
+    under both metrics); the tests of tests/test_gpu_edit_ranges.py run every one, on every grid."""
+    assert len(vr.EDIT_LAUNCHES) == 16 and len(set(vr.EDIT_LAUNCHES.values())) == 12
+    assert {inst[3] for inst in vr.EDIT_LAUNCHES.values()} == {"TopLists<false>", "TopLists<true>", "ScoreTally", "FloorGate"}
+    per_sink = {}
+    for (query, prune, metric), (words, pruned, hist, sink) in vr.EDIT_LAUNCHES.items():
+        assert words == 8 and pruned == prune and hist == (prune and metric == "edit")
+        per_sink.setdefault(sink, set()).add((pruned, hist))
+    assert all(v == {(False, False), (True, True), (True, False)} for v in per_sink.values())
+    ran = {(q, prune, m) for queries in vr.EDIT_QUERIES.values() for q in queries for prune in (True, False) for m in vr.EDIT_METRICS}
+    assert ran == set(vr.EDIT_LAUNCHES)
+
+
+@pytest.mark.parametrize("name", vr.EDIT_RAW)
+def test_edit_raw_grids_hold_their_seams(name):
+    from support import edit_distance as ed
+
+    g = vr.edit_grid(name)
+    alphabet = vr.alphabet_of(g)
+    a, b, c, _ = vr.SYMBOLS[alphabet]
+    units = {u for side in (g.left, g.right) for s in side for u in s}
+    assert {a, b, c} <= units and max(units) == a == alphabet - 1
+    assert (len(g.left), len(g.right)) == ((32, 72) if g.size <= 128 else vr.EDIT_CUT)
+    assert g.size <= 128 or (len(g.left) % vr.TOP_G != 0 and -(-len(g.left) // vr.TOP_G) == 3)  # three groups, the last ragged
+    for side in (g.left, g.right):
+        lengths = {len(s) for s in side}
+        assert lengths >= {n for n in vr.EDIT_LENGTH_SEAMS if n <= g.size and (g.size >= 256 or n <= 1)}, (name, sorted(lengths))
+    runs = lambda side: {len(s) for s in side if s and set(s) == {a}}
+    doubles = [(m, 2 * m) for m in runs(g.left) if 2 * m in runs(g.left) and m in runs(g.right) and 2 * m in runs(g.right)]
+    assert doubles, "no run of m units beside one of 2 m units on both sides"
+    for metric in vr.EDIT_METRICS:
+        full = vr.edit_records(g, metric)
+        by_pair = {(i, j): s for s, i, j in full}
+        assert len(full) == g.pairs
+        bases = vr.edit_thresholds(full)
+        assert bases[0] == 0.5 and bases[2] == 1.0
+        for t in bases:  # a pair exactly on it, pairs below it
+            assert any(h[0] == t for h in full) and full[-1][0] < t
+        m, m2 = doubles[0]
+        index = lambda side, n: next(k for k, s in enumerate(side) if s == [a] * n)
+        short_long, long_short = by_pair[index(g.left, m), index(g.right, m2)], by_pair[index(g.left, m2), index(g.right, m)]
+        assert (short_long, long_short) == ((0.5, 0.5) if metric == "edit" else (1.0, 0.5))
+        # the stacked pass against the two-row programme on a few short pairs of the grid
+        for i, j in list(by_pair)[:: max(1, len(by_pair) // 7)]:
+            x, y = g.left[i], g.right[j]
+            if len(x) * len(y) <= 64 * 64:
+                dist = (ed.distance if metric == "edit" else ed.within)(tp.text(x), tp.text(y))
+                assert by_pair[i, j] == ed.score(metric, len(x), len(y), dist)
+
+
+@pytest.mark.parametrize("name", vr.EDIT_LEVELS)
+def test_edit_levels_grids_hold_the_highest_symbol(name):
+    g = vr.edit_grid(name)
+    assert vr.alphabet_of(g) == 255 and (len(g.left), len(g.right)) == vr.EDIT_LEVELS_ITEMS
+    assert {len(it) for it in g.left} == {1, 2, 3} == {len(it) for it in g.right}
+    assert any(lv and set(lv) == {254} for it in g.right for lv in it)  # a level of nothing but the code alphabet - 1
+    assert g.size // 2 < max(len(lv) for it in g.left + g.right for lv in it) <= g.size
+    for metric in vr.EDIT_METRICS:
+        plain, both_empty = vr.edit_records(g, metric, 0), vr.edit_records(g, metric, 2)
+        assert len(plain) == g.pairs and 0 < len(both_empty) < g.pairs and set(both_empty) <= set(plain)
+        cl, cr = vr.edit_categories(g, 2)
+        assert any(int(cl[i]) == 0 == int(cr[j]) for _, i, j in both_empty)  # a pair of two items without a category
+        for full in (plain, both_empty):
+            for t in vr.edit_thresholds(full):
+                assert any(h[0] == t for h in full) and full[-1][0] < t < full[0][0]

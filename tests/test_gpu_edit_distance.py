@@ -372,7 +372,51 @@ def test_levels_queries(dev, metric, wide, mode, monkeypatch):
         assert got.as_tuples() == want and len(want) > 0
 
 
-# ================================================================================================= 5: the public surface
+# ================================================================================================== 5: explicit floors
+def _with_caller_ids(table):
+    """The table reporting caller ids with gaps: row r reports ``ed.caller_id`` of what it reported."""
+    import copy
+
+    out = copy.copy(table)
+    out.orig = table.orig * 3 + 2
+    return out
+
+
+@pytest.mark.parametrize("shift", ed.FLOOR_SHIFTS)
+@pytest.mark.parametrize("kind", ed.FLOOR_CORPORA)
+@pytest.mark.parametrize("metric", ed.METRICS)
+def test_explicit_floors(dev, metric, kind, shift, monkeypatch):
+    """``nsm_edit_raw_floor_grid`` / ``nsm_edit_levels_floor_grid`` with ``left_floor`` / ``right_floor`` arrays of the
+    caller's own (``best`` only ever derives them from a profile): indexed by caller ids with gaps, on the left side only,
+    on the right side only and on both, sitting on every item's best and second-best score ("on"), one double below and
+    one above; one left item's floor lies above all of its scores.  Expected: ``grid.filter_by_floors`` of every pair's
+    record.  tests/test_cpu_edit_distance.py checks that every "on" floor has a pair exactly on it."""
+    from napkon_string_matching_amd import grid
+
+    if kind.startswith("raw_"):
+        left, right, lt, rt, full = _raw_case(dev, metric, int(kind[4:]))
+        tabs = (_with_caller_ids(lt), _with_caller_ids(rt))
+        run = lambda lf, rf, prune: grid.indel_raw_floor_grid(*tabs, 0.0, lf, rf, prune=prune, metric=metric)
+    else:
+        wide = kind == "levels_wide"
+        left, right, (li, ls, ri, rs), _ = _levels_case(dev, wide, 0)
+        full = _levels_full(metric, wide, monkeypatch)
+        tabs = (_with_caller_ids(li), ls, _with_caller_ids(ri), rs)
+        run = lambda lf, rf, prune: grid.indel_levels_floor_grid(*tabs, 0.0, lf, rf, prune=prune, metric=metric)
+    assert len(full) == len(left) * len(right)
+    hits = _hits([(s, ed.caller_id(i), ed.caller_id(j)) for s, i, j in full])
+    for label, lf, rf in ed.floor_cases(full, len(left), len(right), ed.FLOOR_SHIFTS[shift]):
+        lf, rf = (None if f is None else ed.by_caller_id(f) for f in (lf, rf))
+        want = grid.filter_by_floors(hits, lf, rf).as_tuples()
+        assert not any(i == ed.caller_id(ed.ABOVE_ALL) for _, i, _ in want) or lf is None
+        for prune in (True, False):
+            got = run(lf, rf, prune).as_tuples()
+            assert got == want, f"{metric} {kind} floors {shift} their scores, {label}, prune={prune}: " \
+                                f"{len(got)} records, expected {len(want)}; only in got {sorted(set(got) - set(want))[:4]}, " \
+                                f"lost {sorted(set(want) - set(got))[:4]}"
+
+
+# ================================================================================================= 6: the public surface
 WORDS = ["gewicht", "groesse", "alter", "patient", "aufnahme", "blutdruck", "systolisch", "diastolisch", "kg", "cm"]
 COLUMNS = ["Identifier", "Variable", "Sheet", "Category", "Term", "Tokens", "Parameter"]
 

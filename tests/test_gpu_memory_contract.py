@@ -1,4 +1,8 @@
-"""The memory contract of include/nsm_hip.h, entry by entry, inside a guard-band arena (tests/support/arena.py).
+"""The memory contract of every header include/nsm_hip*.h, entry by entry, inside a guard-band arena
+(tests/support/arena.py): the 29 entries of nsm_hip.h against the oracle; the nine nsm_set_* and the nine nsm_edit_* entries
+of the additive headers through the same case runners, under every measure and metric but the forwarding code 0, against the
+plain-Python definitions; nsm_support_hits.  nsm_assign_hits, nsm_group_hits and nsm_span_hits have arena tests of their own
+(the catalogue at the end checks that they still do).
 
 Every other file of the suite compares results with the oracle and gives each buffer a ``torch`` tensor of its own: the
 allocator rounds it up to 512 bytes, places nothing right behind it, and most outputs start as zeros.  A record written one
@@ -26,6 +30,8 @@ import pytest
 
 from support import any_operands as ao
 from support import arena as ar
+from support import edge_support as es
+from support import measure_probes as mp
 from support import memory_cases as mc
 from support import probe_tables
 from support import threshold_probes as tp
@@ -33,7 +39,8 @@ from support import threshold_probes as tp
 
 pytestmark = pytest.mark.gpu
 
-HEADER = Path(__file__).resolve().parent.parent / "include" / "nsm_hip.h"
+HEADERS = sorted((Path(__file__).resolve().parent.parent / "include").glob("nsm_hip*.h"))
+NSM_E_BADARG = 10001  # include/nsm_hip.h
 COVERED = {}  # C entry -> the tests that cover it
 
 
@@ -356,7 +363,7 @@ def _one_row_tables(g, dev):
     if g.kind == "indel" and g.raw:
         return dict(zip(("left", "right"), probe_tables.raw_indel_tables(g, dev)))
     if g.kind == "jaccard" and g.raw:
-        return dict(zip(("left", "right"), probe_tables.raw_jaccard_tables(g, dev)))
+        return dict(zip(("left", "right"), mp.raw_tables(g, dev)))  # (the probe grid's tables, or those of a measure's view of it)
     if g.kind == "indel":
         return dict(zip(LEVELS_PREFIXES, probe_tables.levels_indel_tables(g, dev, False)))
     return dict(zip(("left", "right"), probe_tables.levels_jaccard_tables(g, dev, False)))
@@ -377,11 +384,20 @@ def _mode_of(tabs, g):
 def test_floor_grids(dev, entry):
     """Both floors, indexed by caller ids with gaps (3 k + 2); the floor columns are inputs and stay as they are; ``stats``
     is added to on every other launch and NULL on the rest."""
+    _floor_grid_case(dev, entry, mc.FLOOR_GRIDS[entry])
+
+
+def _code(variant):
+    """The argument an entry of an additive header takes behind its last table: the measure or metric."""
+    return () if variant is None else (mc.CODE[variant],)
+
+
+def _floor_grid_case(dev, entry, name, variant=None):
     import torch
 
     lib_module, lib = _lib()
-    g = tp.grid(mc.FLOOR_GRIDS[entry])
-    thr, lf, rf, want = mc.floor_case(g.name)
+    g = mc.view(name, variant)
+    thr, lf, rf, want = mc.floor_case(name, variant)
     tabs = _one_row_tables(g, dev)
     tabs["left"], tabs["right"] = _with_caller_ids(tabs["left"]), _with_caller_ids(tabs["right"])
     prefixes = list(tabs)
@@ -399,7 +415,7 @@ def test_floor_grids(dev, entry):
                 arena.carve(f"stats@{run}", 32)
                 arena.fill(f"stats@{run}", np.array([11, 12, 13, 14], dtype=np.uint64))
                 st = arena.ptr(f"stats@{run}")
-            rc = getattr(lib, entry)(*structs, thr, lfp, rfp, *middle, hits, cap, count, st, stream)
+            rc = getattr(lib, entry)(*structs, *_code(variant), thr, lfp, rfp, *middle, hits, cap, count, st, stream)
             if st:
                 _sync(dev)
                 stats_seen.append(arena.read(f"stats@{run}", np.uint64).tolist())
@@ -407,8 +423,18 @@ def test_floor_grids(dev, entry):
 
         return call
 
-    _check_hit_entry(dev, f"{entry} {g.name}", tabs, prepare, want, extra_bytes=_region_bytes(lf.nbytes, rf.nbytes))
+    what = f"{entry} {g.name}" + (f" {variant}" if variant else "")
+    _check_hit_entry(dev, what, tabs, prepare, want, extra_bytes=_region_bytes(lf.nbytes, rf.nbytes))
     assert stats_seen and all(all(a >= b for a, b in zip(s, (11, 12, 13, 14))) and s[0] >= 11 + len(want) for s in stats_seen)
+
+
+@covers(*{e for e, _, _ in mc.additive(mc.FLOOR_GRIDS)})
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.FLOOR_GRIDS))
+def test_floor_grids_of_the_additive_headers(dev, entry, sibling, variant):
+    """``nsm_set_*_floor_grid`` under Dice, overlap and containment and ``nsm_edit_*_floor_grid`` under both Levenshtein
+    metrics: the sibling's grid, capacities, caller ids and ``stats`` runs, the code behind the last table; the expected
+    records are the definition's (tests/support/set_measures.py, edit_distance.py)."""
+    _floor_grid_case(dev, entry, mc.FLOOR_GRIDS[sibling], variant)
 
 
 # ------------------------------------------------------------------------------------------------- split-path workspace
@@ -498,13 +524,25 @@ def test_top_k(dev, entry):
     """``out`` at exactly ``left->n * min(k, right->n)`` records (the entry clamps k; the host allocates that much) and
     ``stats`` at 32 bytes; rows with no record, with fewer than k and with more; the levels entries with a category
     predicate and a blacklist.  A run with ``stats = NULL`` and one with it give the same records; ``stats`` is added to."""
+    _top_k_case(dev, entry, mc.TOP_K_GRIDS[entry])
+
+
+@covers(*{e for e, _, _ in mc.additive(mc.TOP_K_GRIDS)})
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.TOP_K_GRIDS))
+def test_top_k_of_the_additive_headers(dev, entry, sibling, variant):
+    """The six ``nsm_set_*`` / ``nsm_edit_*`` top-k entries, plain, grouped (the code stands before ``right_group``) and
+    levels with a category predicate and a blacklist, under every code but 0, against the definitions."""
+    _top_k_case(dev, entry, mc.grid_name(mc.TOP_K_GRIDS, sibling, variant), variant)
+
+
+def _top_k_case(dev, entry, name, variant=None):
     import torch
 
     from napkon_string_matching_amd import grid
 
     lib_module, lib = _lib()
-    g = tp.grid(mc.TOP_K_GRIDS[entry])
-    thr, allowed, banned = mc.top_k_case(g.name)
+    g = mc.view(name, variant)
+    thr, allowed, banned = mc.top_k_case(name, variant)
     tabs = _one_row_tables(g, dev)
     prefixes = list(tabs)
     left, right = _item_tables(tabs)
@@ -513,7 +551,8 @@ def test_top_k(dev, entry):
     ranks = tp.RowRanks(allowed, None if groups is None else groups.tolist())
     bs, bj = grid.banned_csr(banned, len(g.left), dev)
     k_effs = [min(k, right.n) for k in mc.TOP_K]
-    arena = _arena(entry, dev, ar.table_bytes(*tabs.values()) + _region_bytes(4 * len(g.right), 4 * (len(g.left) + 1), 8 * len(allowed)) +
+    arena = _arena(entry + (f" {variant}" if variant else ""), dev,
+                   ar.table_bytes(*tabs.values()) + _region_bytes(4 * len(g.right), 4 * (len(g.left) + 1), 8 * len(allowed)) +
                    sum(2 * _region_bytes(left.n * k * 16, 8, 32) for k in k_effs))
     homed = {p: ar.rehome(t, arena, p) for p, t in tabs.items()}
     structs = [homed[p].struct() for p in prefixes]
@@ -535,8 +574,8 @@ def test_top_k(dev, entry):
                 arena.fill(f"stats@{tag}", np.array([11, 12, 13, 14], dtype=np.uint64))
                 st = arena.ptr(f"stats@{tag}")
             middle = (thr, k, lib_module.FLAG_PRUNE) if g.raw else (thr, k, _mode_of(tabs, g), lib_module.FLAG_PRUNE, *tail)
-            _ok(getattr(lib, entry)(*structs, *front, *middle, arena.ptr(f"out@{tag}"), arena.ptr(f"count@{tag}"), st, _stream(dev)),
-                f"{entry} k={k}")
+            _ok(getattr(lib, entry)(*structs, *_code(variant), *front, *middle, arena.ptr(f"out@{tag}"), arena.ptr(f"count@{tag}"), st,
+                                    _stream(dev)), f"{entry} {variant or ''} k={k}")
             _sync(dev)
             arena.check(unchanged=inputs)
             n = int(arena.read(f"count@{tag}", np.uint64)[0])
@@ -558,9 +597,22 @@ def test_profiles(dev, entry, empty):
     """Caller ids with gaps (3 k + 2); ``left_best`` / ``right_best`` at largest id + 1 entries and ``pairs`` at T, all
     random bytes on entry: "the call initialises its outputs itself ... other entries stay as they are".  ``empty``: that
     side's table has no rows (its columns are still there) -- pairs are 0, the other side's entries -1.0."""
+    _profile_case(dev, entry, mc.PROFILE_GRIDS[entry], empty)
+
+
+@covers(*{e for e, _, _ in mc.additive(mc.PROFILE_GRIDS)})
+@pytest.mark.parametrize("empty", [None, "left", "right"])
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.PROFILE_GRIDS))
+def test_profiles_of_the_additive_headers(dev, entry, sibling, variant, empty):
+    """``nsm_set_*_profile`` and ``nsm_edit_*_profile`` under every code but 0: the sibling's conditions, the definitions'
+    pair counts and best scores."""
+    _profile_case(dev, entry, mc.grid_name(mc.PROFILE_GRIDS, sibling, variant), empty, variant)
+
+
+def _profile_case(dev, entry, name, empty, variant=None):
     lib_module, lib = _lib()
-    g = tp.grid(mc.PROFILE_GRIDS[entry])
-    ladder, pairs, best_l, best_r = mc.profile_case(g.name)
+    g = mc.view(name, variant)
+    ladder, pairs, best_l, best_r = mc.profile_case(name, variant)
     tabs = _one_row_tables(g, dev)
     tabs["left"], tabs["right"] = _with_caller_ids(tabs["left"]), _with_caller_ids(tabs["right"])
     prefixes = list(tabs)
@@ -569,7 +621,8 @@ def test_profiles(dev, entry, empty):
         pairs = [0] * len(ladder)
         best_l = {} if empty == "left" else {i: -1.0 for i in best_l}
         best_r = {} if empty == "right" else {j: -1.0 for j in best_r}
-    arena = _arena(f"{entry} {empty}", dev, ar.table_bytes(*tabs.values()) + _region_bytes(8 * len(ladder), 8 * ids_l, 8 * ids_r, 32))
+    arena = _arena(f"{entry} {empty}" + (f" {variant}" if variant else ""), dev,
+                   ar.table_bytes(*tabs.values()) + _region_bytes(8 * len(ladder), 8 * ids_l, 8 * ids_r, 32))
     homed = {p: ar.rehome(t, arena, p) for p, t in tabs.items()}
     structs = {p: homed[p].struct() for p in prefixes}
     if empty:
@@ -580,8 +633,8 @@ def test_profiles(dev, entry, empty):
     arena.fill("stats", np.array([11, 12, 13, 14], dtype=np.uint64))
     t = (ctypes.c_double * len(ladder))(*ladder)
     middle = (lib_module.FLAG_PRUNE,) if g.raw else (_mode_of(tabs, g), lib_module.FLAG_PRUNE, 0, 0)
-    _ok(getattr(lib, entry)(*structs.values(), t, len(ladder), *middle, arena.ptr("pairs"), arena.ptr("left_best"),
-                            arena.ptr("right_best"), arena.ptr("stats"), _stream(dev)), entry)
+    _ok(getattr(lib, entry)(*structs.values(), *_code(variant), t, len(ladder), *middle, arena.ptr("pairs"), arena.ptr("left_best"),
+                            arena.ptr("right_best"), arena.ptr("stats"), _stream(dev)), f"{entry} {variant or ''}")
     _sync(dev)
     arena.check(unchanged=inputs)
     assert arena.read("pairs", np.uint64).tolist() == pairs  # fully written
@@ -602,12 +655,24 @@ def test_profiles(dev, entry, empty):
 def test_listed_pairs(dev, entry):
     """"the call writes pairs[p].score and nothing else": the i and j bytes of every record, the id -> row maps and the
     guard behind the last record stay as they are; duplicates, ids outside the maps and ids whose map entry is -1."""
+    _pairs_case(dev, entry, mc.PAIRS_GRIDS[entry])
+
+
+@covers(*{e for e, _, _ in mc.additive(mc.PAIRS_GRIDS)})
+@pytest.mark.parametrize("entry,sibling,variant", mc.additive(mc.PAIRS_GRIDS))
+def test_listed_pairs_of_the_additive_headers(dev, entry, sibling, variant):
+    """``nsm_set_*_pairs`` and ``nsm_edit_*_pairs`` under every code but 0 on the sibling's grid and lists.  The grid keeps
+    its empty rows: a pair whose measure divides by zero gets -1.0, as nsm_hip_measures.h says."""
+    _pairs_case(dev, entry, mc.PAIRS_GRIDS[sibling], variant)
+
+
+def _pairs_case(dev, entry, name, variant=None):
     import torch
 
     from napkon_string_matching_amd import grid
 
     lib = _lib()[1]
-    g = tp.grid(mc.PAIRS_GRIDS[entry])
+    g = tp.grid(name)
     tabs = _one_row_tables(g, dev)
     prefixes = list(tabs)
     left, right = _item_tables(tabs)
@@ -615,7 +680,8 @@ def test_listed_pairs(dev, entry):
     assert lmap.numel() == len(g.left) and rmap.numel() == len(g.right) and int(lmap.min()) >= 0
     lmap[list(mc.UNMAPPED_LEFT)] = -1
     rmap[list(mc.UNMAPPED_RIGHT)] = -1
-    arena = _arena(entry, dev, ar.table_bytes(*tabs.values()) + _region_bytes(4 * lmap.numel(), 4 * rmap.numel()) +
+    arena = _arena(entry + (f" {variant}" if variant else ""), dev,
+                   ar.table_bytes(*tabs.values()) + _region_bytes(4 * lmap.numel(), 4 * rmap.numel()) +
                    sum(_region_bytes(16 * n) for n in mc.PAIR_COUNTS))
     homed = {p: ar.rehome(t, arena, p) for p, t in tabs.items()}
     structs = [homed[p].struct() for p in prefixes]
@@ -623,21 +689,89 @@ def test_listed_pairs(dev, entry):
     inputs = list(arena.regions)
     for n_pairs in mc.PAIR_COUNTS:
         pairs = mc.pair_list(g, n_pairs)
-        name = f"pairs@{n_pairs}"
-        arena.carve(name, 16 * n_pairs)
-        records = arena.poison(name, np.float64).reshape(-1, 2)  # (the scores stay random bytes)
+        region = f"pairs@{n_pairs}"
+        arena.carve(region, 16 * n_pairs)
+        records = arena.poison(region, np.float64).reshape(-1, 2)  # (the scores stay random bytes)
         ij = records.view(np.int32).reshape(-1, 4)
         ij[:, 2], ij[:, 3] = [p[0] for p in pairs], [p[1] for p in pairs]
-        arena.fill(name, records)
-        _ok(getattr(lib, entry)(*structs, lptr, int(lmap.numel()), rptr, int(rmap.numel()), arena.ptr(name), n_pairs, _stream(dev)), entry)
+        arena.fill(region, records)
+        _ok(getattr(lib, entry)(*structs, *_code(variant), lptr, int(lmap.numel()), rptr, int(rmap.numel()), arena.ptr(region), n_pairs,
+                                _stream(dev)), f"{entry} {variant or ''}")
         _sync(dev)
         arena.check(unchanged=inputs)
-        now = arena.read(name, np.float64).reshape(-1, 2)
+        now = arena.read(region, np.float64).reshape(-1, 2)
         assert now.view(np.int32).reshape(-1, 4)[:, 2:].tobytes() == ij[:, 2:].tobytes(), f"{entry}: i / j of a record written"
-        want = np.array(mc.pair_scores(g, pairs), dtype=np.float64)
+        want = np.array(mc.pair_scores(g, pairs, variant), dtype=np.float64)
         wrong = np.flatnonzero(now[:, 0].view(np.uint64) != want.view(np.uint64))
         assert wrong.size == 0, f"{entry} n_pairs={n_pairs}: records {wrong[:6].tolist()}: got {now[wrong[:6], 0].tolist()}, " \
                                 f"want {want[wrong[:6]].tolist()} for {[pairs[w] for w in wrong[:6]]}"
+
+
+# ---------------------------------------------------------------------------------------------------------- edge support
+def _support_call(dev, what, lists, nodes, min_score, min_support, with_stats):
+    """One ``nsm_support_hits`` call with every list's records, ``support[l]`` at exactly ``lists[l].n`` words and
+    ``stats`` at exactly 40 bytes (or NULL) in one arena.  Returns (status, arena, input regions)."""
+    lib_module, lib = _lib()
+    records = [mc.support_records(hits) for hits, _, _ in lists]
+    arena = _arena(what, dev, _region_bytes(40, *[r.nbytes for r in records], *[4 * len(r) for r in records]))
+    descs = (lib_module.NsmHitList * len(lists))()
+    out = (ctypes.c_void_p * len(lists))()
+    for k, (slot, rec, (_, left_base, right_base)) in enumerate(zip(descs, records, lists)):
+        if len(rec):
+            arena.carve(f"hits{k}", rec.nbytes)
+            arena.fill(f"hits{k}", rec)
+        slot.hits, slot.n = (arena.ptr(f"hits{k}") if len(rec) else None), len(rec)
+        slot.left_base, slot.left_ids, slot.right_base, slot.right_ids = left_base, nodes - left_base, right_base, nodes - right_base
+    inputs = list(arena.regions)
+    for k, rec in enumerate(records):
+        if len(rec):
+            arena.carve(f"support{k}", 4 * len(rec))
+        out[k] = arena.ptr(f"support{k}") if len(rec) else None
+    st = 0
+    if with_stats:
+        arena.carve("stats", 40)
+        arena.fill("stats", np.array(mc.SUPPORT_STATS_START, dtype=np.uint64))
+        st = arena.ptr("stats")
+    rc = lib.nsm_support_hits(descs, len(lists), nodes, float(min_score), min_support, out, st, _stream(dev))
+    _sync(dev)
+    return rc, arena, inputs
+
+
+@covers("nsm_support_hits")
+@pytest.mark.parametrize("with_stats", [True, False], ids=["stats", "stats_null"])
+@pytest.mark.parametrize("min_support", [0, 1])
+def test_support_hits(dev, min_support, with_stats):
+    """include/nsm_hip_support.h: ``support[l]`` has ``lists[l].n`` words, ``stats`` five, ADDED to; the hit lists are
+    inputs.  Four lists and one with ``n = 0`` (no records, no words: both pointers NULL); one counting pass and a peel."""
+    from napkon_string_matching_amd import grid
+
+    lists, nodes, min_score = mc.support_case()
+    words, rounds = grid.truss_of_hits(lists, nodes, min_support, min_score)
+    rc, arena, inputs = _support_call(dev, f"nsm_support_hits {min_support}", lists, nodes, min_score, min_support, with_stats)
+    _ok(rc, f"nsm_support_hits min_support={min_support}")
+    arena.check(unchanged=inputs)
+    for k, want in enumerate(words):
+        if len(want):
+            got = arena.read(f"support{k}", np.int32)
+            assert np.array_equal(got, want), f"list {k}: records {np.flatnonzero(got != want)[:6].tolist()}"
+    if with_stats:
+        edge_records, distinct = es.edge_counts(lists, nodes, min_score)
+        total, alive = es.final_triangles_x3(lists, nodes, words)
+        added = [edge_records, distinct, alive, rounds, total]
+        assert arena.read("stats", np.uint64).tolist() == [a + b for a, b in zip(mc.SUPPORT_STATS_START, added)]
+
+
+@covers("nsm_support_hits")
+@pytest.mark.parametrize("side", ["i", "j", "negative"])
+def test_support_hits_refuses_an_id_outside_its_list(dev, side):
+    """The header's check on the device: an id outside ``[0, left_ids)`` / ``[0, right_ids)`` -- whatever the record's
+    score -- returns NSM_E_BADARG BEFORE anything is written: ``support`` and ``stats`` still hold the arena's bytes."""
+    lib_module, lib = _lib()
+    lists, nodes, min_score = mc.support_case()
+    lists = mc.support_case_with_bad_id(lists, nodes, side)
+    rc, arena, inputs = _support_call(dev, f"nsm_support_hits bad {side}", lists, nodes, min_score, 1, True)
+    assert rc == NSM_E_BADARG and b"outside" in lib.nsm_last_error(), (rc, lib.nsm_last_error())
+    arena.check(unchanged=list(arena.regions))  # inputs, every support[l] and stats: as they were
 
 
 # ------------------------------------------------------------------------------------------------------------------ sort
@@ -883,10 +1017,34 @@ def test_build_level_items(dev, layout, rows):
 
 
 # ---------------------------------------------------------------------------------------------------------- the catalogue
+COVERED_HERE_BY_NAME = {"nsm_support_hits"}  # (its name has none of the kinds' endings; test_support_hits above)
+PINNED_ELSEWHERE = {"nsm_assign_hits": "test_gpu_assign.py", "nsm_group_hits": "test_gpu_groups.py",
+                    "nsm_span_hits": "test_gpu_forest.py"}  # entry -> the file whose arena test pins its memory contract
+
+
 def test_every_entry_with_caller_memory_is_covered():
-    """Every ``nsm_*`` grid, floor, top-k, profile, pairs, sort and build entry of the header has a case in this file."""
-    declared = set(re.findall(r"^(?:int|uint64_t)\s+(nsm_\w+)\(", HEADER.read_text(encoding="utf-8"), flags=re.M))
-    wanted = {e for e in declared if re.search(r"_grid$|_top_k|_profile$|_pairs$|^nsm_sort_hits$|^nsm_build_|_workspace_bytes$", e)}
-    assert len(wanted) == 29 and declared - wanted == {"nsm_abi_version", "nsm_release", "nsm_release_all"}, sorted(declared - wanted)
+    """Every ``nsm_*`` grid, floor, top-k, profile, pairs, sort and build entry of EVERY header ``include/nsm_hip*.h`` has a
+    case in this file, and so has ``nsm_support_hits``.  The three other hit-list entries are pinned in arena tests of their
+    own files, which must still import the arena and name the entry.  An entry of a new header is either of a known kind --
+    then it needs a case here -- or of none: then it has to be placed in one of the two lists by hand."""
+    declared = {}
+    for header in HEADERS:
+        for e in re.findall(r"^(?:int|uint64_t)\s+(nsm_\w+)\(", header.read_text(encoding="utf-8"), flags=re.M):
+            assert e not in declared, f"{e} is declared in {declared[e]} and in {header.name}"
+            declared[e] = header.name
+    assert [h.name for h in HEADERS] == ["nsm_hip.h", "nsm_hip_assign.h", "nsm_hip_edit.h", "nsm_hip_groups.h", "nsm_hip_measures.h",
+                                         "nsm_hip_span.h", "nsm_hip_support.h"]
+    kinds = r"_grid$|_top_k|_profile$|_pairs$|^nsm_sort_hits$|^nsm_build_|_workspace_bytes$"
+    wanted = {e for e in declared if re.search(kinds, e)} | COVERED_HERE_BY_NAME
+    per_header = {h.name: sum(1 for e in wanted if declared[e] == h.name) for h in HEADERS}
+    assert per_header == {"nsm_hip.h": 29, "nsm_hip_measures.h": 9, "nsm_hip_edit.h": 9, "nsm_hip_support.h": 1,
+                          "nsm_hip_assign.h": 0, "nsm_hip_groups.h": 0, "nsm_hip_span.h": 0}, per_header
+    assert len(wanted) == 48
+    assert set(declared) - wanted == {"nsm_abi_version", "nsm_release", "nsm_release_all"} | set(PINNED_ELSEWHERE), \
+        sorted(set(declared) - wanted)
     assert wanted == set(COVERED), (sorted(wanted - set(COVERED)), sorted(set(COVERED) - wanted))
     assert all(name in globals() for names in COVERED.values() for name in names)
+    for entry, file in PINNED_ELSEWHERE.items():
+        text = (Path(__file__).resolve().parent / file).read_text(encoding="utf-8")
+        assert re.search(r"^from support import arena\b", text, flags=re.M) and f'_lib.entry("{entry}")' in text and \
+            "arena.check(" in text, f"{file} no longer runs {entry} inside the guard-band arena"
